@@ -8,9 +8,10 @@ stream uses seed 3 + 1000003 g), dynamic heuristic 0.99999.  A "step" is one chu
 reads through the reference's chunk body
     place() (Q x B lookup sums) -> apply_heuristic() -> place_thorough() (NR placement).
 
-Two timed loops over the SAME chunks, both in the JSON line:
+A plain run times one loop and prints the headline:
   value            inputs resident in HBM when the clock starts, results left in HBM (the bench
-                   contract's definition of `value`): epa_dev_place_chunk on device buffers;
+                   contract's definition of `value`): epa_dev_place_chunk on device buffers.
+--full adds the secondary measurements to the same JSON line, among them a second timed loop over the SAME chunks,
   pcie_inclusive   SURVEY 8d's definition (H2D of the queries + D2H of the results inside the
                    step): the double-buffered epa_dev_chunk_stage / _launch / _finish pipeline,
                    4-bit wire format up, pairs + results down, copies on the copy stream.
@@ -19,14 +20,15 @@ job is --chunk x N reads, sharded with the reference's local_seq_package formula
 slices).  --scaling weak (default, the bench contract's K steps): per-GPU work fixed, total work
 grows with N.  --scaling strong --reads R: the job is R reads whatever N is, steps =
 ceil(R / (chunk x N)) -- BASELINE configs[3] (cfg4) is `--gpus 8 --scaling strong --reads 10000000`.
-Every default run ALSO times that fixed 10^7-read job on its N GPUs (`strong_cfg4` in the line), so
-that the driver's N = 1, 2, 4, 8 lines carry a strong-scaling curve next to the weak one.
+Every --full run ALSO times that fixed 10^7-read job on its N GPUs (`strong_cfg4` in the line), so
+that the N = 1, 2, 4, 8 lines carry a strong-scaling curve next to the weak one.
 The only exchange is the RCCL gather of the per-pair results to rank 0, overlapped, no per-chunk
 host synchronisation: the PRODUCT's gather (libepa_dev.so epa_comm_*, csrc/comm.hip); torch.distributed
 launches, barriers and broadcasts the 128-byte id (EPA_BENCH_GATHER=torch: the torch harness of the same
 protocol, epa_ng_amd/parallel.py).
 
-    python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full     # + roofline, PCIe loop, cfg4 job, CPU baseline, legs
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps 5 --warmup 1
 """
 import argparse
@@ -60,21 +62,26 @@ def parse():
     p.add_argument("--reads", type=int, default=0,
                    help="strong scaling: total reads of the job (steps = ceil(reads / (chunk x N)))")
     p.add_argument("--strong-reads", type=int, default=10000000,
-                   help="size of the fixed job timed as `strong_cfg4` (BASELINE configs[3]: 10^7 reads); 0 = skip")
+                   help="--full: size of the fixed job timed as `strong_cfg4` (BASELINE configs[3]: 10^7 reads); 0 = skip")
     p.add_argument("--pool", type=int, default=12,
                    help="distinct synthetic chunks resident per GPU; longer runs cycle through them")
     p.add_argument("--tips", type=int, default=512)
     p.add_argument("--width", type=int, default=1500)
     p.add_argument("--read-len", type=int, default=150)
-    p.add_argument("--cpu-sample", type=int, default=20000, help="reads timed on the CPU baseline")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--cpu-sample", type=int, default=20000, help="--full: reads timed on the CPU baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--parity-sample", type=int, default=0,
-                   help="with --no-cpu-baseline: still check this many reads of step 0 against the oracle (untimed)")
+                   help="--full with --no-cpu-baseline: still check this many reads of step 0 against the oracle (untimed)")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the secondary measurements (chunk-5000 rate, reference-binary hook)")
+                   help="--full: skip the extra legs (strong_cfg4, chunk-5000, cfg3 / cfg5, CLI, reference-binary hook)")
     p.add_argument("--serial-schedule", action="store_true",
                    help="run every loop in the serialised two-slot order (Newton launches never overlap): the command whose "
                         "kernel trace must agree with roofline.ms_per_launch (profiles/rN_kernel_trace_stats_serialised.txt)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements and checks: serialised pass + roofline, PCIe-inclusive loop, "
+                        "fixed-size strong_cfg4 job, CPU baseline + parity, chunk-5000, cfg3 / cfg5 legs, CLI end to end")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write the rows the last timed step computed as DIR/<name>.npy (float64)")
     p.add_argument("--workload", choices=["dna", "aa", "cfg5"], default="dna",
                    help="dna = cfg2 (the metric's config); aa = cfg3 shape (use --tips 2000 --width 500 "
                         "--read-len 100), a parity/measurement case, not the headline")
@@ -192,6 +199,22 @@ def sclk_fields(clks, exec_tflops):
                          "(profiles/r5_fma_clock.txt: the clock and cycles per FMA of a bare v_fma_f64 stream)"}
 
 
+def dump_outputs(d, arrays, limit=64 << 20):
+    """--dump-outputs: every array of `arrays` (the same number of rows each) as d/<name>.npy in float64.  Beyond
+    `limit` bytes in all, a fixed seeded sample of the rows is written instead, the same rows of every array, and
+    their indices as d/row_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    rows = limit // (8 * (len(arrays) + 1))
+    keep = None
+    if n * 8 * len(arrays) > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        arrays = dict(arrays, row_index=np.arange(n))
+    for k, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(d, k + ".npy"), v if keep is None else v[keep])
+
+
 def cfg5_leg(a):
     """BASELINE configs[4] shape on ONE GPU, the `prescoring == false` branch of the chunk body
     (src/core/place.cpp:219-231: Work = all B x Q pairs, every one gets the Newton-Raphson BLO): 4000-tip
@@ -240,7 +263,11 @@ def cfg5_leg(a):
                         "traffic": None, "traffic_source": "no PMC pass of this leg"},
            "eight_gpu_projection": "cfg5 = 10^6 reads over 8 GPUs = 125 000 reads = %.3g pairs per GPU: %.1f s at this rate"
                                    % (125000.0 * B, 125000.0 * B / (pairs / t_all))}
-    if a.parity_sample > 0:
+    if a.dump_outputs:              # the last timed call's placements, query by query, best first
+        dump_outputs(a.dump_outputs, {"seq_id": np.repeat(np.arange(Q), [len(g[0]) for g in got]),
+                                      **{k: np.concatenate([g[j] for g in got]) for j, k in
+                                         enumerate(("branch_id", "lnl", "pendant_length", "distal_length", "lwr"))}})
+    if a.full and a.parity_sample > 0:
         import oracle_lib
         from oracle_lib import Oracle
         hostlib.configure_threads()
@@ -700,20 +727,27 @@ def main():
             ev.chunk_launch(slot, threshold=0.99999, max_span=a.read_len, max_pairs=cap, pairs_out=bufs_deep[slot][0],
                             results_out=bufs_deep[slot][1], keep_on_device=True)
             ev.chunk_finish_device(slot)
-            _, hb0, hs0, wire0 = host_chunks[0]
-            ev.chunk_stage(slot, wire0, hb0, hs0)
-            ev.chunk_launch(slot, threshold=0.99999, max_span=a.read_len, max_pairs=cap)
-            ev.chunk_finish(slot, copy=False)
+            if a.full:                                   # the pinned bounce buffers of the PCIe loop
+                _, hb0, hs0, wire0 = host_chunks[0]
+                ev.chunk_stage(slot, wire0, hb0, hs0)
+                ev.chunk_launch(slot, threshold=0.99999, max_span=a.read_len, max_pairs=cap)
+                ev.chunk_finish(slot, copy=False)
         torch.cuda.synchronize()
     st_res, step_resident, fin_resident = make_loop_deep(True, exch)
     elapsed = timed(step_resident, fin_resident, "resident", record=False)
     # what the LAST TIMED step left in HBM (outside the clock): the rows the `parity` block checks
     last_i = a.warmup + a.steps - 1
     last_out = None
-    if rank == 0 and world == 1 and Q:
+    if rank == 0 and Q and (a.dump_outputs or (a.full and world == 1)):
         n_last = st_res["n_of_slot"].get(last_i % S_DEEP, 0)
         last_out = (last_i % n_chunks, bufs_deep[last_i % S_DEEP][0][:n_last].cpu().numpy().copy(),
                     bufs_deep[last_i % S_DEEP][1][:n_last].cpu().numpy().copy())
+    if rank == 0 and a.dump_outputs:
+        # what a caller of the chunk body receives for that chunk (N > 1: rank 0's own shard): the selected (branch,
+        # read) pairs and their optimised results, in the library's row order
+        pr, rs = (last_out[1], last_out[2]) if last_out else (np.zeros((0, 2)), np.zeros((0, 3)))
+        dump_outputs(a.dump_outputs, {"branch_id": pr[:, 0], "seq_id": pr[:, 1], "lnl": rs[:, 0],
+                                      "pendant_length": rs[:, 1], "distal_length": rs[:, 2]})
     # the serialised pass: the two-slot order, Newton launches never overlap -> per-launch kernel times for the roofline
     class NoGather:                # the serialised pass measures kernels, not the exchange: rows stay where they are
         carried_rows = 0
@@ -724,18 +758,20 @@ def main():
         def finish(self):
             pass
 
-    _, step_serial, fin_serial = make_loop(True, NoGather())
-    elapsed_serial = timed(step_serial, fin_serial, "serial", n_warm=1)
+    elapsed_serial = exch2 = None
+    if a.full:
+        _, step_serial, fin_serial = make_loop(True, NoGather())
+        elapsed_serial = timed(step_serial, fin_serial, "serial", n_warm=1)
 
-    # ---------------- loop 2: PCIe inside the step, overlapped on the copy streams
-    exch2 = make_gather(True)
-    state, step_pcie, finish_pcie = make_loop_deep(False, exch2)
-    elapsed_pcie = timed(step_pcie, finish_pcie, "pcie")
+        # ---------------- loop 2: PCIe inside the step, overlapped on the copy streams
+        exch2 = make_gather(True)
+        state, step_pcie, finish_pcie = make_loop_deep(False, exch2)
+        elapsed_pcie = timed(step_pcie, finish_pcie, "pcie")
 
     # ---------------- the fixed-size job of BASELINE configs[3] (cfg4: 10^7 reads) on these N GPUs:
     # ceil(R / (chunk x N)) steps of `chunk` reads per rank, inputs resident, gather to rank 0 included
     strong = None
-    if a.strong_reads and states == 4 and not a.no_extras and not (a.scaling == "strong" and a.reads):
+    if a.full and a.strong_reads and states == 4 and not a.no_extras and not (a.scaling == "strong" and a.reads):
         s_steps = -(-a.strong_reads // (a.chunk * world))
         el_s = timed(step_resident, fin_resident, "strong", n_timed=s_steps, n_warm=1, record=False)
         strong = {"reads": s_steps * a.chunk * world, "value": round(s_steps * a.chunk * world / el_s, 2),
@@ -754,96 +790,98 @@ def main():
 
     total_reads = a.steps * step_reads
     value = total_reads / elapsed
-    # ---------------- roofline of the dominant kernel (thorough NR), per launch
-    pairs = float(np.mean(th_pairs))
-    R = float(np.sum(th_rounds)) / float(np.sum(th_pairs))
-    kbar = float(np.sum(th_evals)) / max(1.0, 2.0 * float(np.sum(th_rounds)))
-    nq = a.read_len
-    if states == 4:
-        flops_pair = nq * (884.0 + R * (1258.0 + 240.0 * kbar))
-        # the initial inner CLV (2 x U products, the fold, the U^-1 product: 432 of the 884 flop
-        # per site) is served from the per-branch precompute of k_build_lookup, not recomputed
-        flops_exec = nq * (452.0 + R * (1258.0 + 240.0 * kbar))
-    else:  # same accounting with s = 20: P = c(4s^2+s), E = c(2s^2+2s), D = 6cs
-        P_, E_, D_ = 4 * (4 * 400 + 20), 4 * (2 * 400 + 40), 6 * 4 * 20
-        flops_pair = nq * ((2 * P_ + E_) + R * (4 * P_ + E_ + 2 * kbar * D_))
-        flops_exec = nq * (3 * 4 * 20 + R * (4 * P_ + E_ + 2 * kbar * D_))
-    cs = 4 * states
-    bytes_pair = 2 * nq * cs * 8 + 2 * nq * 4 + nq + 24
-    t_th = float(np.mean(th_ms)) * 1e-3
-    exec_tflops = pairs * flops_exec / t_th / 1e12
-    alg_tflops = pairs * flops_pair / t_th / 1e12
-    traffic = traffic_pre = None   # HBM bytes per launch from the committed PMC passes, same workload only
-    aa_mfma = states == 20 and a.read_len <= 192 and not os.environ.get("EPA_BENCH_AA_VALU")
-    kname = "k_thorough_dna" if states == 4 else ("k_thorough_aa_mfma" if aa_mfma else "k_thorough_aa")
-    # HBM bytes per launch come from the committed PMC passes of the SAME kernel sources (hash in the
-    # file, profiles/make_traffic.py) and the same workload; anything else reports null
-    traffic_note = "no PMC profile of these kernel sources and this workload under profiles/"
-    try:
-        sys.path.insert(0, os.path.join(ROOT, "profiles"))
-        from make_traffic import src_hash
-        here = src_hash()
-    except Exception:  # noqa: BLE001
-        here = None
-    for tf in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")), reverse=True):
+    roof = roof_pre = None
+    if a.full:
+        # ---------------- roofline of the dominant kernel (thorough NR), per launch
+        pairs = float(np.mean(th_pairs))
+        R = float(np.sum(th_rounds)) / float(np.sum(th_pairs))
+        kbar = float(np.sum(th_evals)) / max(1.0, 2.0 * float(np.sum(th_rounds)))
+        nq = a.read_len
+        if states == 4:
+            flops_pair = nq * (884.0 + R * (1258.0 + 240.0 * kbar))
+            # the initial inner CLV (2 x U products, the fold, the U^-1 product: 432 of the 884 flop
+            # per site) is served from the per-branch precompute of k_build_lookup, not recomputed
+            flops_exec = nq * (452.0 + R * (1258.0 + 240.0 * kbar))
+        else:  # same accounting with s = 20: P = c(4s^2+s), E = c(2s^2+2s), D = 6cs
+            P_, E_, D_ = 4 * (4 * 400 + 20), 4 * (2 * 400 + 40), 6 * 4 * 20
+            flops_pair = nq * ((2 * P_ + E_) + R * (4 * P_ + E_ + 2 * kbar * D_))
+            flops_exec = nq * (3 * 4 * 20 + R * (4 * P_ + E_ + 2 * kbar * D_))
+        cs = 4 * states
+        bytes_pair = 2 * nq * cs * 8 + 2 * nq * 4 + nq + 24
+        t_th = float(np.mean(th_ms)) * 1e-3
+        exec_tflops = pairs * flops_exec / t_th / 1e12
+        alg_tflops = pairs * flops_pair / t_th / 1e12
+        traffic = traffic_pre = None   # HBM bytes per launch from the committed PMC passes, same workload only
+        aa_mfma = states == 20 and a.read_len <= 192 and not os.environ.get("EPA_BENCH_AA_VALU")
+        kname = "k_thorough_dna" if states == 4 else ("k_thorough_aa_mfma" if aa_mfma else "k_thorough_aa")
+        # HBM bytes per launch come from the committed PMC passes of the SAME kernel sources (hash in the
+        # file, profiles/make_traffic.py) and the same workload; anything else reports null
+        traffic_note = "no PMC profile of these kernel sources and this workload under profiles/"
         try:
-            tall = json.load(open(os.path.join(ROOT, "profiles", tf)))
-            tj = tall[kname]
-            if tall.get("kernel_sources_sha16") != here:
-                continue
-            if tj["reads_per_step"] == Q and abs(tj["pairs_per_launch"] - pairs) < 0.02 * pairs:
-                # FETCH_SIZE x its calibrated correction (2.0 on gfx950, profiles/r2_traffic_calibration.txt)
-                traffic = (tall.get("fetch_correction", 1.0) * tj["fetch_kb"] + tj["write_kb"]) * 1024.0
-                traffic_pre = tall.get("k_preplace_pairs" if states == 4 else "k_preplace_sites")
-                if traffic_pre:
-                    traffic_pre = (tall.get("fetch_correction", 1.0) * traffic_pre["fetch_kb"] + traffic_pre["write_kb"]) * 1024.0
-                traffic_note = "profiles/" + tf
-                break
-        except (OSError, KeyError, ValueError):
+            sys.path.insert(0, os.path.join(ROOT, "profiles"))
+            from make_traffic import src_hash
+            here = src_hash()
+        except Exception:  # noqa: BLE001
+            here = None
+        for tf in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")), reverse=True):
+            try:
+                tall = json.load(open(os.path.join(ROOT, "profiles", tf)))
+                tj = tall[kname]
+                if tall.get("kernel_sources_sha16") != here:
+                    continue
+                if tj["reads_per_step"] == Q and abs(tj["pairs_per_launch"] - pairs) < 0.02 * pairs:
+                    # FETCH_SIZE x its calibrated correction (2.0 on gfx950, profiles/r2_traffic_calibration.txt)
+                    traffic = (tall.get("fetch_correction", 1.0) * tj["fetch_kb"] + tj["write_kb"]) * 1024.0
+                    traffic_pre = tall.get("k_preplace_pairs" if states == 4 else "k_preplace_sites")
+                    if traffic_pre:
+                        traffic_pre = (tall.get("fetch_correction", 1.0) * traffic_pre["fetch_kb"] + traffic_pre["write_kb"]) * 1024.0
+                    traffic_note = "profiles/" + tf
+                    break
+            except (OSError, KeyError, ValueError):
+                pass
+        roof = {"bound": "mfma" if aa_mfma else "fp64-valu", "kernel": kname,
+                "achieved": round(exec_tflops, 3), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(exec_tflops / FP64_PEAK_TFLOPS, 4),
+                "traffic": traffic, "traffic_source": traffic_note,
+                "note": ("achieved / frac price the fp64 flop the kernel EXECUTES (its 20 x 20 products and the Newton "
+                         "contraction are v_mfma_f64_4x4x4_4b_f64, no padding); " if aa_mfma else
+                         "achieved / frac price the fp64 flop the kernel EXECUTES (zero MFMA instructions: "
+                         "fp64 vector FMA kernel); ") + "*_algorithmic price SURVEY 8d's per-pair figure",
+                "peak_source": "AMD MI355X spec sheet, fp64 vector = fp64 matrix = 78.6 TFLOP/s (the microarch "
+                               "guide lists no fp64 row); measured ceiling of a dependency-free v_fma_f64 "
+                               "stream on this chip: %.1f TFLOP/s (profiles/r1_mfma_overlap.txt)" % FP64_MEASURED_CEILING,
+                "frac_of_measured_fma_ceiling": round(exec_tflops / FP64_MEASURED_CEILING, 4),
+                **sclk_fields(th_clk, exec_tflops),
+                "achieved_algorithmic": round(alg_tflops, 3), "frac_algorithmic": round(alg_tflops / FP64_PEAK_TFLOPS, 4),
+                "pairs_per_launch": pairs, "rounds_per_pair": round(R, 3), "newton_iters_per_solve": round(kbar, 3),
+                "flops_per_pair": round(flops_pair), "flops_executed_per_pair": round(flops_exec),
+                "ms_per_launch": round(t_th * 1e3, 4),
+                "hbm_algorithmic_GBs": round(pairs * bytes_pair / t_th / 1e9, 1),
+                "hbm_frac": round(pairs * bytes_pair / t_th / 1e9 / HBM_PEAK_GBS, 4)}
+        try:   # the XCDs' current shares of a Newton launch's pair list (epa_dev_xcd_shares; an eighth each = not adapted)
+            roof["xcd_shares"] = [round(float(x), 4) for x in ev.xcd_shares()]
+        except Exception:  # noqa: BLE001
             pass
-    roof = {"bound": "mfma" if aa_mfma else "fp64-valu", "kernel": kname,
-            "achieved": round(exec_tflops, 3), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(exec_tflops / FP64_PEAK_TFLOPS, 4),
-            "traffic": traffic, "traffic_source": traffic_note,
-            "note": ("achieved / frac price the fp64 flop the kernel EXECUTES (its 20 x 20 products and the Newton "
-                     "contraction are v_mfma_f64_4x4x4_4b_f64, no padding); " if aa_mfma else
-                     "achieved / frac price the fp64 flop the kernel EXECUTES (zero MFMA instructions: "
-                     "fp64 vector FMA kernel); ") + "*_algorithmic price SURVEY 8d's per-pair figure",
-            "peak_source": "AMD MI355X spec sheet, fp64 vector = fp64 matrix = 78.6 TFLOP/s (the microarch "
-                           "guide lists no fp64 row); measured ceiling of a dependency-free v_fma_f64 "
-                           "stream on this chip: %.1f TFLOP/s (profiles/r1_mfma_overlap.txt)" % FP64_MEASURED_CEILING,
-            "frac_of_measured_fma_ceiling": round(exec_tflops / FP64_MEASURED_CEILING, 4),
-            **sclk_fields(th_clk, exec_tflops),
-            "achieved_algorithmic": round(alg_tflops, 3), "frac_algorithmic": round(alg_tflops / FP64_PEAK_TFLOPS, 4),
-            "pairs_per_launch": pairs, "rounds_per_pair": round(R, 3), "newton_iters_per_solve": round(kbar, 3),
-            "flops_per_pair": round(flops_pair), "flops_executed_per_pair": round(flops_exec),
-            "ms_per_launch": round(t_th * 1e3, 4),
-            "hbm_algorithmic_GBs": round(pairs * bytes_pair / t_th / 1e9, 1),
-            "hbm_frac": round(pairs * bytes_pair / t_th / 1e9 / HBM_PEAK_GBS, 4)}
-    try:   # the XCDs' current shares of a Newton launch's pair list (epa_dev_xcd_shares; an eighth each = not adapted)
-        roof["xcd_shares"] = [round(float(x), 4) for x in ev.xcd_shares()]
-    except Exception:  # noqa: BLE001
-        pass
-    # preplacement kernel against the HBM roofline, SURVEY 8d's algorithmic bytes for ONE launch:
-    # query windows + the Q x B result table + one read of the lookup table
-    ncol = 16 if states == 4 else 24
-    pre_bytes = Q * nq + 8.0 * Q * B + 8.0 * ncol * W * B
-    t_pre = float(np.mean(pre_ms)) * 1e-3
-    roof_pre = {"bound": "hbm", "kernel": "k_preplace_pairs" if states == 4 else "k_preplace_sites",
-                "achieved": round(pre_bytes / t_pre / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(pre_bytes / t_pre / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic_pre,
-                "algorithmic_bytes_per_launch": pre_bytes,
-                "ms_per_launch": round(t_pre * 1e3, 4),
-                # the kernel's own unit of work: one 8-byte LDS gather per (query, branch, site pair) [DNA]
-                # or site [20 states], against the LDS rate of ds_read_b64 (32 lanes / clk / CU, 256 CUs, 2.4 GHz)
-                "lds_gathers_per_launch": float(Q) * B * (nq / 2.0 if states == 4 else nq),
-                "lds_gather_frac": round(float(Q) * B * (nq / 2.0 if states == 4 else nq) / t_pre / (256 * 32 * 2.4e9), 4)}
+        # preplacement kernel against the HBM roofline, SURVEY 8d's algorithmic bytes for ONE launch:
+        # query windows + the Q x B result table + one read of the lookup table
+        ncol = 16 if states == 4 else 24
+        pre_bytes = Q * nq + 8.0 * Q * B + 8.0 * ncol * W * B
+        t_pre = float(np.mean(pre_ms)) * 1e-3
+        roof_pre = {"bound": "hbm", "kernel": "k_preplace_pairs" if states == 4 else "k_preplace_sites",
+                    "achieved": round(pre_bytes / t_pre / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(pre_bytes / t_pre / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic_pre,
+                    "algorithmic_bytes_per_launch": pre_bytes,
+                    "ms_per_launch": round(t_pre * 1e3, 4),
+                    # the kernel's own unit of work: one 8-byte LDS gather per (query, branch, site pair) [DNA]
+                    # or site [20 states], against the LDS rate of ds_read_b64 (32 lanes / clk / CU, 256 CUs, 2.4 GHz)
+                    "lds_gathers_per_launch": float(Q) * B * (nq / 2.0 if states == 4 else nq),
+                    "lds_gather_frac": round(float(Q) * B * (nq / 2.0 if states == 4 else nq) / t_pre / (256 * 32 * 2.4e9), 4)}
 
     extras = {}
     # ---------------- CPU baseline: the oracle's OpenMP restatement on a bounded sample
     cpu = None
     parity = None
-    if (not a.no_cpu_baseline or a.parity_sample > 0) and world == 1:   # rank 0 at N=1 only (bench contract)
+    if a.full and (not a.no_cpu_baseline or a.parity_sample > 0) and world == 1:   # rank 0 at N=1 only (bench contract)
         # the oracle's OpenMP threads = the CPUs this process may really use (a container can see
         # 256 CPUs and be limited to 16 by its cgroup quota: oversubscribing would slow the baseline)
         eff = hostlib.configure_threads()
@@ -924,7 +962,7 @@ def main():
                                                                          "/".join(map(repr, freqs)), alpha))
             extras["reference_binary"] = reference_binary_check(newick, labels, seqs, hc[:nref], hb[:nref], hs[:nref],
                                                                 W, states, model, best)
-    if world == 1 and not a.no_extras and Q >= 5000:
+    if a.full and world == 1 and not a.no_extras and Q >= 5000:
         # the reference's default chunk size (--chunk-size 5000, src/util/Options.hpp) through the
         # same double-buffered pipeline: 40 chunks cut from step 0's reads, PCIe inside the clock
         hc, hb, hs, wire = host_chunks[last_i % n_chunks]
@@ -1011,13 +1049,13 @@ def main():
                                        "staged chunks (twelve slots, two groups begun ahead); per chunk the same bits as a launch of its own",
                                "per_chunk_launch": per_chunk}
 
-    if world == 1 and states == 4 and not a.no_extras and not os.environ.get("EPA_BENCH_NO_CFG3"):
+    if a.full and world == 1 and states == 4 and not a.no_extras and not os.environ.get("EPA_BENCH_NO_CFG3"):
         # BASELINE configs[2] (cfg3: 2000-tip 20-state reference, 100-residue queries) as a short second
         # measurement by the same script in its own process, so that the driver's line carries it too
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "aa", "--tips", "2000", "--width", "500",
                                 "--read-len", "100", "--chunk", "50000", "--steps", "6", "--warmup", "2", "--pool", "3",
-                                "--cpu-sample", "1000", "--no-extras"],
+                                "--cpu-sample", "1000", "--no-extras", "--full"],
                                capture_output=True, text=True, timeout=900)
             aj = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
             extras["cfg3_aa"] = {"value": aj["value"], "unit": aj["unit"], "ms_per_step": aj["ms_per_step"],
@@ -1036,12 +1074,12 @@ def main():
         # BASELINE configs[4] (cfg5) at a 2000-read sample of one GPU's shard: --no-heur, every pair optimised
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "cfg5", "--chunk", "2000", "--steps", "3",
-                                "--warmup", "1", "--parity-sample", "6"], capture_output=True, text=True, timeout=900)
+                                "--warmup", "1", "--parity-sample", "6", "--full"], capture_output=True, text=True, timeout=900)
             extras["cfg5_noheur"] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         except Exception as e:  # noqa: BLE001
             extras["cfg5_noheur"] = {"status": "failed: %r" % (e,)}
 
-    if world == 1 and states == 4 and not a.no_extras and not os.environ.get("EPA_BENCH_NO_CLI"):
+    if a.full and world == 1 and states == 4 and not a.no_extras and not os.environ.get("EPA_BENCH_NO_CLI"):
         try:
             nrd = int(os.environ.get("EPA_BENCH_CLI_READS", "1000000"))
             use = [(c, b, s_) for c, b, s_, _ in host_chunks[:max(1, -(-nrd // max(Q, 1)))]]
@@ -1052,18 +1090,20 @@ def main():
 
     metric = ("query placements/sec (whole node), 512-tip GTR+G4 DNA ref, preplace+thorough" if states == 4
               else "query placements/sec (whole node), AA PROTGTR+G4 ref (cfg3 shape), preplace+thorough")
-    pcie = {"value": round(total_reads / elapsed_pcie, 2), "unit": "placements/s",
-            "ms_per_step": round(elapsed_pcie / a.steps * 1e3, 3),
-            "h2d_bytes_per_step": state["bytes_up"] // max(1, n_steps),
-            "d2h_bytes_per_step": state["bytes_down"] // max(1, n_steps),
-            "host_ms_per_step": {"stage (memcpy to pinned + H2D enqueue)": round(state["t_stage"] / max(1, a.steps - 1) * 1e3, 3),
-                                 "launch_begin (queues preplacement + selection)": round(state["t_launch"] / a.steps * 1e3, 3),
-                                 "finish (wait for the previous chunk's kernels + D2H)": round(state["t_finish"] / max(1, a.steps - 1) * 1e3, 3),
-                                 "launch_end (waits for the candidate count, queues the Newton kernels)": round(state["t_end"] / a.steps * 1e3, 3)},
-            "how": "per step: launch_begin(i); finish(i-1); stage(i+1); launch_end(i) -- %s codes + windows up, "
-                   "pairs + results down, copies on the copy streams under the previous / next chunk's kernels%s"
-                   % ("4-bit" if states == 4 else "1-byte",
-                      "; N > 1: results gathered over RCCL to rank 0, which copies them to the host" if world > 1 else "")}
+    pcie = None
+    if a.full:
+        pcie = {"value": round(total_reads / elapsed_pcie, 2), "unit": "placements/s",
+                "ms_per_step": round(elapsed_pcie / a.steps * 1e3, 3),
+                "h2d_bytes_per_step": state["bytes_up"] // max(1, n_steps),
+                "d2h_bytes_per_step": state["bytes_down"] // max(1, n_steps),
+                "host_ms_per_step": {"stage (memcpy to pinned + H2D enqueue)": round(state["t_stage"] / max(1, a.steps - 1) * 1e3, 3),
+                                     "launch_begin (queues preplacement + selection)": round(state["t_launch"] / a.steps * 1e3, 3),
+                                     "finish (wait for the previous chunk's kernels + D2H)": round(state["t_finish"] / max(1, a.steps - 1) * 1e3, 3),
+                                     "launch_end (waits for the candidate count, queues the Newton kernels)": round(state["t_end"] / a.steps * 1e3, 3)},
+                "how": "per step: launch_begin(i); finish(i-1); stage(i+1); launch_end(i) -- %s codes + windows up, "
+                       "pairs + results down, copies on the copy streams under the previous / next chunk's kernels%s"
+                       % ("4-bit" if states == 4 else "1-byte",
+                          "; N > 1: results gathered over RCCL to rank 0, which copies them to the host" if world > 1 else "")}
     out = {"metric": metric,
            "value": round(value, 2), "unit": "placements/s", "n_gpus": world, "steps": a.steps,
            "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
@@ -1072,8 +1112,8 @@ def main():
                         "slots": S_DEEP, "chunks_begun_ahead": 0 if a.serial_schedule else A_DEEP,
                         "ms_per_step_serialised_two_slot_order": (round(elapsed_serial / a.steps * 1e3, 3) if elapsed_serial else None),
                         "note": "value / ms_per_step: the deep pipeline (chunk k's Newton kernel queued into chunk k-1's tail; the "
-                                "order the CLI's chunk loop runs); roofline.ms_per_launch, kernel_ms_per_step, sclk: a serialised "
-                                "pass of the two-slot order over the same chunks, where launches do not overlap"},
+                                "order the CLI's chunk loop runs); roofline.ms_per_launch, kernel_ms_per_step, sclk (--full): a "
+                                "serialised pass of the two-slot order over the same chunks, where launches do not overlap"},
            "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None, "dtype": "f64",
            "data": "synthetic",
            "config": {"workload": ("cfg2: %d-tip DNA GTR+G4 ref, W=%d, %d bp reads, dyn-heur 0.99999, "
@@ -1085,9 +1125,9 @@ def main():
                       "value_definition": "inputs resident in HBM when the clock starts (bench contract); "
                                           "see pcie_inclusive for SURVEY 8d's H2D/D2H-inclusive rate",
                       "lookup_build_ms_once": round(lookup_ms, 3),
-                      "kernel_ms_per_step": {"preplace": round(float(np.mean(pre_ms)), 3),
-                                             "select": round(float(np.mean(sel_ms)), 3),
-                                             "thorough": round(float(np.mean(th_ms)), 3)}},
+                      "kernel_ms_per_step": ({"preplace": round(float(np.mean(pre_ms)), 3),
+                                              "select": round(float(np.mean(sel_ms)), 3),
+                                              "thorough": round(float(np.mean(th_ms)), 3)} if a.full else None)},
            "pcie_inclusive": pcie, "strong_cfg4": strong,
            "rccl_ranks": world if (world > 1 and (dist.get_backend() == "nccl" if gather_path == "torch"
                                                   else not os.environ.get("EPA_RCCL_LIB"))) else 0,
@@ -1102,7 +1142,7 @@ def main():
                        "rccl_path": gather_info["rccl_path"], "devices": gather_info["devices"],
                        "distinct_devices": len(set(gather_info["devices"] or [])),
                        "probe_seconds": gather_info["probe_seconds"],
-                       "rows_cap": rows_cap, "carried_rows_rank0": int(exch.carried_rows + exch2.carried_rows),
+                       "rows_cap": rows_cap, "carried_rows_rank0": int(exch.carried_rows + (exch2.carried_rows if exch2 else 0)),
                        "rows_collected_rank0": (int(getattr(exch, "rows_seen", 0) + getattr(exch2, "rows_seen", 0)) if gather_path != "torch" else None)}
                       if world > 1 else None),
            "per_rank_ms_per_step": [round(x / a.steps * 1e3, 3) for x in rank_elapsed["resident"]],

@@ -6,7 +6,7 @@ for rep in 1 2 3; do
     unset EPA_DEV_SO EPA_BENCH_OPTS
     [ $v = spec ] && export EPA_DEV_SO=$PWD/exp/libepa_dev_spec.so
     [ $v = stag ] && export EPA_BENCH_OPTS=preplace_stagger=1
-    python bench.py --steps 10 --warmup 4 --no-cpu-baseline --no-extras > /tmp/v.log 2>/tmp/v.err
+    python bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --no-extras > /tmp/v.log 2>/tmp/v.err
     echo "== $v (rep $rep)" >> $out
     python - >> $out <<PY
 import json

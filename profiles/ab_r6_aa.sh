@@ -2,7 +2,7 @@
 # same-box A/B of the 20-state kernel: one barrier per Newton evaluation (product) against the two-barrier form
 # (variant library exp/libepa_dev_aa2b.so = -DAAM_PRIVATE_TABLES=0), cfg3 shape, three interleaved rounds
 out=gpurun_out/r6_aa_ab.txt; : > $out
-AA="--workload aa --tips 2000 --width 500 --read-len 100 --chunk 50000 --pool 3 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+AA="--full --workload aa --tips 2000 --width 500 --read-len 100 --chunk 50000 --pool 3 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
 for rep in 1 2 3; do
   for v in base aa2b; do
     unset EPA_DEV_SO

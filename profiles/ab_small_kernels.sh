@@ -9,7 +9,7 @@ run() {   # name, env...
   name=$1; shift
   rm -rf /tmp/abst
   env "$@" timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/abst -o st -- \
-    python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras > /tmp/ab.log 2>&1
+    python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras > /tmp/ab.log 2>&1
   echo "== $name ($*)" >> $out
   grep -o '"value": [0-9.]*, "unit"' /tmp/ab.log | head -1 >> $out
   grep -o '"kernel_ms_per_step": {[^}]*}' /tmp/ab.log | head -1 >> $out

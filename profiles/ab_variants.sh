@@ -9,7 +9,7 @@ for rep in 1 2; do
     lib=${v%%+*}
     case $v in *+db) export EPA_PREPLACE_DB=1;; *+duo) export EPA_PREPLACE_DUO=1;; esac
     if [ $lib = base ]; then unset EPA_DEV_SO; else export EPA_DEV_SO=$PWD/exp/libepa_dev_$lib.so; fi
-    python bench.py --steps 10 --warmup 4 --no-cpu-baseline --no-extras $BENCH_ARGS > /tmp/v.log 2>/tmp/v.err
+    python bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --no-extras $BENCH_ARGS > /tmp/v.log 2>/tmp/v.err
     echo "== $v (rep $rep)" >> $out
     grep -o '"value": [0-9.]*, "unit"' /tmp/v.log | head -1 >> $out
     grep -o '"kernel_ms_per_step": {[^}]*}' /tmp/v.log | head -1 >> $out

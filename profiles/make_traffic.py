@@ -7,6 +7,7 @@ without a profile refresh gives null, not stale bytes).
 import hashlib, json, os, re, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("EPA_PROF_OUT", os.path.join(ROOT, "prof_out"))   # the PMC summaries of run_round.sh
 
 
 def src_hash():
@@ -36,7 +37,7 @@ def parse(path):
 if __name__ == "__main__":
     tag = sys.argv[1]
     reads, pairs = int(sys.argv[2]), float(sys.argv[3])
-    dna = parse(os.path.join(ROOT, "gpurun_out", tag + "_pmc_summary.txt"))
+    dna = parse(os.path.join(OUT, tag + "_pmc_summary.txt"))
     out = {"_comment": "HBM-side traffic per launch from rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE in separate "
                        "runs; KB), bench.py default workload.  bytes = 2 x FETCH_SIZE + WRITE_SIZE: the factor is "
                        "calibrated on known byte counts (profiles/r2_traffic_calibration.txt: on gfx950 FETCH_SIZE "
@@ -48,12 +49,12 @@ if __name__ == "__main__":
             if name == "k_thorough_dna":
                 out[name]["pairs_per_launch"] = pairs
     if len(sys.argv) > 5:
-        aa = parse(os.path.join(ROOT, "gpurun_out", tag + "_aa_pmc_summary.txt"))
+        aa = parse(os.path.join(OUT, tag + "_aa_pmc_summary.txt"))
         if "k_preplace_sites" in aa and "FETCH_SIZE" in aa["k_preplace_sites"]:
             out["k_preplace_sites"] = {"reads_per_step": int(sys.argv[4]), "fetch_kb": aa["k_preplace_sites"]["FETCH_SIZE"],
                                        "write_kb": aa["k_preplace_sites"].get("WRITE_SIZE", 0.0)}
         if "k_thorough" in aa and "FETCH_SIZE" in aa["k_thorough"]:
             out["k_thorough_aa_mfma"] = {"reads_per_step": int(sys.argv[4]), "pairs_per_launch": float(sys.argv[5]),
                                          "fetch_kb": aa["k_thorough"]["FETCH_SIZE"], "write_kb": aa["k_thorough"].get("WRITE_SIZE", 0.0)}
-    json.dump(out, open(os.path.join(ROOT, "gpurun_out", tag + "_traffic.json"), "w"), indent=1)
+    json.dump(out, open(os.path.join(OUT, tag + "_traffic.json"), "w"), indent=1)
     print(json.dumps(out)[:400])

@@ -1415,7 +1415,7 @@ def test_bench_two_ranks_on_one_gpu(scaling, gather):
         import fake_rccl_util
         env = fake_rccl_util.env(env)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--chunk", "6000", "--tips", "64", "--width", "600", "--scaling", scaling, "--no-cpu-baseline"]
+           "--chunk", "6000", "--tips", "64", "--width", "600", "--scaling", scaling, "--no-cpu-baseline", "--full"]
     # strong: a fixed job of 36 000 reads = 3 steps of 2 x 6000; weak: the 3 steps asked for, plus the
     # fixed-size `strong_cfg4` leg (48 000 reads = 4 steps per rank, cycling through the resident chunks)
     cmd += ["--reads", "36000", "--pool", "2"] if scaling == "strong" else ["--strong-reads", "48000", "--pool", "3"]
@@ -1444,6 +1444,41 @@ def test_bench_two_ranks_on_one_gpu(scaling, gather):
         assert g["rows_collected_rank0"] > 2 * 6000      # both loops' rows of both ranks reached rank 0
     else:
         assert g["path"].startswith("torch.distributed")
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain bench run (no --full): exactly --steps timed steps, the headline fields and nothing of the secondary
+    measurements; --dump-outputs writes the rows the last timed step left, which equal a place_chunk call of the
+    same seeded chunk bit for bit"""
+    import subprocess
+    import sys
+    steps, warmup, pool, chunk = 3, 1, 2, 3000
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--chunk", str(chunk), "--tips", "64", "--width", "600", "--pool", str(pool), "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == steps and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["unit"] == "placements/s" and line["metric"].startswith("query placements/sec")
+    assert abs(line["value"] - chunk / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    assert line["roofline"] is None and line["pcie_inclusive"] is None and line["cpu_baseline"] is None
+    assert line["strong_cfg4"] is None and "cfg3_aa" not in line and "cli_e2e" not in line
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("branch_id", "seq_id", "lnl", "pendant_length", "distal_length")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    # the bench's workload: step i places chunk i % n_chunks, chunk g drawn with seed 3 + 1000003 g
+    n_chunks = min(steps + warmup, max(pool, warmup + 2))
+    g = (steps + warmup - 1) % n_chunks
+    root = synth.random_tree(64, 1)
+    rates = synth.gamma_rates(synth.CFG2_ALPHA)
+    labels, seqs = synth.simulate_msa(root, 600, synth.CFG2_SUBST, synth.CFG2_FREQS, rates, 2)
+    ref = hostlib.Reference(synth.newick(root), labels, seqs, states=4, subst=synth.CFG2_SUBST, freqs=synth.CFG2_FREQS,
+                            rates=rates)
+    codes, wb, ws = synth.make_reads_compact(seqs, chunk, 150, 0.03, 3 + 1000003 * g, 4)
+    pairs, res = ref.evaluator().place_chunk(codes, wb, ws, threshold=0.99999, max_span=150)
+    assert len(pairs) > chunk
+    assert np.array_equal(got["branch_id"], pairs["branch_id"]) and np.array_equal(got["seq_id"], pairs["seq_id"])
+    for k in ("lnl", "pendant_length", "distal_length"):
+        assert np.array_equal(got[k], res[k]), k
 
 
 def test_bench_two_ranks_transport_that_hangs_falls_back_within_the_probe_timeout():
@@ -1590,7 +1625,7 @@ def test_bench_over_rccl_on_all_visible_gpus():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = _run_ranks([os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
                        "--chunk", "20000", "--strong-reads", str(20000 * n * 4), "--pool", "3",
-                       "--no-cpu-baseline"], n, timeout=900)
+                       "--no-cpu-baseline", "--full"], n, timeout=900)
     line = json.loads([l for l in outs[0][0].splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == n and line["rccl_ranks"] == n
     assert line["gather"]["path"].startswith("epa_comm") and line["gather"]["transport"] == "RCCL"
