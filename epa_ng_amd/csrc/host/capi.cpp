@@ -3,6 +3,7 @@
 #include <cstring>
 #include <fstream>
 #include <sstream>
+#include <stdexcept>
 
 #include "epa_host.hpp"
 
@@ -222,7 +223,9 @@ int epa_host_place_file(void* h, const char* query_file, const char* outdir, uin
     Options o = r->opt;
     if (chunk_size) { o.chunk_size = chunk_size; o.chunk_size_given = true; o.device_min_chunk = 0; }   // the harness asks for exact chunks
     o.prescoring = prescoring != 0;
-    if (prescoring_threshold > 0) o.prescoring_threshold = prescoring_threshold;
+    // a negative threshold keeps the default; 0 is a valid one (keeps no candidates, src/main.cpp:205-218)
+    if (prescoring_threshold > 1.0) throw std::range_error{"prescoring threshold outside of [0,1]"};
+    if (prescoring_threshold >= 0) o.prescoring_threshold = prescoring_threshold;
     o.premasking = premasking != 0;
     const Run_Stats st = simple_mpi(*r->tree, query_file, outdir, o, invocation ? invocation : "epa_host_place_file", device);
     if (n_queries) *n_queries = st.queries;
@@ -249,6 +252,25 @@ int epa_host_filter(const double* lwr, uint32_t n, double thresh, int acc, uint3
     filter(s, o);
     *n_kept = (uint32_t)s[0].size();
     for (uint32_t i = 0; i < *n_kept; ++i) kept_branch_ids[i] = (uint32_t)s[0][i].branch_id();
+  });
+}
+
+// the pipeline's post-processing of one pquery: compute_and_set_lwr + filter on placements (lnl[i] on branch[i]),
+// so the tie rule (lnL descending, then branch id) is what decides among equal LWRs
+int epa_host_filter_pquery(const double* lnl, const uint32_t* branch, uint32_t n, double thresh, int acc,
+                           uint32_t mn, uint32_t mx, uint32_t* kept_branch_ids, double* kept_lwr, uint32_t* n_kept) {
+  return guarded([&] {
+    Sample s(1);
+    for (uint32_t i = 0; i < n; ++i) s[0].emplace_back(branch[i], lnl[i], 0.0, 0.0);
+    Options o;
+    o.support_threshold = thresh; o.acc_threshold = acc != 0; o.filter_min = mn; o.filter_max = mx;
+    compute_and_set_lwr(s);
+    filter(s, o);
+    *n_kept = (uint32_t)s[0].size();
+    for (uint32_t i = 0; i < *n_kept; ++i) {
+      kept_branch_ids[i] = (uint32_t)s[0][i].branch_id();
+      kept_lwr[i] = s[0][i].lwr();
+    }
   });
 }
 

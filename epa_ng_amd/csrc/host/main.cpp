@@ -133,6 +133,16 @@ int main(int argc, char** argv) {
     else { std::cerr << "option " << a << " is outside the placement hot path of this build\n"; return 1; }
   }
   if (tree_file.empty() || ref_file.empty() || query_file.empty()) { usage(); return 1; }
+  // the reference's CLI checks (src/main.cpp:165-218, 368-370)
+  if (!(opt.prescoring_threshold >= 0.0 && opt.prescoring_threshold <= 1.0)) {
+    std::cerr << "-g / -G: " << opt.prescoring_threshold << " not in [0, 1]\n";
+    return 1;
+  }
+  if (!(opt.support_threshold >= 0.0 && opt.support_threshold <= 1.0)) {
+    std::cerr << "--filter-acc-lwr / --filter-min-lwr: " << opt.support_threshold << " not in [0, 1]\n";
+    return 1;
+  }
+  if (opt.filter_min > opt.filter_max) { std::cerr << "filter-min must not exceed filter-max!\n"; return 1; }
   try {
     std::ifstream tf(tree_file);
     if (!tf) throw std::runtime_error{"file_check failed: " + tree_file};

@@ -183,12 +183,14 @@ Work apply_heuristic(const std::vector<double>& lnl, size_t Q, size_t B, const O
     for (long q = 0; q < (long)Q; ++q) {
       const double* row = &lnl[(size_t)q * B];
       std::iota(order.begin(), order.end(), 0u);
+      // selection order of every rule: lnL descending, ties by the lowest branch id ("Tie rule")
+      const auto by_lnl = [row](uint32_t a, uint32_t b) { return row[a] > row[b] || (row[a] == row[b] && a < b); };
       size_t n_keep = 0;
       if (options.baseball) {
         // baseball_heuristic (src/core/heuristics.hpp:70-117); quirk D7: clamp at B
         const double strike_box = 3, best = *std::max_element(row, row + B);
         const size_t max_strikes = 6, max_pitches = 40;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return row[a] > row[b]; });
+        std::sort(order.begin(), order.end(), by_lnl);
         size_t hits = 0;
         while (hits < B && !(row[order[hits]] < best - strike_box)) ++hits;
         // size_t arithmetic of heuristics.hpp:107: the difference wraps when hits > max_pitches
@@ -196,15 +198,15 @@ Work apply_heuristic(const std::vector<double>& lnl, size_t Q, size_t B, const O
         n_keep = std::min(B, hits + to_add);
       } else {
         row_lwr(row, B, lwr);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lwr[a] > lwr[b]; });
+        std::sort(order.begin(), order.end(), by_lnl);
         if (options.prescoring_by_percentage) {
           // until_top_percent (src/set_manipulators.cpp:82-88)
           n_keep = std::min(B, (size_t)std::ceil(options.prescoring_threshold * (double)B));
         } else {
-          // until_accumulated_reached(pq, thresh, 1, inf) (:90-114)
+          // until_accumulated_reached(pq, thresh, 1, inf) (:90-114): the crossing element is included;
+          // a threshold <= 0 keeps none (the top-up goes to min - 1 = 0)
           double sum = 0.0;
           while (n_keep < B && sum < options.prescoring_threshold) sum += lwr[order[n_keep++]];
-          if (n_keep < 1) n_keep = 1;
         }
       }
       keep[q].assign(order.begin(), order.begin() + n_keep);
@@ -394,9 +396,16 @@ void compute_and_set_lwr(Sample& sample) {
   }
 }
 
+// sort_by_lwr (src/set_manipulators.cpp:71-74) with the tie rule of the device ("Tie rule"): LWR
+// descending, then lnL descending, then the lowest branch id.  LWR is monotone in lnL, so for LWRs computed from
+// the lnLs (compute_and_set_lwr) this is "lnL descending, then branch id": equal LWRs of different lnL (both 0
+// after underflow) are ordered by lnL, not by their position in the pquery
 static void sort_by_lwr(PQuery& pq) {
-  std::stable_sort(pq.begin(), pq.end(),
-                   [](const Placement& a, const Placement& b) { return a.lwr() > b.lwr(); });
+  std::sort(pq.begin(), pq.end(), [](const Placement& a, const Placement& b) {
+    if (a.lwr() != b.lwr()) return a.lwr() > b.lwr();
+    if (a.likelihood() != b.likelihood()) return a.likelihood() > b.likelihood();
+    return a.branch_id() < b.branch_id();
+  });
 }
 
 void filter(Sample& sample, const Options& options) {
@@ -405,6 +414,8 @@ void filter(Sample& sample, const Options& options) {
   if (thresh < 0.0 || thresh > 1.0)
     throw std::range_error{"thresh is not a valid likelihood weight ratio (outside of [0,1])"};
   if (options.filter_min < 1) throw std::range_error{"Filter min cannot be smaller than 1!"};
+  if (options.acc_threshold && options.filter_min > options.filter_max)
+    throw std::range_error{"Filter min cannot be smaller than max!"};   // (sic, :175-177)
   const size_t mn = options.filter_min, mx = options.filter_max;
 #pragma omp parallel for schedule(static)
   for (long i = 0; i < (long)sample.size(); ++i) {
@@ -419,9 +430,11 @@ void filter(Sample& sample, const Options& options) {
       if (n_keep + 1 < mn) n_keep = std::min(pq.size(), mn - 1);
     } else {
       // discard_by_support_threshold (:131-163)
-      while (n_keep < pq.size() && pq[n_keep].lwr() > thresh) ++n_keep;
-      if (n_keep < mn) n_keep = std::min(pq.size(), mn);
-      if (mx && n_keep > mx) n_keep = mx;
+      // (the max clamp looks at the count before the min top-up, :151-159)
+      size_t above = 0;
+      while (above < pq.size() && pq[above].lwr() > thresh) ++above;
+      n_keep = above < mn ? std::min(pq.size(), mn) : above;
+      if (mx && above > mx) n_keep = mx;
     }
     pq.placements().resize(n_keep);
   }

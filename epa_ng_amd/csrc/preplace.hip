@@ -1178,8 +1178,9 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_sites(
 // src/core/heuristics.hpp:40-68; compute_and_set_lwr src/set_manipulators.cpp:43-69;
 // until_accumulated_reached :90-114).  One wave per query, the row of B log-likelihoods in
 // registers (NR values per lane); the largest remaining LWR is extracted until the running sum
-// reaches `threshold` (the crossing element is included, min 1).  Ties: lowest branch id first
-// (the reference's std::sort is unstable).  Selections go to stage[q][0..cap).
+// reaches `threshold` (the crossing element is included; a threshold <= 0 selects none, as the
+// reference's top-up to min - 1 = 0 does).  Ties: lowest branch id first (the reference's std::sort
+// is unstable; the host rules use the same order).  Selections go to stage[q][0..cap).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll

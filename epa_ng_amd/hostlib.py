@@ -60,6 +60,8 @@ def host_lib():
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.epa_host_filter.argtypes = [dp, C.c_uint32, C.c_double, C.c_int, C.c_uint32, C.c_uint32,
                                       u32p, u32p]
+        L.epa_host_filter_pquery.argtypes = [dp, u32p, C.c_uint32, C.c_double, C.c_int, C.c_uint32, C.c_uint32,
+                                             u32p, dp, u32p]
         L.epa_host_heuristic.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_int, C.c_double, u32p,
                                          u32p, C.c_uint64, C.POINTER(C.c_uint64)]
         _LIB = L
@@ -233,6 +235,21 @@ def filter_lwr(lwr, thresh, acc=False, mn=1, mx=0xffffffff):
     if rc:
         raise RuntimeError(host_lib().epa_host_last_error().decode())
     return out[:n.value]
+
+
+def filter_pquery(lnl, branch_ids, thresh, acc=False, mn=1, mx=7):
+    """compute_and_set_lwr + filter of the chunk loop on one pquery (placement i: lnl[i] on
+    branch_ids[i]) -> (kept branch ids, their LWRs), in the filter's order"""
+    ll = np.ascontiguousarray(lnl, np.float64)
+    br = np.ascontiguousarray(branch_ids, np.uint32)
+    ids, lw = np.zeros(len(ll), np.uint32), np.zeros(len(ll), np.float64)
+    n = C.c_uint32()
+    u32p = C.POINTER(C.c_uint32)
+    rc = host_lib().epa_host_filter_pquery(_dp(ll), br.ctypes.data_as(u32p), len(ll), thresh, int(acc), mn, mx,
+                                           ids.ctypes.data_as(u32p), _dp(lw), C.byref(n))
+    if rc:
+        raise RuntimeError(host_lib().epa_host_last_error().decode())
+    return ids[:n.value], lw[:n.value]
 
 
 def parse_model(path):
