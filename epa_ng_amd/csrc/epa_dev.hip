@@ -508,7 +508,8 @@ extern "C" int epa_dev_set_option(epa_ctx* ctx, const char* key, int value) {
       {"thorough_generic", &EpaOptions::thorough_generic}, {"preplace_generic", &EpaOptions::preplace_generic},
       {"select_full_rows", &EpaOptions::select_full_rows}, {"select_sort", &EpaOptions::select_sort},
       {"queued_thorough", &EpaOptions::queued_thorough},   {"xcd_balance", &EpaOptions::xcd_balance},
-      {"aa_valu", &EpaOptions::aa_valu},                   {"timers", &EpaOptions::timers}};
+      {"aa_valu", &EpaOptions::aa_valu},                   {"timers", &EpaOptions::timers},
+      {"newton_lds", &EpaOptions::newton_lds}};
   for (const Entry& e : table)
     if (strcmp(key, e.name) == 0) {
       ctx->opt.*e.field = value;

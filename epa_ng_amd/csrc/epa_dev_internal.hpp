@@ -148,6 +148,7 @@ struct EpaOptions {
   int xcd_balance = 1;        // XCD shares of a Newton launch follow the measured speeds (epa_xcd_feedback)
   int aa_valu = 0;            // 20-state windows on the lane = site VALU kernel instead of the matrix-core kernel
   int timers = 1;             // hipEvent records around the kernel families (epa_dev_last_kernel_ms)
+  int newton_lds = 0;         // single-wave 4-state Newton kernels read their table through LDS instead of DPP
 };
 
 struct epa_ctx {

@@ -136,7 +136,51 @@ struct LaneConst {
   int npos;    // ZERO0: this lane's entry of the COMPACT Newton table [order][category][x = 1..3] (36
                // doubles, read back as 18 aligned ds_read_b128); lanes of eigen index 0 / slot 3: a dump slot
   const double* e2t;  // LDS: 2^(j/64), j = 0..63 (exp_tab)
+  // TDPP instantiations: the Newton table in registers, the same 12 entries per order in every 16-lane row.  Row
+  // lane p = 0..5 holds (category p / 3, eigen index p % 3 + 1), p = 8..13 holds (2 + (p - 8) / 3, (p - 8) % 3 + 1);
+  // p = 6, 7, 14, 15 hold nothing (lrn = cn = 0).  Categories 2, 3 sit 8 lanes after 0, 1 so that a half-chunk's
+  // upper rows reach theirs with one row_ror:8 (see dpp_rows23_upper).
+  double lrn;    // lambda_x * r_k of the row entry
+  double cn[3];  // w_k * lrn^m, m = 0, 1, 2
 };
+
+// ---- TDPP: the fp64 ALU's one DPP control, row_newbcast:n, hands every lane of a 16-lane row the value of lane n of
+// that row as an operand of the FMA itself -- no LDS round trip, no lgkmcnt wait (profiles/r7_dpp_bcast.txt).  The
+// asm hides these reads from the compiler's hazard recognizer: a VALU write of a broadcast source needs 2 wait states
+// before the first DPP read: dpp_ready puts an s_nop 1 between the last write of the sources and their readers
+// (profiles/dpp_hazard_check.py checks the built object for a compiler move slipped in between).
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {   // f(0), f(1), ..., f(N - 1) with compile-time indices
+  if constexpr (N > 0) {
+    static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
+}
+constexpr int dpp_pos(int k, int x) { return (k >> 1) * 8 + (k & 1) * 3 + x - 1; }   // row lane of entry (k, x >= 1)
+template <int N>
+__device__ __forceinline__ void fmac_bcast(double& acc, double t, double s) {   // acc = fma(s, t[lane N of the row], acc)
+  asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(t), "v"(s), "i"(N));
+}
+__device__ __forceinline__ void dpp_ready(double& a, double& b, double& c) {
+  asm("s_nop 1" : "+v"(a), "+v"(b), "+v"(c));
+}
+// rows 2, 3 take the entries 8 lanes on (categories 2, 3 where rows 0, 1 keep 0, 1): the half-chunk layout
+__device__ __forceinline__ void dpp_rows23_upper(double& a, double& b, double& c) {
+  int al = __double2loint(a), ah = __double2hiint(a), bl = __double2loint(b), bh = __double2hiint(b);
+  int cl = __double2loint(c), ch = __double2hiint(c);
+  asm("s_nop 1\n\t"
+      "v_mov_b32_dpp %0, %0 row_ror:8 row_mask:0xc bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %1, %1 row_ror:8 row_mask:0xc bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %2, %2 row_ror:8 row_mask:0xc bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %3, %3 row_ror:8 row_mask:0xc bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %4, %4 row_ror:8 row_mask:0xc bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %5, %5 row_ror:8 row_mask:0xc bank_mask:0xf"
+      : "+v"(al), "+v"(ah), "+v"(bl), "+v"(bh), "+v"(cl), "+v"(ch));
+  a = __hiloint2double(ah, al);
+  b = __hiloint2double(bh, bl);
+  c = __hiloint2double(ch, cl);
+  dpp_ready(a, b, c);   // after the moves that may pair the halves up again
+}
 
 // 16-byte LDS reads of table entries: ds_read_b128 moves 256 B/clk/CU, the ds_read2_b64 the compiler
 // picks for unaligned pairs 128 (MI355X_MICROARCH.md, LDS table) -- and the tables are what keeps the
@@ -413,10 +457,49 @@ __device__ __forceinline__ void half_contract(const double (&S)[16], const doubl
 // ZERO0: eigenvalue 0 is exactly 0 (stationary mode) -> its e1/e2 columns vanish.
 // Then  f = sum_sites -l1/l0,  f' = sum_sites (l1/l0)^2 - l2/l0   (pll_compute_likelihood_
 // derivatives): 40 (48) FMAs per site.
-template <int NCH, bool ZERO0, int NW, bool TAILH = false, int NG = 1>
+template <int NCH, bool ZERO0, int NW, bool TAILH = false, int NG = 1, bool TDPP = false>
 __device__ __forceinline__ void derivatives(const SiteState<NCH>& st, double* tab, int lane,
                                             const LaneConst& lc, Comb<NW, NG>& cb, double t, double& f,
                                             double& df) {
+  if constexpr (TDPP) {
+    // the table in registers (LaneConst::lrn): the same exp and products as the LDS form, the same FMAs in the same
+    // order per accumulator, each reading its table entry by row_newbcast
+    static_assert(ZERO0 && NW == 1 && NG == 1 && TH_WAVES < 3, "the DPP form exists for the single-wave ZERO0 kernels");
+    const double e = TH_EXP(lc.lrn * t);
+    double T0 = e * lc.cn[0], T1 = e * lc.cn[1], T2 = e * lc.cn[2];
+    dpp_ready(T0, T1, T2);
+    double fl = 0.0, dfl = 0.0;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      if (TAILH && ch == NCH - 1) {
+        // half-chunk (the last chunk): rows 2, 3 contract categories 2, 3 with the immediates of 0, 1
+        dpp_rows23_upper(T0, T1, T2);
+        double l0 = st.S[ch][0], l1 = 0.0, l2 = 0.0;
+        static_for<6>([&](auto j) {   // (category kk = j / 3 of this half, eigen index j % 3 + 1)
+          const double sv = st.S[ch][(j / 3) * 4 + j % 3 + 1];
+          fmac_bcast<j>(l0, T0, sv); fmac_bcast<j>(l1, T1, sv); fmac_bcast<j>(l2, T2, sv);
+        });
+        l0 = xhalf_add(l0);
+        const double l12 = xhalf_add2(l1, l2);
+        const double qv = -l12 * fast_rcp(l0);
+        const bool lower = lane < 32;
+        if (st.valid[ch]) { fl += lower ? qv : 0.0; dfl += lower ? qv * qv : qv; }
+        continue;
+      }
+      double l0 = st.S[ch][0], l1 = 0.0, l2 = 0.0;
+      static_for<12>([&](auto j) {    // (category j / 3, eigen index j % 3 + 1): sumtable entry 4 k + x
+        constexpr int k = j / 3, x = j % 3 + 1;
+        const double sv = st.S[ch][k * 4 + x];
+        fmac_bcast<dpp_pos(k, x)>(l0, T0, sv); fmac_bcast<dpp_pos(k, x)>(l1, T1, sv); fmac_bcast<dpp_pos(k, x)>(l2, T2, sv);
+      });
+      const double inv = fast_rcp(l0);
+      const double d1 = -l1 * inv;
+      const double d2 = fma(d1, d1, -l2 * inv);
+      if (st.valid[ch]) { fl += d1; dfl += d2; }
+    }
+    wave_sum2(fl, dfl, f, df);
+    return;
+  }
   double e[16], e1[16], e2[16];
   if constexpr (ZERO0) {
     // compact table: entry (order m, category k, eigen index x >= 1) at m * 12 + k * 3 + x - 1
@@ -615,14 +698,14 @@ __device__ __forceinline__ double window_lnl(const SiteState<NCH>& st, const dou
 }
 
 // pllmod_opt_minimize_newton (pll-modules; rtsafe-style safeguarded Newton).  Wave-uniform.
-template <int NCH, bool ZERO0, int NW, bool TAILH = false, int NG = 1>
+template <int NCH, bool ZERO0, int NW, bool TAILH = false, int NG = 1, bool TDPP = false>
 __device__ __forceinline__ double newton(const SiteState<NCH>& st, double* tab, int lane,
                                          const LaneConst& lc, Comb<NW, NG>& cb, double x1, double xguess,
                                          double x2, double tol, int max_iters, uint32_t& evals) {
   double rts = xguess, f, df, xl, xh, dx;
   if (rts < x1) rts = x1;
   if (rts > x2) rts = x2;
-  derivatives<NCH, ZERO0, NW, TAILH, NG>(st, tab, lane, lc, cb, rts, f, df);
+  derivatives<NCH, ZERO0, NW, TAILH, NG, TDPP>(st, tab, lane, lc, cb, rts, f, df);
   ++evals;
   if (!isfinite(f) || !isfinite(df)) return NAN;
   if (df >= 0.0 && fabs(f) < tol) return rts;
@@ -643,7 +726,7 @@ __device__ __forceinline__ double newton(const SiteState<NCH>& st, double* tab, 
     }
     if (fabs(dx) < tol || i == max_iters) return rts;
     if (rts < x1) rts = x1;
-    derivatives<NCH, ZERO0, NW, TAILH, NG>(st, tab, lane, lc, cb, rts, f, df);
+    derivatives<NCH, ZERO0, NW, TAILH, NG, TDPP>(st, tab, lane, lc, cb, rts, f, df);
     ++evals;
     if (!isfinite(f) || !isfinite(df)) return NAN;
     if (df > 0.0 && fabs(f) < tol) return rts;
@@ -652,7 +735,7 @@ __device__ __forceinline__ double newton(const SiteState<NCH>& st, double* tab, 
   return NAN;
 }
 
-template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL, bool TAILH = false, int NG = 1>
+template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL, bool TAILH = false, int NG = 1, bool TDPP = false>
 __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pidx, const int lane,
                                              double* tab, const double* qts, double* qa, const LaneConst& lc,
                                              Comb<NW, NG>& cb, uint32_t (&wstat)[3]) {
@@ -889,7 +972,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
     auto solve = [&](double cur) -> double {
       double g = cur;
       if (g < xmin || g > xmax) g = a.blo.default_branch;
-      const double r = newton<NCH, ZERO0, NW, TAILH, NG>(st, tab, lane, lc, cb, xmin, g, xmax, xtol, (int)a.blo.max_newton, evals);
+      const double r = newton<NCH, ZERO0, NW, TAILH, NG, TDPP>(st, tab, lane, lc, cb, xmin, g, xmax, xtol, (int)a.blo.max_newton, evals);
       chain = zero_after(r);
       // keep_update: the length is replaced when the solver moved it
       return (isfinite(r) && fabs(cur - r) > 1e-10) ? r : cur;
@@ -919,7 +1002,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
     double xmin = a.blo.min_branch, xmax = a.blo.max_branch, xtol = xmin / 10.0;
     double xguess = tp;
     if (xguess < xmin || xguess > xmax) xguess = a.blo.default_branch;
-    double xres = newton<NCH, ZERO0, NW, TAILH, NG>(st, tab, lane, lc, cb, xmin, xguess, xmax, xtol, (int)a.blo.max_newton, evals);
+    double xres = newton<NCH, ZERO0, NW, TAILH, NG, TDPP>(st, tab, lane, lc, cb, xmin, xguess, xmax, xtol, (int)a.blo.max_newton, evals);
     if (xres > 0.0) tp = xres;
     chain = zero_after(tp);
     // ---- NR for the distal length with the proximal P-matrix held fixed (:170-211)
@@ -929,7 +1012,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
     xtol = xmin / 10.0;
     xmax = orig - xtol;
     if (xguess < xmin || xguess > xmax) xguess = orig / 2.0;
-    xres = newton<NCH, ZERO0, NW, TAILH, NG>(st, tab, lane, lc, cb, xmin, xguess, xmax, xtol, (int)a.blo.max_newton, evals);
+    xres = newton<NCH, ZERO0, NW, TAILH, NG, TDPP>(st, tab, lane, lc, cb, xmin, xguess, xmax, xtol, (int)a.blo.max_newton, evals);
     if (xres > 0.0) { td = xres; tx = orig - xres; }
     chain = zero_after(td);
     // ---- score (:217-222)
@@ -970,7 +1053,9 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
 // and every wave gets a ~25-pair random sample of the 10x cost spread (1..32 NR rounds).
 // INV: the model has +I (instantiated for ZERO0 only; a separate instantiation so that the
 // default kernel's register allocation is untouched: the runtime-flag version cost 40 more spills)
-template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL = false, bool TAILH = false, int NG = 1>
+// TDPP: the Newton table broadcast by DPP from registers instead of through LDS (single-wave ZERO0 classes; the LDS
+// form stays reachable by the context option "newton_lds")
+template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL = false, bool TAILH = false, int NG = 1, bool TDPP = false>
 __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const ThArgs a) {
   constexpr int NWV = NW * NG;     // waves of the workgroup: site blocks (NW) or category groups (NG)
   __shared__ __attribute__((aligned(16))) double tab[64 * NWV];  // broadcast table of each wave
@@ -997,6 +1082,15 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
     // compact Newton table position; the 28 lanes without an entry (eigen index 0, slot 3) get the dump slots 36..63
     const int dump = lc.slot == 3 ? 36 + (lane & 15) : 52 + lc.slot * 4 + lk;
     lc.npos = (lc.slot < 3 && lx != 0) ? lc.slot * 12 + lk * 3 + lx - 1 : dump;
+  }
+  if constexpr (TDPP) {   // row layout of the register table (LaneConst::lrn)
+    const int p = lane & 15, q = p & 7;
+    const int kn = q < 6 ? 2 * (p >> 3) + q / 3 : 0, xn = q % 3 + 1;
+    const double wn = q < 6 ? a.m.w[kn] : 0.0;
+    lc.lrn = q < 6 ? a.m.lam[xn] * a.m.rate[kn] : 0.0;
+    lc.cn[0] = wn;
+    lc.cn[1] = wn * lc.lrn;
+    lc.cn[2] = wn * lc.lrn * lc.lrn;
   }
   __syncthreads();
   const uint32_t x = blockIdx.x & 7;
@@ -1048,7 +1142,7 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
       const uint32_t cur = nxt;
       uint32_t f = 0;
       if (lane == 0) f = atomicAdd(ctr, 1u);
-      process_pair<NCH, ZERO0, INV, NW, LOCAL, TAILH, NG>(a, lo + cur, lane, tab + cb.wv * 64, qts, qa + cb.wv * (16 * QA_STRIDE), lc, cb, wstat);
+      process_pair<NCH, ZERO0, INV, NW, LOCAL, TAILH, NG, TDPP>(a, lo + cur, lane, tab + cb.wv * 64, qts, qa + cb.wv * (16 * QA_STRIDE), lc, cb, wstat);
       nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)f);
 #ifdef TH_TIMING
       ++npr;
@@ -1061,7 +1155,7 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
 #endif
   } else {
     for (uint64_t p = lo + w; p < hi; p += stride)
-      process_pair<NCH, ZERO0, INV, NW, LOCAL, TAILH, NG>(a, p, lane, tab + cb.wv * 64, qts, qa + cb.wv * (16 * QA_STRIDE), lc, cb, wstat);
+      process_pair<NCH, ZERO0, INV, NW, LOCAL, TAILH, NG, TDPP>(a, p, lane, tab + cb.wv * 64, qts, qa + cb.wv * (16 * QA_STRIDE), lc, cb, wstat);
   }
   if (threadIdx.x == 0) {
     atomicAdd(&a.stats[0], (unsigned long long)wstat[0]);
@@ -1081,6 +1175,7 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
 
 #ifdef TH_ONLY_MAIN   // experiment builds (exp/): the dominant instantiation alone
 template __global__ void k_thorough_dna<3, true, false, 1, false, true, 1>(const ThArgs a);
+template __global__ void k_thorough_dna<3, true, false, 1, false, true, 1, true>(const ThArgs a);
 }  // namespace
 #else
 // ---------------------------------------------------------------------------------------------
@@ -1327,6 +1422,21 @@ __global__ void __launch_bounds__(256) k_pair_class(const epa_pair* __restrict__
   }
 }
 
+// k_thorough_dna<NCH, ZERO0, INV, NW, LOCAL, TAILH>: the single-wave ZERO0 kernels of the sliding BLO broadcast the
+// Newton table by DPP unless the context option "newton_lds" asks for the LDS form (same results).  (--raxml-blo,
+// LOCAL, stays on the LDS form: this compiler's register allocator crashes on its DPP instantiations under the
+// iterative-ilp scheduler.)
+template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL = false, bool TAILH = false>
+void launch_dna(const epa_ctx* ctx, uint32_t nwg, const ThArgs& a) {
+  if constexpr (ZERO0 && NW == 1 && !LOCAL && TH_WAVES < 3) {
+    if (!ctx->opt.newton_lds) {
+      hipLaunchKernelGGL((k_thorough_dna<NCH, ZERO0, INV, NW, LOCAL, TAILH, 1, true>), dim3(nwg), dim3(64), 0, ctx->stream, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_thorough_dna<NCH, ZERO0, INV, NW, LOCAL, TAILH>), dim3(nwg), dim3(64 * NW), 0, ctx->stream, a);
+}
+
 }  // namespace
 
 // One launch per span class present (see epa_span_class).  `order` = this class's pair indices
@@ -1365,19 +1475,19 @@ static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t m
     if (want > n_pairs) want = n_pairs;                                                            \
     const uint32_t nwg = (uint32_t)((want + 7) / 8 * 8);                                           \
     constexpr bool TH_ = (NW_) == 1 && ((N) == 2 || (N) == 3);   /* half-chunk tail instantiations exist for these */  \
-    if (tailh && TH_ && ctx->dna_zero0 && !ctx->blo.sliding && !a.cinv)                                                \
-      hipLaunchKernelGGL((k_thorough_dna<N, true, false, 1, true, TH_>), dim3(nwg), dim3(64), 0, ctx->stream, a);      \
-    else if (tailh && TH_ && ctx->dna_zero0 && !ctx->blo.sliding)   /* --raxml-blo with +I */                          \
-      hipLaunchKernelGGL((k_thorough_dna<N, true, true, 1, true, TH_>), dim3(nwg), dim3(64), 0, ctx->stream, a);       \
-    else if (tailh && TH_ && ctx->dna_zero0 && ctx->blo.sliding && a.cinv)                                            \
-      hipLaunchKernelGGL((k_thorough_dna<N, true, true, 1, false, TH_>), dim3(nwg), dim3(64), 0, ctx->stream, a);      \
-    else if (tailh && TH_ && ctx->dna_zero0 && ctx->blo.sliding)                                                       \
-      hipLaunchKernelGGL((k_thorough_dna<N, true, false, 1, false, TH_>), dim3(nwg), dim3(64), 0, ctx->stream, a);     \
-    else if (!ctx->blo.sliding && a.cinv) hipLaunchKernelGGL((k_thorough_dna<N, true, true, NW_, true>), dim3(nwg), dim3(64 * (NW_)), 0, ctx->stream, a); \
-    else if (!ctx->blo.sliding) hipLaunchKernelGGL((k_thorough_dna<N, true, false, NW_, true>), dim3(nwg), dim3(64 * (NW_)), 0, ctx->stream, a); \
-    else if (a.cinv) hipLaunchKernelGGL((k_thorough_dna<N, true, true, NW_>), dim3(nwg), dim3(64 * (NW_)), 0, ctx->stream, a); \
-    else if (ctx->dna_zero0) hipLaunchKernelGGL((k_thorough_dna<N, true, false, NW_>), dim3(nwg), dim3(64 * (NW_)), 0, ctx->stream, a); \
-    else hipLaunchKernelGGL((k_thorough_dna<N, false, false, NW_>), dim3(nwg), dim3(64 * (NW_)), 0, ctx->stream, a); \
+    if (tailh && TH_ && ctx->dna_zero0 && !ctx->blo.sliding && !a.cinv)                                            \
+      launch_dna<N, true, false, 1, true, TH_>(ctx, nwg, a);                                                       \
+    else if (tailh && TH_ && ctx->dna_zero0 && !ctx->blo.sliding)   /* --raxml-blo with +I */                      \
+      launch_dna<N, true, true, 1, true, TH_>(ctx, nwg, a);                                                        \
+    else if (tailh && TH_ && ctx->dna_zero0 && ctx->blo.sliding && a.cinv)                                        \
+      launch_dna<N, true, true, 1, false, TH_>(ctx, nwg, a);                                                       \
+    else if (tailh && TH_ && ctx->dna_zero0 && ctx->blo.sliding)                                                   \
+      launch_dna<N, true, false, 1, false, TH_>(ctx, nwg, a);                                                      \
+    else if (!ctx->blo.sliding && a.cinv) launch_dna<N, true, true, NW_, true>(ctx, nwg, a);                       \
+    else if (!ctx->blo.sliding) launch_dna<N, true, false, NW_, true>(ctx, nwg, a);                                \
+    else if (a.cinv) launch_dna<N, true, true, NW_>(ctx, nwg, a);                                                  \
+    else if (ctx->dna_zero0) launch_dna<N, true, false, NW_>(ctx, nwg, a);                                         \
+    else launch_dna<N, false, false, NW_>(ctx, nwg, a);                                                            \
   } while (0)
   // half-chunk tail (TAILH), classes 10 / 11: every window of the class ends within 32 sites of its
   // last chunk's start (150-site reads: 64 + 64 + 22).  Same-box A/B on the cfg2 bench: 6.57 - 6.69

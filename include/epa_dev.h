@@ -216,6 +216,9 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
  *   "xcd_balance"       0: the eight XCDs keep equal shares of a Newton launch (default 1: epa_dev_xcd_shares)
  *   "aa_valu"           1: 20-state windows on the lane = site VALU kernel instead of the matrix-core kernel
  *   "timers"            0: no hipEvent records around the kernel families (epa_dev_last_kernel_ms returns < 0)
+ *   "newton_lds"        1: the single-wave 4-state Newton kernels (windows up to 256 sites, exact zero eigenvalue,
+ *                          sliding BLO) read their per-evaluation table through LDS instead of broadcasting it from registers
+ *                          by DPP (default 0: DPP; bit-identical results)
  * Unknown key: EPA_ERR_INVALID_ARG.
  */
 int epa_dev_set_option(epa_ctx* ctx, const char* key, int value);

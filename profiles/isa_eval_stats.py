@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction mix of ONE Newton evaluation of k_thorough_dna's cfg2 instantiation
-(<NCH 3, ZERO0, no +I, 1 wave, sliding, half-chunk tail, 1 category group>), from the built object:
-    python profiles/isa_eval_stats.py > profiles/r6_newton_eval_isa.txt
+(<NCH 3, ZERO0, no +I, 1 wave, sliding, half-chunk tail, 1 category group, DPP table>), from the built object:
+    python profiles/isa_eval_stats.py > profiles/r7_newton_eval_isa.txt
+    python profiles/isa_eval_stats.py lds     # the same instantiation with the LDS table (option "newton_lds")
 The evaluation is the stretch from the table-driven exp (v_rndne_f64) of a Newton loop to the four v_readlane_b32
 behind the paired DPP reduction; the first such stretch of the kernel (the pendant solve's loop body) is printed."""
 import collections
@@ -20,7 +21,8 @@ with tempfile.TemporaryDirectory() as d:
     subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
     asm = subprocess.check_output([LLVM + "llvm-objdump", "-d", co], text=True)
-name = "k_thorough_dnaILi3ELb1ELb0ELi1ELb0ELb1ELi1EE"
+lds = len(sys.argv) > 1 and sys.argv[1] == "lds"
+name = "k_thorough_dnaILi3ELb1ELb0ELi1ELb0ELb1ELi1ELb%dEE" % (0 if lds else 1)
 lines = asm.split("\n")
 start = next(i for i, l in enumerate(lines) if name in l and l.rstrip().endswith(">:"))
 ins = []
@@ -56,9 +58,15 @@ print("one Newton evaluation (exp of the proposal -> f, f' in scalar registers):
 for k, v in sorted(cls.items(), key=lambda kv: -kv[1]):
     print("  %4d  %s" % (v, k))
 valu = sum(v for k, v in cls.items() if not k.startswith(("scalar", "ds_")))
-print("  vector instructions: %d, of them fp64 fma %d; LDS reads %d (the 36-entry table: 18 ds_read_b128 for the two full chunks"
-      " + 9 for the half chunk, whose lanes need other entries; 1 ds_read_b64 = exp_tab's 2^(j/64))"
-      % (valu, cls["fp64 fma"], sum(v for k, v in cls.items() if k.startswith("ds_read"))))
+print("  vector instructions: %d, of them fp64 fma %d (%d with a row_newbcast operand); LDS reads %d"
+      % (valu, cls["fp64 fma"], sum(1 for op, _ in body if op.startswith("v_fmac_f64_dpp")),
+         sum(v for k, v in cls.items() if k.startswith("ds_read"))))
+if lds:
+    print("  (the 36-entry table: 18 ds_read_b128 for the two full chunks + 9 for the half chunk, whose lanes need other"
+          " entries; 1 ds_read_b64 = exp_tab's 2^(j/64))")
+else:
+    print("  (the table in three registers per lane, read by row_newbcast; 6 v_mov_b32_dpp row_ror:8 give the half"
+          " chunk's upper rows their categories; 1 ds_read_b64 = exp_tab's 2^(j/64))")
 print("-- listing")
 for op, a in body:
     print("  %-28s %s" % (op, a[:70]))
