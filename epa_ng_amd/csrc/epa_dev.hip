@@ -247,11 +247,11 @@ __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict
                                                       double* __restrict__ lookup,
                                                       double* __restrict__ refI,
                                                       uint8_t* __restrict__ resc0,
-                                                      const double* __restrict__ cinv) {
+                                                      const double* __restrict__ cinv, uint32_t b0) {
   __shared__ double U[S * S], Ui[S * S];
   __shared__ double Eh[EPA_MAX_CATS * S], Ep[EPA_MAX_CATS * S];  // exp tables: half branch, pendant
   const int c = m->c, ncols = m->ncols;
-  const uint32_t b = blockIdx.y;
+  const uint32_t b = b0 + blockIdx.y;   // b0: first branch of this slice of the launch (grid.y limit)
   const double half = blen[b] * 0.5;
   for (int i = threadIdx.x; i < S * S; i += blockDim.x) { U[i] = m->U[i]; Ui[i] = m->Ui[i]; }
   for (int i = threadIdx.x; i < c * S; i += blockDim.x) {
@@ -333,16 +333,18 @@ __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict
 }
 
 int launch_build_lookup(epa_ctx* ctx) {
-  dim3 grid((ctx->W + 255) / 256, ctx->B);
   epa_timer_start(ctx, ctx->t_lookup);
-  if (ctx->s == 4)
-    hipLaunchKernelGGL(k_build_lookup<4>, grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT,
-                       ctx->scSum, ctx->blen, ctx->blo.pendant_default, ctx->W, ctx->lookup, ctx->refI,
-                       ctx->resc0, ctx->cinv);
-  else
-    hipLaunchKernelGGL(k_build_lookup<20>, grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT,
-                       ctx->scSum, ctx->blen, ctx->blo.pendant_default, ctx->W, ctx->lookup, ctx->refI,
-                       ctx->resc0, ctx->cinv);
+  for (uint32_t b0 = 0; b0 < ctx->B; b0 += EPA_GRID_Y) {   // branch in grid.y, in slices of its limit
+    const dim3 grid((ctx->W + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, ctx->B - b0));
+    if (ctx->s == 4)
+      hipLaunchKernelGGL(k_build_lookup<4>, grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT,
+                         ctx->scSum, ctx->blen, ctx->blo.pendant_default, ctx->W, ctx->lookup, ctx->refI,
+                         ctx->resc0, ctx->cinv, b0);
+    else
+      hipLaunchKernelGGL(k_build_lookup<20>, grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT,
+                         ctx->scSum, ctx->blen, ctx->blo.pendant_default, ctx->W, ctx->lookup, ctx->refI,
+                         ctx->resc0, ctx->cinv, b0);
+  }
   EPA_HIP(ctx, hipGetLastError());
   if (ctx->s == 4) {
     int rc = launch_build_lookup2(ctx);
@@ -634,7 +636,7 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
 
 static int precompute_from_tree(epa_ctx* ctx, const epa_tree_desc* t, const uint32_t* d_tipmap);
 __global__ void k_align_rates(const ModelDev* __restrict__ m, double* __restrict__ refT,
-                              const uint32_t* __restrict__ sc_side, uint32_t* __restrict__ scSum, uint32_t W);
+                              const uint32_t* __restrict__ sc_side, uint32_t* __restrict__ scSum, uint32_t W, uint32_t b0);
 
 static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const epa_tree_desc* tree = nullptr) {
   const int s = (int)d->states, c_in = (int)d->rate_cats;
@@ -857,8 +859,9 @@ static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const ep
     }
   }
   if (d_sc_side) {
-    hipLaunchKernelGGL(k_align_rates, dim3((uint32_t)((W + 255) / 256), (uint32_t)B), dim3(256), 0, ctx->stream,
-                       ctx->dmodel, ctx->refT, d_sc_side, ctx->scSum, (uint32_t)W);
+    for (uint32_t b0 = 0; b0 < (uint32_t)B; b0 += EPA_GRID_Y)
+      hipLaunchKernelGGL(k_align_rates, dim3((uint32_t)((W + 255) / 256), std::min<uint32_t>(EPA_GRID_Y, (uint32_t)B - b0)),
+                         dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT, d_sc_side, ctx->scSum, (uint32_t)W, b0);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_sc_side);
   }
@@ -980,8 +983,8 @@ __global__ void __launch_bounds__(256) k_tip_sides(const ModelDev* __restrict__ 
                                                    const uint32_t* __restrict__ tip_of_branch,
                                                    const uint8_t* __restrict__ tipchars,
                                                    const uint32_t* __restrict__ tipmap, uint32_t W,
-                                                   double* __restrict__ refT) {
-  const uint32_t b = blockIdx.y;
+                                                   double* __restrict__ refT, uint32_t b0) {
+  const uint32_t b = b0 + blockIdx.y;
   const uint32_t t = tip_of_branch[b];
   if (t == 0xffffffffu) return;
   const uint32_t site = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1016,8 +1019,8 @@ __global__ void k_scaler_sum(const uint32_t* __restrict__ sc_side, uint32_t* __r
 // sc_side [2B][c][W] per-rate counts of the branch sides; thread per (branch, site).
 __global__ void __launch_bounds__(256) k_align_rates(const ModelDev* __restrict__ m, double* __restrict__ refT,
                                                      const uint32_t* __restrict__ sc_side,
-                                                     uint32_t* __restrict__ scSum, uint32_t W) {
-  const uint32_t b = blockIdx.y;
+                                                     uint32_t* __restrict__ scSum, uint32_t W, uint32_t b0) {
+  const uint32_t b = b0 + blockIdx.y;
   const uint32_t site = blockIdx.x * blockDim.x + threadIdx.x;
   if (site >= W) return;
   const int c = m->c, s = m->s;
@@ -1119,13 +1122,14 @@ static int precompute_from_tree(epa_ctx* ctx, const epa_tree_desc* t, const uint
   TREE_HIP(hipMalloc(&d_tob, sizeof(uint32_t) * B));
   TREE_HIP(hipMemcpy(d_tob, tip_of_branch.data(), sizeof(uint32_t) * B, hipMemcpyHostToDevice));
   const dim3 blk(256);
-  hipLaunchKernelGGL(k_tip_sides, dim3((W + 255) / 256, B), blk, 0, ctx->stream, ctx->dmodel, d_tob, d_tips,
-                     d_tipmap, W, ctx->refT);
+  for (uint32_t b0 = 0; b0 < B; b0 += EPA_GRID_Y)
+    hipLaunchKernelGGL(k_tip_sides, dim3((W + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, B - b0)), blk, 0, ctx->stream,
+                       ctx->dmodel, d_tob, d_tips, d_tipmap, W, ctx->refT, b0);
   for (size_t l = 0; l + 1 < lev_begin.size(); ++l) {
     const uint32_t cnt = lev_begin[l + 1] - lev_begin[l];
     if (!cnt) continue;
-    for (uint32_t off = 0; off < cnt; off += 65535) {  // grid.y limit
-      const dim3 grid((W + 255) / 256, std::min<uint32_t>(65535, cnt - off));
+    for (uint32_t off = 0; off < cnt; off += EPA_GRID_Y) {  // grid.y limit
+      const dim3 grid((W + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, cnt - off));
       if (ctx->s == 4)
         hipLaunchKernelGGL(k_clv_level<4>, grid, blk, 0, ctx->stream, ctx->dmodel, d_recs + lev_begin[l] + off,
                            d_tips, d_tipmap, W, ctx->refT, d_sc, ctx->rate_scalers ? 1 : 0);
@@ -1135,8 +1139,9 @@ static int precompute_from_tree(epa_ctx* ctx, const epa_tree_desc* t, const uint
     }
   }
   if (ctx->rate_scalers) {
-    hipLaunchKernelGGL(k_align_rates, dim3((W + 255) / 256, B), blk, 0, ctx->stream, ctx->dmodel, ctx->refT, d_sc,
-                       ctx->scSum, W);
+    for (uint32_t b0 = 0; b0 < B; b0 += EPA_GRID_Y)
+      hipLaunchKernelGGL(k_align_rates, dim3((W + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, B - b0)), blk, 0, ctx->stream,
+                         ctx->dmodel, ctx->refT, d_sc, ctx->scSum, W, b0);
   } else {
     const size_t nbw = (size_t)B * W;
     hipLaunchKernelGGL(k_scaler_sum, dim3((uint32_t)((nbw + 255) / 256)), blk, 0, ctx->stream, d_sc, ctx->scSum, nbw, W);

@@ -13,6 +13,9 @@
 #define EPA_MAX_STATES 20
 #define EPA_MAX_CATS 16
 #define EPA_MAX_COLS 24
+// HIP's limit of grid.y / grid.z: a launch with the branch (or a record of a tree level) in grid.y goes out in slices
+// of this many, the kernel adds the slice's first branch
+#define EPA_GRID_Y 65535u
 
 // Model constants handed to kernels by value (kernarg -> SGPRs via s_load).
 struct ModelDNA {

@@ -236,6 +236,11 @@ int epa_host_place_file(void* h, const char* query_file, const char* outdir, uin
 // host-side set operations exposed for unit tests with literal vectors
 // (the reference's test/src/set_manipulators.cpp:340-443)
 // the C++ chunk loop's query slice of a rank (place_ranks.cpp; src/net/epa_mpi_util.cpp:10-30)
+// the chunk loop's memory clamp (place.cpp: device_chunk_reads), for tests
+uint64_t epa_host_device_chunk_reads(uint64_t free_bytes, uint64_t branches, int slots, uint64_t wanted, uint64_t user_chunk) {
+  return (uint64_t)epa::device_chunk_reads(free_bytes, (size_t)branches, slots, (size_t)wanted, (size_t)user_chunk);
+}
+
 void epa_host_local_seq_package(uint64_t num_sequences, int rank, int world, uint64_t* offset, uint64_t* count) {
   const auto p = epa::local_seq_package((size_t)num_sequences, rank, world);
   *offset = p.first;

@@ -445,7 +445,17 @@ struct Run_Stats {
   // and overlap, so they do not add up to seconds_loop = wall time from the first read to the closed jplace)
   double seconds_encode = 0, seconds_sample = 0, seconds_text = 0, seconds_loop = 0;
   int host_threads = 0;
+  // which chunk body the run used: "pipelined" (staged device chunks, several in flight), "fused" (one
+  // epa_dev_place_chunk at a time), "place_all" (--no-heur on the device) or "host" (table round trip + host
+  // heuristics); and the reads per device chunk after the memory clamp (device_chunk_reads)
+  std::string chunk_path;
+  size_t device_chunk = 0;
 };
+// Reads per device chunk that fit a device: `slots` pipeline slots each own a preplacement table of
+// Q x pitch(branches) x 8 bytes (pitch: the row rounded up to 64 bytes), plus a quarter of that for codes, bitmap and
+// candidates, all within half of `free_bytes`.  `wanted` is returned unless that is too much; never 0.  user_chunk:
+// an explicit --chunk-size the result may not exceed (0: none) -- the clamp only ever lowers it.
+size_t device_chunk_reads(uint64_t free_bytes, size_t branches, int slots, size_t wanted, size_t user_chunk);
 Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const std::string& outdir,
                      const Options& options, const std::string& invocation, int device = 0);
 // same, one worker thread per listed GPU; the jplace does not depend on the device count

@@ -202,7 +202,8 @@ int main(int argc, char** argv) {
          << ", \"loop_s\": " << st.seconds_loop << ", \"read_index_s\": " << st.seconds_read << ", \"encode_s\": " << st.seconds_encode
          << ", \"stage_wait_s\": " << st.seconds_stage_wait << ", \"device_calls_s\": " << st.seconds_place + st.seconds_thorough
          << ", \"build_sample_s\": " << st.seconds_sample << ", \"lwr_filter_s\": " << st.seconds_post
-         << ", \"jplace_text_s\": " << st.seconds_text << ", \"write_s\": " << st.seconds_write << "}\n";
+         << ", \"jplace_text_s\": " << st.seconds_text << ", \"write_s\": " << st.seconds_write
+         << ", \"chunk_path\": \"" << st.chunk_path << "\", \"device_chunk\": " << st.device_chunk << "}\n";
     }
   } catch (const std::exception& e) {
     std::cerr << e.what() << "\nAborting with a failure." << std::endl;

@@ -441,7 +441,7 @@ void filter(Sample& sample, const Options& options) {
 }
 
 namespace {
-struct Chunk_Timing { double place = 0, thorough = 0, post = 0; size_t pairs = 0; };
+struct Chunk_Timing { double place = 0, thorough = 0, post = 0; size_t pairs = 0; const char* path = ""; };
 
 // the body of the reference's chunk loop (src/core/place.cpp:219-246) for one chunk on one device
 Sample process_chunk(const MSA& chunk, const Encoded_Chunk& enc, const Tree& tree, Device_Evaluator& dev,
@@ -458,7 +458,8 @@ Sample process_chunk(const MSA& chunk, const Encoded_Chunk& enc, const Tree& tre
                              (uint64_t)n * B <= 0xffffffffull;
   // --host-heuristic: keep the Q x B table round trip and the host heuristics (cross-check)
   const bool host_heur = options.host_heuristic;
-  const bool fused = options.prescoring && options.device_select && B <= 65536 && !host_heur;
+  const bool fused = options.prescoring && options.device_select && !host_heur;
+  tm.path = all_on_device ? "place_all" : fused ? "fused" : "host";
   if (all_on_device) {
     tm.pairs = place_all(chunk, enc, tree, dev, blo_sample, options, seq_id_offset);
     t1 = clk::now();
@@ -492,6 +493,15 @@ Sample process_chunk(const MSA& chunk, const Encoded_Chunk& enc, const Tree& tre
   return blo_sample;
 }
 }  // namespace
+
+size_t device_chunk_reads(uint64_t free_bytes, size_t branches, int slots, size_t wanted, size_t user_chunk) {
+  const uint64_t pitch = ((uint64_t)branches * 8 + 63) / 64 * 64;   // bytes of one table row
+  const uint64_t per_read = std::max<uint64_t>(1, pitch * (uint64_t)std::max(1, slots) * 5 / 4);
+  const uint64_t room = (free_bytes / 2) / per_read;
+  uint64_t reads = std::min<uint64_t>(wanted, room);
+  if (user_chunk) reads = std::min<uint64_t>(reads, user_chunk);
+  return (size_t)std::max<uint64_t>(reads, 1);
+}
 
 Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const std::string& outdir,
                      const Options& options, const std::string& invocation, int device) {
@@ -568,20 +578,19 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
   // Reads per device chunk.  The device_min_chunk floor lifts the DEFAULT chunk size only: an explicit
   // --chunk-size is the user's memory knob (src/main.cpp:234-238) and is honoured as given unless
   // --device-min-chunk is given as well.  Either way the chunk is clamped to what the smallest device
-  // has room for: two pipeline slots x Q x pitch(B) x 8 bytes of preplacement table (+ a quarter for
-  // codes, bitmap, candidates) within half of its free memory.
+  // has room for (device_chunk_reads): the loop's kSlots pipeline slots x Q x pitch(B) x 8 bytes of
+  // preplacement table (+ a quarter for codes, bitmap, candidates) within half of its free memory.
   size_t device_chunk = options.chunk_size;
   if (!options.chunk_size_given || options.device_min_chunk_given)
     device_chunk = std::max<size_t>(device_chunk, options.device_min_chunk);
-  {
-    const size_t pitch = (tree.num_branches() * 8 + 63) / 64 * 64;
-    for (auto& d : devs) {
-      uint64_t fr = 0, tot = 0;
-      if (epa_dev_mem_info(d->ctx(), &fr, &tot) != EPA_OK) continue;
-      const size_t room = (size_t)(fr / 2) / (pitch * 2 * 5 / 4);
-      if (room < device_chunk) device_chunk = std::max<size_t>(std::min<size_t>(options.chunk_size, device_chunk), std::max<size_t>(room, 1));
-    }
+  constexpr int kSlots = 4;   // pipeline slots per device: a finished chunk's pinned rows stay valid for two more chunks
+  for (auto& d : devs) {
+    uint64_t fr = 0, tot = 0;
+    if (epa_dev_mem_info(d->ctx(), &fr, &tot) != EPA_OK) continue;
+    device_chunk = device_chunk_reads(fr, tree.num_branches(), kSlots, device_chunk,
+                                      options.chunk_size_given && !options.device_min_chunk_given ? options.chunk_size : 0);
   }
+  st.device_chunk = device_chunk;
   // Post-processing pool.  The reference hands a finished chunk to an asynchronous writer (src/io/jplace_writer.hpp:58-69);
   // here everything behind the device calls -- pquery building, LWR, filter, jplace text -- leaves the device worker
   // with the chunk: the pool's threads take a finished chunk in kParts query-range jobs and run those stages
@@ -594,7 +603,6 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
   Fasta_Stream reader(query_file);
   const int stager_team = reader.is_bfast() ? std::max(1, std::min(3, host_cores / 5)) : std::max(1, std::min(8, host_cores / 2));
   const int n_post = std::max(2, std::min(12, host_cores - (int)devices.size() - stager_team));
-  constexpr int kSlots = 4;   // pipeline slots per device: a finished chunk's pinned rows stay valid for two more chunks
   constexpr size_t kParts = 4;   // post-processing jobs per chunk (query ranges): a 50 000-read chunk is ~35 ms of serial work,
                                  // which is what the run's tail -- and the pool's load balance -- is made of
   struct Finished {
@@ -777,8 +785,8 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
   });
 
   // --host-heuristic: keep the Q x B table round trip and the host heuristics (cross-check); --no-pipeline: one chunk at a time
-  const bool pipelined = options.prescoring && options.device_select && tree.num_branches() <= 65536 &&
-                         !options.host_heuristic && !options.no_pipeline;
+  const bool pipelined = options.prescoring && options.device_select && !options.host_heuristic && !options.no_pipeline;
+  if (pipelined) st.chunk_path = "pipelined";
   auto worker = [&](size_t k) {
     try {
       auto take = [&](Staged& cur) -> bool {
@@ -798,6 +806,7 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
         st.pairs += tm.pairs;
         st.seconds_place += tm.place;
         st.seconds_thorough += tm.thorough;
+        if (!pipelined) st.chunk_path = tm.path;
       };
       if (!pipelined) {
         for (;;) {

@@ -142,6 +142,8 @@ Run_Stats simple_mpi_ranks(const Tree& tree, const std::string& query_file, cons
   size_t per_chunk = options.chunk_size;
   if (!options.chunk_size_given || options.device_min_chunk_given) per_chunk = std::max<size_t>(per_chunk, options.device_min_chunk);
   if (no_heur) per_chunk = std::max<size_t>(1, std::min<size_t>(per_chunk, 0xffffffffull / std::max<size_t>(1, tree.num_branches())));   // B x Q pairs per call < 2^32
+  st.chunk_path = no_heur ? "place_all" : "fused";
+  st.device_chunk = per_chunk;
   const size_t part = (total + (size_t)world - 1) / (size_t)world;
   const size_t nchunks = (part + per_chunk - 1) / per_chunk;   // the SAME on every rank: posts are collective
   // rows per rank and gather: candidates per read average 2 .. 3 under the default heuristic; beyond that

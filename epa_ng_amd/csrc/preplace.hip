@@ -468,8 +468,8 @@ __device__ __forceinline__ uint32_t dna_sym(uint32_t code) {
 // the very `a0 + a1` the reference's 4-way unrolled loop forms first (Lookup_Store.hpp:120-131),
 // x + 0.0 == x covers the singles of the tail.
 __global__ void __launch_bounds__(256) k_build_lookup2(const double* __restrict__ lookup, uint32_t W,
-                                                       double* __restrict__ lookup2) {
-  const uint32_t b = blockIdx.y;
+                                                       double* __restrict__ lookup2, uint32_t b0) {
+  const uint32_t b = b0 + blockIdx.y;
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= W * PE) return;
   const uint32_t s = i / PE, e = i - s * PE;
@@ -1528,56 +1528,246 @@ __global__ void __launch_bounds__(256) k_select_wg(const double* __restrict__ ln
   if (t == 0) counts[q] = so.count(taken);
 }
 
-// Same selection for references with more than 16384 branches: the row does not fit the register
-// file, so it is streamed from HBM/L2 once per pass (max, total, then one pass per selected
-// branch: 3-4 on typical data); taken branches are remembered in a per-lane bitmask
-// (element i lives in lane i % 64, bit i / 64; up to 64 x 64 x NW branches).
-template <int NW>
-__global__ void __launch_bounds__(256) k_select_big(const double* __restrict__ lnl, uint32_t Q, uint32_t B, uint32_t pitch,
-                                                    double threshold, int mode, uint32_t limit, SelOut so,
-                                                    uint32_t* __restrict__ counts,
-                                                    uint32_t* __restrict__ status) {
-  const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
-  if (q >= Q) return;
-  const double* src = lnl + (size_t)q * pitch;
-  unsigned long long takenmask[NW];
+// Same selection for references with more than 16384 branches: the row does not fit the register file, so it is streamed
+// from HBM/L2 -- workgroup of 256 per query, a fixed number of passes whatever the rule keeps (its predecessor streamed the row
+// once per SELECTED branch and remembered the taken ones in a per-lane mask of 65536 bits: profiles/large_tree_select.md).  Every rule keeps a PREFIX of the row in
+// selection order (lnL descending, branch ascending), so the work is: how long is the prefix (n), which key is its
+// last (K), how many of the elements equal to K belong to it (r of m, the lowest branch ids) -- then one pass
+// writes every element above K and the first r ties.  The order inside a query's staging row is free (the rows are
+// compacted query by query and sorted stably on the branch bits; the bitmap has no order at all).
+//   pass 1      row maximum;   pass 2   tot = sum exp(v - mx) (dynamic), strike-box hits (baseball)
+//   n           fixed: the host's ceil(x B); baseball: hits + the reference's wrapped top-up;
+//               dynamic, 0 < thr < 1: pass 3 compacts (seg_key, branch) of the elements within band_x of the maximum
+//               (k_select_seg's bound: what lies below cannot be needed to reach thr) into LDS; up to SS_CAP of them
+//               are sorted there by a bitonic network and SelRule walks the sorted prefix exactly as the other
+//               kernels do -- the list is then written straight from LDS (3 passes in all);
+//               dynamic otherwise (more than SS_CAP inside the band, thr >= 1): a radix select over the 64-bit keys,
+//               8 passes, whose 256-bin LDS histograms hold the LWR sums beside the counts: the digit where the
+//               accumulated LWR (from the top) reaches thr; the ties of the last key are added one by one.
+//   K, r, m     fixed / baseball: the same radix select on the counts alone (the n-th key from the top)
+//   last pass   elements above K, and the first r of the m ties in branch order (a running count per 256-branch
+//               step, only when r < m).
+// The LWR sums of the radix select are formed bin by bin (LDS atomics, then a scan), not in selection order: another
+// association than SelRule::accept's loop, the same decision wherever rounding cannot flip it.
+constexpr uint32_t SS_CAP = 2048;   // LDS list of the dynamic rule: 2048 x (8 + 4) B = 24 KB
+
+template <typename T>
+__device__ __forceinline__ T ss_block_scan(T v, T* __restrict__ s_w) {   // inclusive, 256 threads, s_w[4]
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int w = 0; w < NW; ++w) takenmask[w] = 0ull;
-  double mx = -INFINITY;
-  for (uint32_t i = lane; i < B; i += 64) mx = fmax(mx, src[i]);
-  mx = wave_max(mx);
-  double tot = 0.0;
-  for (uint32_t i = lane; i < B; i += 64) tot += exp(src[i] - mx);
-  tot = wave_add(tot);
-  SelRule rule(mode, threshold, limit);
-  uint32_t taken = 0;
-  while (rule.more(taken, B)) {
-    double best = -INFINITY;
-    uint32_t bi = 0xffffffffu;
-    for (uint32_t i = lane, r = 0; i < B; i += 64, ++r) {
-      const double v = src[i];
-      const bool free_ = !((takenmask[r >> 6] >> (r & 63)) & 1ull);
-      if (free_ && v > best) { best = v; bi = i; }
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-      const double ob = __shfl_xor(best, o);
-      const uint32_t oi = __shfl_xor(bi, o);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (bi == 0xffffffffu) break;
-    if (!rule.accept(best, mx, tot, taken)) break;
-    if ((bi & 63u) == lane) {
-      const uint32_t r = bi >> 6;
-#pragma unroll
-      for (int w = 0; w < NW; ++w)
-        if ((uint32_t)w == (r >> 6)) takenmask[w] |= 1ull << (r & 63);
-    }
-    if (lane == 0) so.put(q, bi, taken, status);
-    ++taken;
+  for (int o = 1; o < 64; o <<= 1) {
+    const T u = __shfl_up(v, o);
+    if ((int)lane >= o) v += u;
   }
-  if (lane == 0) counts[q] = so.count(taken);
+  __syncthreads();
+  if (lane == 63) s_w[wv] = v;
+  __syncthreads();
+  T before = 0;
+  for (uint32_t w = 0; w < wv; ++w) before += s_w[w];
+  return v + before;
+}
+
+__global__ void __launch_bounds__(256) k_select_stream(const double* __restrict__ lnl, uint32_t Q, uint32_t B, uint32_t pitch,
+                                                       double threshold, double band_x, int mode, uint32_t limit, SelOut so,
+                                                       uint32_t* __restrict__ counts, uint32_t* __restrict__ status) {
+  __shared__ unsigned long long s_key[SS_CAP];
+  __shared__ uint32_t s_br[SS_CAP];
+  __shared__ double s_hw[256];     // per digit: LWR sum, then its inclusive scan from the top digit down
+  __shared__ uint32_t s_hc[256];   // per digit: count, then its scan
+  __shared__ double s_wd[4];
+  __shared__ uint32_t s_wu[4];
+  __shared__ uint32_t s_cnt, s_first, s_last, s_n;
+  const uint32_t q = blockIdx.x;
+  if (q >= Q) return;
+  const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+  const double* src = lnl + (size_t)q * pitch;
+  // ---- pass 1: maximum
+  double mx = -INFINITY;
+  for (uint32_t i = t; i < B; i += 256) mx = fmax(mx, src[i]);
+  mx = wave_max(mx);
+  if (lane == 0) s_wd[wv] = mx;
+  if (t == 0) { s_cnt = 0u; s_n = 0xffffffffu; }
+  __syncthreads();
+  mx = fmax(fmax(s_wd[0], s_wd[1]), fmax(s_wd[2], s_wd[3]));
+  __syncthreads();
+  // ---- pass 2: total (dynamic) / strike-box hits (baseball)
+  double tot = 1.0;
+  uint32_t n = 0;
+  if (mode == 0) {
+    tot = 0.0;
+    for (uint32_t i = t; i < B; i += 256) tot += exp(src[i] - mx);
+    tot = wave_add(tot);
+    if (lane == 0) s_wd[wv] = tot;
+    __syncthreads();
+    tot = (s_wd[0] + s_wd[1]) + (s_wd[2] + s_wd[3]);
+    __syncthreads();
+  } else if (mode == 2) {
+    uint32_t hits = 0;
+    for (uint32_t i = t; i < B; i += 256) hits += !(src[i] < mx - 3.0) ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) hits += __shfl_xor(hits, o);
+    if (lane == 0) s_wu[wv] = hits;
+    __syncthreads();
+    hits = s_wu[0] + s_wu[1] + s_wu[2] + s_wu[3];
+    __syncthreads();
+    // SelRule::accept: std::min(max_pitches - hits, max_strikes) in size_t arithmetic, clamped at B by more()
+    n = (uint32_t)min((unsigned long long)B, (unsigned long long)hits + (hits > 40u ? 6u : min(40u - hits, 6u)));
+  } else {
+    n = min(limit, B);
+  }
+  const bool weighted = mode == 0;
+  bool listed = false;
+  if (weighted && threshold > 0.0 && threshold < 1.0) {
+    // ---- pass 3 (dynamic): the elements that can be candidates, into LDS
+    const double lo = mx - band_x;
+    for (uint32_t i = t; i < B; i += 256) {
+      const double v = src[i];
+      if (v >= lo) {
+        const uint32_t slot = atomicAdd(&s_cnt, 1u);
+        if (slot < SS_CAP) { s_key[slot] = seg_key(v); s_br[slot] = i; }
+      }
+    }
+    __syncthreads();
+    const uint32_t cnt = s_cnt;
+    if (cnt <= SS_CAP) {
+      uint32_t N = 2;
+      while (N < cnt) N <<= 1;
+      for (uint32_t i = cnt + t; i < N; i += 256) { s_key[i] = 0ull; s_br[i] = 0xffffffffu; }
+      __syncthreads();
+      for (uint32_t k = 2; k <= N; k <<= 1)
+        for (uint32_t j = k >> 1; j; j >>= 1) {
+          for (uint32_t i = t; i < N; i += 256) {
+            const uint32_t l = i ^ j;
+            if (l > i) {
+              const unsigned long long ka = s_key[i], kb = s_key[l];
+              const uint32_t ba = s_br[i], bb = s_br[l];
+              const bool inorder = ka > kb || (ka == kb && ba < bb);   // key descending, branch ascending
+              if (((i & k) == 0u) != inorder) { s_key[i] = kb; s_key[l] = ka; s_br[i] = bb; s_br[l] = ba; }
+            }
+          }
+          __syncthreads();
+        }
+      if (wv == 0) {   // the rule on the sorted prefix, wave-uniform
+        SelRule rule(0, threshold, 0u);
+        uint32_t taken = 0;
+        while (taken < cnt && rule.more(taken, B)) {
+          (void)rule.accept(seg_val(s_key[taken]), mx, tot, taken);
+          ++taken;
+        }
+        // the band holds every candidate by construction; a list that ended first goes to the radix select below
+        if (lane == 0 && !(taken == cnt && cnt < B && rule.more(taken, B))) s_n = taken;
+      }
+      __syncthreads();
+      if (s_n != 0xffffffffu) {
+        n = s_n;
+        listed = true;
+        for (uint32_t i = t; i < n; i += 256) so.put(q, s_br[i], i, status);
+      }
+    }
+  }
+  if (listed || (weighted && !(threshold > 0.0))) {   // (a threshold <= 0 keeps none)
+    if (t == 0) counts[q] = so.count(n);
+    return;
+  }
+  // ---- radix select, top digit first: K = key of the last kept element, r of its m ties are kept
+  unsigned long long K = 0ull;
+  uint32_t r = 0, m = 0;
+  bool all = weighted ? false : n >= B;
+  if (weighted || (n > 0 && !all)) {
+    unsigned long long prefix = 0ull;
+    uint32_t rem = n, cabove = 0;
+    double sabove = 0.0;
+    for (int p = 7; p >= 0 && !all; --p) {
+      const uint32_t shift = 8u * (uint32_t)p;
+      s_hc[t] = 0u;
+      s_hw[t] = 0.0;
+      if (t == 0) { s_first = 256u; s_last = 0u; }
+      __syncthreads();
+      for (uint32_t i = t; i < B; i += 256) {
+        const double v = src[i];
+        const unsigned long long k = seg_key(v);
+        if (p == 7 || (k >> (shift + 8u)) == prefix) {
+          const uint32_t d = (uint32_t)(k >> shift) & 255u;
+          atomicAdd(&s_hc[d], 1u);
+          if (weighted) atomicAdd(&s_hw[d], exp(v - mx) / tot);
+        }
+      }
+      __syncthreads();
+      // thread t owns digit 255 - t: scans run from the top digit down
+      const uint32_t c = s_hc[255u - t];
+      const double w = s_hw[255u - t];
+      const uint32_t ic = ss_block_scan<uint32_t>(c, s_wu);
+      const double iw = weighted ? ss_block_scan<double>(w, s_wd) : 0.0;
+      __syncthreads();
+      s_hc[t] = ic;   // from here on indexed by t, not by digit
+      s_hw[t] = iw;
+      if (c) {
+        if (weighted ? (sabove + iw >= threshold) : (ic >= rem)) atomicMin(&s_first, t);
+        atomicMax(&s_last, t);
+      }
+      __syncthreads();
+      uint32_t ts = s_first;
+      if (ts == 256u) {
+        // the whole row stays below thr (thr >= 1 and the like): everything is kept.  Further down only another
+        // rounding of the same sum can end here: the lowest digit present
+        if (p == 7) { all = true; n = B; break; }
+        ts = s_last;
+      }
+      const uint32_t ec = ts ? s_hc[ts - 1u] : 0u;
+      const double ew = ts ? s_hw[ts - 1u] : 0.0;
+      m = s_hc[ts] - ec;
+      cabove += ec;
+      rem -= weighted ? 0u : ec;
+      sabove += ew;
+      prefix = (prefix << 8) | (unsigned long long)(255u - ts);
+      __syncthreads();
+    }
+    if (!all) {
+      K = prefix;
+      if (weighted) {
+        const double w = exp(seg_val(K) - mx) / tot;
+        double sum = sabove;
+        while (r < m && sum < threshold) { sum += w; ++r; }
+        n = cabove + r;
+      } else {
+        r = rem;
+      }
+    }
+  }
+  // ---- last pass: everything above K, the first r ties in branch order
+  if (n > 0) {
+    const bool ordered = !all && r < m;
+    uint32_t tie_base = 0;
+    if (t == 0) s_cnt = 0u;   // now the staging rows' slot counter
+    __syncthreads();
+    for (uint32_t base = 0; base < B; base += 256) {
+      const uint32_t i = base + t;
+      const unsigned long long k = i < B ? seg_key(src[i]) : 0ull;
+      bool sel = i < B && (all || k > K);
+      bool eq = i < B && !all && k == K;
+      if (ordered) {
+        const unsigned long long bal = __ballot(eq);
+        if (lane == 0) s_wu[wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = tie_base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wv; ++w) before += s_wu[w];
+        tie_base += s_wu[0] + s_wu[1] + s_wu[2] + s_wu[3];
+        eq = eq && before < r;
+        __syncthreads();
+      }
+      sel = sel || eq;
+      uint32_t slot = 0;
+      if (!so.bitmap) {   // staging form: one slot per kept element, handed out per wave
+        const unsigned long long bal = __ballot(sel);
+        uint32_t wbase = 0;
+        if (lane == 0 && bal) wbase = atomicAdd(&s_cnt, (uint32_t)__popcll(bal));
+        wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+        slot = wbase + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      }
+      if (sel) so.put(q, i, slot, status);
+    }
+  }
+  if (t == 0) counts[q] = so.count(n);
 }
 
 // span-class histogram of the selected pairs: sum of the per-query candidate counts by the class
@@ -1680,8 +1870,9 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 int launch_build_lookup2(epa_ctx* ctx) {
   if (!ctx->lookup2)
     EPA_HIP(ctx, hipMalloc(&ctx->lookup2, sizeof(double) * (size_t)ctx->B * 2 * ((ctx->W + 1) / 2) * PE));
-  dim3 grid((ctx->W * PE + 255) / 256, ctx->B);
-  hipLaunchKernelGGL(k_build_lookup2, grid, dim3(256), 0, ctx->stream, ctx->lookup, ctx->W, ctx->lookup2);
+  for (uint32_t b0 = 0; b0 < ctx->B; b0 += EPA_GRID_Y)   // branch in grid.y, in slices of its limit
+    hipLaunchKernelGGL(k_build_lookup2, dim3((ctx->W * PE + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, ctx->B - b0)), dim3(256), 0,
+                       ctx->stream, ctx->lookup, ctx->W, ctx->lookup2, b0);
   EPA_HIP(ctx, hipGetLastError());
   return EPA_OK;
 }
@@ -1855,8 +2046,8 @@ int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double th
   const uint32_t B = ctx->B;
   const uint32_t pitch = ctx->lnl_pitch ? ctx->lnl_pitch : B;  // row pitch of d_lnl in doubles
   if (!sp->rerun) sp->pre_status = (const uint32_t*)ctx->d_status;
-  if (B > 64 * 64 * 16)
-    return epa_fail(ctx, EPA_ERR_UNSUPPORTED, "select_candidates: more than 65536 branches");
+  // k_select_stream (B > 16384): how far below the row maximum a candidate of the dynamic rule can lie (k_select_seg's bound)
+  const double stream_band = (ctx->heur_mode == 0 && threshold > 0.0 && threshold < 1.0) ? 1.0 - std::log((1.0 - threshold) / (double)B) : 0.0;
   // selection rule of the context (epa_dev_set_heuristic); fixed: ceil(x * B) best, at least... none:
   // until_top_percent keeps ceil(x * B) elements, 0 for x == 0 (src/set_manipulators.cpp:82-88)
   const int mode = ctx->heur_mode;
@@ -1916,7 +2107,7 @@ int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double th
     else if (nr <= 32) SEL(32); else if (nr <= 64) SEL(64);
     else if (nr <= 128) hipLaunchKernelGGL(k_select_wg<32>, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status);
     else if (nr <= 256) hipLaunchKernelGGL(k_select_wg<64>, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status);
-    else hipLaunchKernelGGL(k_select_big<16>, grid, dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status);
+    else hipLaunchKernelGGL(k_select_stream, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, stream_band, mode, limit, so, counts, status);
 #undef SEL
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, ctx->stream, bcount, B + 1);   // bcount[B] = total
     if (d_span && !seg_hist)
@@ -1962,13 +2153,11 @@ int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double th
   const int nr = (int)((B + 63) / 64);
   const SelOut so{sp->stage, cap, nullptr, nullptr, 0u};
 #define SEL(N) hipLaunchKernelGGL(k_select<N>, grid, dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status)
-#define SELBIG(N) hipLaunchKernelGGL(k_select_big<N>, grid, dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status)
   if (nr <= 2) SEL(2); else if (nr <= 4) SEL(4); else if (nr <= 8) SEL(8); else if (nr <= 16) SEL(16);
   else if (nr <= 32) SEL(32); else if (nr <= 64) SEL(64);
   else if (nr <= 128) hipLaunchKernelGGL(k_select_wg<32>, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status);
   else if (nr <= 256) hipLaunchKernelGGL(k_select_wg<64>, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status);
-  else SELBIG(16);
-#undef SELBIG
+  else hipLaunchKernelGGL(k_select_stream, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, stream_band, mode, limit, so, counts, status);
 #undef SEL
   EPA_HIP(ctx, rocprim::exclusive_scan(sp->temp, scan_bytes, counts, offsets, 0u, Q + 1,
                                        rocprim::plus<uint32_t>(), ctx->stream));

@@ -64,6 +64,8 @@ def host_lib():
                                              u32p, dp, u32p]
         L.epa_host_heuristic.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_int, C.c_double, u32p,
                                          u32p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.epa_host_device_chunk_reads.restype = C.c_uint64
+        L.epa_host_device_chunk_reads.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64]
         _LIB = L
     return _LIB
 
@@ -224,6 +226,14 @@ class Reference:
         if rc:
             raise RuntimeError(host_lib().epa_host_last_error().decode())
         return nq.value, npairs.value
+
+
+def device_chunk_reads(free_bytes, branches, slots, wanted, user_chunk=0):
+    """reads per device chunk of the CLI's chunk loop after its memory clamp: `slots` preplacement tables of
+    Q x pitch(branches) x 8 bytes plus a quarter fit half of `free_bytes`; at least 1; never above an explicit
+    --chunk-size (user_chunk, 0 = none)"""
+    return int(host_lib().epa_host_device_chunk_reads(int(free_bytes), int(branches), int(slots), int(wanted),
+                                                      int(user_chunk)))
 
 
 def filter_lwr(lwr, thresh, acc=False, mn=1, mx=0xffffffff):

@@ -511,8 +511,9 @@ uint64_t epa_comm_carried_rows(const epa_comm* comm);
 void epa_comm_abort(epa_comm* comm);
 
 /* free / total bytes of the context's device (hipMemGetInfo): the chunk loop sizes its device chunks
- * against it -- a chunk of Q queries keeps 2 pipeline slots x Q x pitch(B) x 8 bytes of preplacement
- * table live (`--chunk-size` is the user's memory knob, src/main.cpp:234-238). */
+ * against it -- every pipeline slot in use keeps its own preplacement table of Q x pitch(B) x 8 bytes
+ * live (the CLI's loop owns 4 slots and budgets 4 tables plus a quarter within half of the free bytes;
+ * `--chunk-size` is the user's memory knob, src/main.cpp:234-238). */
 int epa_dev_mem_info(epa_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 
 /* Diagnostics, no reference counterpart: the shares of a Newton launch's (branch-sorted) pair list that the device's
