@@ -18,7 +18,15 @@ DEV_SO = os.environ.get("EPA_DEV_SO", os.path.join(HERE, "libepa_dev.so"))
 __all__ = ["EpaError", "dev_lib", "device_count", "encode_queries", "Evaluator", "PAIR_DTYPE",
            "RESULT_DTYPE", "ROW_DTYPE", "DEV_SO", "Packed4", "pack_codes_4bit", "unpack_codes_4bit", "Comm",
            "comm_unique_id", "mapped_rccl_path", "comm_set_library", "comm_library_path", "comm_set_default_timeout",
-           "pci_id_str"]
+           "pci_id_str", "FLAG_LOOKUP_BLOCKS", "FLAG_LOOKUP_AUTO", "LOOKUP_RESIDENT", "LOOKUP_BLOCKS", "ERR_NO_MEMORY",
+           "footprint", "lookup_plan", "set_mem_cap"]
+
+# lookup layout of a context (include/epa_dev.h: EPA_FLAG_LOOKUP_*, EPA_LOOKUP_*, EPA_ERR_NO_MEMORY)
+FLAG_LOOKUP_BLOCKS = 0x40
+FLAG_LOOKUP_AUTO = 0x80
+LOOKUP_RESIDENT = 0
+LOOKUP_BLOCKS = 1
+ERR_NO_MEMORY = -10
 
 PAIR_DTYPE = np.dtype([("branch_id", np.uint32), ("seq_id", np.uint32)])
 RESULT_DTYPE = np.dtype([("lnl", np.float64), ("pendant_length", np.float64),
@@ -55,6 +63,11 @@ class _RefDesc(C.Structure):
 class _Stats(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("rounds", C.c_uint64), ("newton_evals", C.c_uint64),
                 ("reverts", C.c_uint64)]
+
+
+class _Footprint(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reft", "scsum", "lookup", "lookup2", "refi", "misc", "create_temp",
+                                          "reference", "bank", "steady", "peak")]
 
 
 _LIB = None
@@ -95,6 +108,8 @@ def dev_lib():
         L.epa_dev_set_query_layout.argtypes = [C.c_void_p, C.c_uint32]
         L.epa_dev_preplace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                        C.c_void_p]
+        L.epa_dev_preplace_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p]
         L.epa_dev_thorough.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(_Stats)]
         L.epa_dev_set_heuristic.argtypes = [C.c_void_p, C.c_int, C.c_double]
@@ -155,12 +170,48 @@ def dev_lib():
         L.epa_dev_last_sclk_mhz.argtypes = [C.c_void_p]
         L.epa_dev_last_sclk_mhz.restype = C.c_double
         L.epa_dev_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
+        L.epa_dev_footprint.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint32,
+                                        C.c_int, C.POINTER(_Footprint)]
+        L.epa_dev_lookup_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
+                                          C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
+        L.epa_dev_set_mem_cap.argtypes = [C.c_uint64]
+        L.epa_dev_set_mem_cap.restype = None
+        L.epa_dev_lookup_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
         _LIB = L
     return _LIB
 
 
 def device_count():
     return dev_lib().epa_dev_device_count()
+
+
+def footprint(states, rate_cats, sites, branches, flags=0, from_tree=False, block_branches=0, banks=1):
+    """device bytes of a reference (epa_dev_footprint; needs no device) -> dict: reft, scsum, lookup, lookup2, refi,
+    misc, create_temp, reference, bank, steady, peak.  flags & FLAG_LOOKUP_BLOCKS prices the blocked layout"""
+    L = dev_lib()
+    f = _Footprint()
+    rc = L.epa_dev_footprint(states, rate_cats, sites, branches, int(flags), int(from_tree), block_branches, banks,
+                             C.byref(f))
+    if rc:
+        raise EpaError(rc, (L.epa_dev_last_error(None) or b"").decode())
+    return {n: int(getattr(f, n)) for n, _ in _Footprint._fields_}
+
+
+def lookup_plan(usable_bytes, states, rate_cats, sites, branches, flags=0, from_tree=False, banks=1):
+    """layout for `usable_bytes` of device memory (epa_dev_lookup_plan; needs no device) -> (LOOKUP_RESIDENT, 0) or
+    (LOOKUP_BLOCKS, branches per block); EpaError with code ERR_NO_MEMORY when not even refT + scSum fit"""
+    L = dev_lib()
+    mode, blk = C.c_int(0), C.c_uint32(0)
+    rc = L.epa_dev_lookup_plan(int(usable_bytes), states, rate_cats, sites, branches, int(flags), int(from_tree), banks,
+                               C.byref(mode), C.byref(blk))
+    if rc:
+        raise EpaError(rc, (L.epa_dev_last_error(None) or b"").decode())
+    return mode.value, blk.value
+
+
+def set_mem_cap(nbytes):
+    """process-wide bound of what context creation plans with instead of the device's free memory (0 = none)"""
+    dev_lib().epa_dev_set_mem_cap(int(nbytes))
 
 
 class Packed4:
@@ -248,7 +299,8 @@ class Evaluator:
     def __init__(self, states, rates, weights, eigenvals, u, uinv, freqs, branch_length,
                  prox_clv, dist_clv, prox_scaler=None, dist_scaler=None, dist_tip=None,
                  tipmap=None, device=0, aa_x_as_n=False, pinv=0.0, invariant_state=None, flags=0):
-        """flags: EPA_FLAG_* of include/epa_dev.h (0x2 = per-rate scalers: the scaler rows are then uint32 [W][c])"""
+        """flags: EPA_FLAG_* of include/epa_dev.h (0x2 = per-rate scalers: the scaler rows are then uint32 [W][c];
+        FLAG_LOOKUP_BLOCKS / FLAG_LOOKUP_AUTO: lookup tables rebuilt per branch block and chunk instead of resident)"""
         L = dev_lib()
         B = len(branch_length)
         self.B, self.s, self.c = B, states, len(rates)
@@ -345,6 +397,18 @@ class Evaluator:
         self._check(self.L.epa_dev_preplace(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span),
                                             Q, _ptr(out)))
         return out
+
+    def preplace_bounded(self, codes, win_begin, win_span, max_span, seg_keys=False):
+        """preplace() with an upper bound of the window spans, which selects the single-chunk kernels of the fused
+        chunk body (epa_dev_preplace_bounded) -> lnl [Q][B], or (lnl, keys uint64 [Q][pitch]) with seg_keys=True: the
+        per-(query, 64-branch segment) maxima those kernels leave for the selection, as order-preserving keys"""
+        Q = len(win_begin)
+        out = np.empty((Q, self.B), np.float64)
+        keys = np.zeros((Q, ((self.B + 63) // 64 + 7) // 8 * 8), np.uint64) if seg_keys else None
+        self._layout(codes)
+        self._check(self.L.epa_dev_preplace_bounded(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q,
+                                                    int(max_span), _ptr(out), _ptr(keys)))
+        return (out, keys) if seg_keys else out
 
     def thorough(self, pairs, codes, win_begin, win_span, Q=None, n_pairs=None, out=None):
         """pairs: structured PAIR_DTYPE array (or device buffer) -> RESULT_DTYPE array."""
@@ -522,6 +586,18 @@ class Evaluator:
 
     def kernel_ms(self, which):
         return self.L.epa_dev_last_kernel_ms(self.h, which.encode())
+
+    def lookup_mode(self):
+        """-> (LOOKUP_RESIDENT, 0) or (LOOKUP_BLOCKS, branches per block buffer) (epa_dev_lookup_mode)"""
+        mode, blk = C.c_int(0), C.c_uint32(0)
+        self._check(self.L.epa_dev_lookup_mode(self.h, C.byref(mode), C.byref(blk)))
+        return mode.value, blk.value
+
+    def mem_info(self):
+        """-> (free, total) bytes of the context's device (epa_dev_mem_info)"""
+        fr, tot = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.epa_dev_mem_info(self.h, C.byref(fr), C.byref(tot)))
+        return fr.value, tot.value
 
 
 def comm_unique_id():

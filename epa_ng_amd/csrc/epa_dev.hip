@@ -237,8 +237,11 @@ int launch_transform(epa_ctx* ctx, const double* d_clv, const uint8_t* d_tip,
 //   Lookup_Store::init_branch (:18-46,114-128; src/core/Lookup_Store.hpp:73-81).
 // One thread per (branch, site); the inner CLV never leaves registers.
 // HBM-bound: reads 2*c*s*8 B + 4 B, writes ncols*8 B per site.
+// BLOCK (blocked lookup layout): refT / scSum / blen are read at the absolute branch b0 + y, the table row goes to
+// row r0 + y of a block buffer, and the starting vectors of the Newton kernels (refI / resc0: c*s*8 + 1 B per
+// branch x site of write traffic) are neither formed nor stored -- the branch is compiled out, not tested per site.
 // =============================================================================================
-template <int S>
+template <int S, bool BLOCK = false>
 __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict__ m,
                                                       const double* __restrict__ refT,
                                                       const uint32_t* __restrict__ scSum,
@@ -247,7 +250,8 @@ __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict
                                                       double* __restrict__ lookup,
                                                       double* __restrict__ refI,
                                                       uint8_t* __restrict__ resc0,
-                                                      const double* __restrict__ cinv, uint32_t b0) {
+                                                      const double* __restrict__ cinv, uint32_t b0,
+                                                      uint32_t r0) {
   __shared__ double U[S * S], Ui[S * S];
   __shared__ double Eh[EPA_MAX_CATS * S], Ep[EPA_MAX_CATS * S];  // exp tables: half branch, pendant
   const int c = m->c, ncols = m->ncols;
@@ -290,7 +294,7 @@ __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict
   // per-site scaling of pll_update_partials: every entry below 2^-256 -> multiply by 2^256
   const bool resc = mx < 0x1p-256;
   if (resc) sc += 1;
-  if (resc0) resc0[(size_t)b * W + site] = resc ? 1 : 0;
+  if constexpr (!BLOCK) { if (resc0) resc0[(size_t)b * W + site] = resc ? 1 : 0; }
   const double mult = resc ? 0x1p+256 : 1.0;
   // g[k][i] = pi_i * (P_pendant I)_i  via the eigenbasis: P I = U (e o (Ui I))
   double g[EPA_MAX_CATS][S];
@@ -302,7 +306,7 @@ __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict
 #pragma unroll
       for (int i = 0; i < S; ++i) acc = fma(Ui[x * S + i], I[k][i] * mult, acc);
       // the thorough kernel starts every pair from exactly this vector (same lengths): keep it
-      if (refI) refI[((size_t)b * c * S + (size_t)(k * S + x)) * W + site] = acc;
+      if constexpr (!BLOCK) { if (refI) refI[((size_t)b * c * S + (size_t)(k * S + x)) * W + site] = acc; }
       it[x] = acc * Ep[k * S + x];
     }
 #pragma unroll
@@ -314,7 +318,7 @@ __global__ void __launch_bounds__(256) k_build_lookup(const ModelDev* __restrict
     }
   }
   const double log_thr = -256.0 * 0.6931471805599453094;  // log(2^-256)
-  double* out = lookup + ((size_t)b * W + site) * ncols;
+  double* out = lookup + ((size_t)(BLOCK ? r0 + blockIdx.y : b) * W + site) * ncols;
   for (int col = 0; col < ncols; ++col) {
     const uint32_t mask = m->colmask[col];
     double terma = 0.0;
@@ -339,11 +343,11 @@ int launch_build_lookup(epa_ctx* ctx) {
     if (ctx->s == 4)
       hipLaunchKernelGGL(k_build_lookup<4>, grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT,
                          ctx->scSum, ctx->blen, ctx->blo.pendant_default, ctx->W, ctx->lookup, ctx->refI,
-                         ctx->resc0, ctx->cinv, b0);
+                         ctx->resc0, ctx->cinv, b0, 0u);
     else
       hipLaunchKernelGGL(k_build_lookup<20>, grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT,
                          ctx->scSum, ctx->blen, ctx->blo.pendant_default, ctx->W, ctx->lookup, ctx->refI,
-                         ctx->resc0, ctx->cinv, b0);
+                         ctx->resc0, ctx->cinv, b0, 0u);
   }
   EPA_HIP(ctx, hipGetLastError());
   if (ctx->s == 4) {
@@ -352,6 +356,42 @@ int launch_build_lookup(epa_ctx* ctx) {
   }
   epa_timer_stop(ctx, ctx->t_lookup);
   return EPA_OK;
+}
+
+// Blocked layout: lookup rows of branches [b0, b0 + nb) into rows [0, nb) of a block buffer (no timer of its own:
+// launch_preplace brackets the block's builds with the "lookup_block" events).
+int launch_build_lookup_block(epa_ctx* ctx, uint32_t b0, uint32_t nb, double* blk_lookup) {
+  for (uint32_t r0 = 0; r0 < nb; r0 += EPA_GRID_Y) {   // branch in grid.y, in slices of its limit
+    const dim3 grid((ctx->W + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, nb - r0));
+    if (ctx->s == 4)
+      hipLaunchKernelGGL((k_build_lookup<4, true>), grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT, ctx->scSum,
+                         ctx->blen, ctx->blo.pendant_default, ctx->W, blk_lookup, (double*)nullptr, (uint8_t*)nullptr,
+                         ctx->cinv, b0 + r0, r0);
+    else
+      hipLaunchKernelGGL((k_build_lookup<20, true>), grid, dim3(256), 0, ctx->stream, ctx->dmodel, ctx->refT, ctx->scSum,
+                         ctx->blen, ctx->blo.pendant_default, ctx->W, blk_lookup, (double*)nullptr, (uint8_t*)nullptr,
+                         ctx->cinv, b0 + r0, r0);
+  }
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}
+
+uint32_t epa_block_branches(const epa_ctx* ctx) {
+  return std::min<uint32_t>(ctx->lookup_block, (ctx->B + 63u) & ~63u);
+}
+size_t epa_block_bytes(int s, uint32_t W, uint32_t blk, size_t* off2) {
+  const size_t l1 = sizeof(double) * (size_t)blk * W * (s == 4 ? 16 : 24);
+  if (off2) *off2 = l1;
+  return l1 + (s == 4 ? sizeof(double) * (size_t)blk * 2 * ((W + 1) / 2) * 36 : 0);
+}
+void* epa_block_buffer(epa_ctx* ctx) {
+  const size_t need = epa_block_bytes(ctx->s, ctx->W, epa_block_branches(ctx), nullptr);
+  void*& p = ctx->blk_buf[ctx->bank];
+  if (p && ctx->blk_sz[ctx->bank] == need) return p;
+  if (p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); p = nullptr; ctx->blk_sz[ctx->bank] = 0; }
+  if (hipMalloc(&p, need) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
+  ctx->blk_sz[ctx->bank] = need;
+  return p;
 }
 
 // src: the caller's scaler row, [W] or (per-rate scalers) libpll's [W][cdim]; dst: [cdim][W]
@@ -505,6 +545,14 @@ extern "C" int epa_dev_set_query_layout(epa_ctx* ctx, uint32_t code_stride) {
 
 extern "C" int epa_dev_set_option(epa_ctx* ctx, const char* key, int value) {
   if (!ctx || !key) return EPA_ERR_INVALID_ARG;
+  if (strcmp(key, "lookup_block") == 0) {
+    if (!ctx->lookup_blocks) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "set_option: lookup_block needs a context in the blocked lookup layout");
+    if (value <= 0 || (value & 63)) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "set_option: lookup_block must be a positive multiple of 64");
+    for (void* p : ctx->blk_buf)
+      if (p) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "set_option: lookup_block must be set before the first preplacement");
+    ctx->lookup_block = (uint32_t)value;
+    return EPA_OK;
+  }
   struct Entry { const char* name; int EpaOptions::*field; };
   static const Entry table[] = {
       {"thorough_generic", &EpaOptions::thorough_generic}, {"preplace_generic", &EpaOptions::preplace_generic},
@@ -602,6 +650,8 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
   if (ctx->blen) (void)hipFree(ctx->blen);
   if (ctx->lookup) (void)hipFree(ctx->lookup);
   if (ctx->lookup2) (void)hipFree(ctx->lookup2);
+  for (void* p : ctx->blk_buf) if (p) (void)hipFree(p);
+  for (auto& v : ctx->blk_ev) for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e);
   if (ctx->th_ctr) (void)hipFree(ctx->th_ctr);
   for (hipEvent_t e : ctx->ev_rb) if (e) (void)hipEventDestroy(e);
   if (ctx->refI) (void)hipFree(ctx->refI);
@@ -635,6 +685,113 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
 }
 
 static int precompute_from_tree(epa_ctx* ctx, const epa_tree_desc* t, const uint32_t* d_tipmap);
+
+// ---- memory footprint and lookup layout plan: pure host arithmetic, shared with create_impl
+// The tuned thorough kernels work on groups of 4 rate categories.  1 or 2 categories (no +G, +G2)
+// are replicated to 4 with the weights divided accordingly: sum_k w_k L_k is unchanged.  Nucleotide
+// models with 3 or 5 .. 16 categories (+G8, +R5, ...) are padded to the next multiple of 4 with copies
+// of the last category at weight 0: every weighted sum gains exact zeros, the per-site rescale
+// test (all entries < 2^-256) sees values it has already seen -- results are those of the
+// unpadded model, and k_thorough_dna serves them with one wave per group of four.
+static int padded_cats(int s, int c_in, uint32_t flags, bool from_tree) {
+  int c = (c_in == 1 || c_in == 2) ? 4 : c_in;
+  if (s == 4 && c_in >= 3 && (c_in & 3)) c = (c_in + 3) & ~3;
+  // 20 states: 3 -> 4, 5 .. 7 -> 8 (k_thorough_aa_mfma serves 4 and 8 categories; more go to the general kernel)
+  if (s == 20 && (c_in == 3 || (c_in >= 5 && c_in <= 7))) c = (c_in + 3) & ~3;
+  // per-rate scaler rows from the caller ([W][c_in]) cannot be padded here: such a context keeps its category
+  // count and runs on the general kernel (as before the category groups existed)
+  if (c_in >= 3 && c != c_in && (flags & EPA_FLAG_RATE_SCALERS) && !from_tree) c = c_in;
+  return c;
+}
+
+// Does a tuned Newton kernel serve the shape (else: k_thorough_generic, and no refI / resc0)?  ONE predicate for
+// create_impl and epa_dev_footprint.  c: padded categories; zero0: the stationary eigenvalue is exactly 0 after create's
+// reorder (any proper GTR without EPA_FLAG_KEEP_EIGENVALUES; the footprint, which sees no eigenvalues, assumes so).
+// The tuned kernels are built for 4 categories (the Newton-variant switches exist to pin parity once a reference build
+// is at hand, not for production runs: they are served by the general kernel too).  --raxml-blo has tuned
+// instantiations for nucleotide models with an exact zero eigenvalue, with or without +I, and for 20-state models;
+// more than 4 categories: nucleotide models, sliding rule, zero eigenvalue (k_thorough_dna), or 20 states x 8.
+static bool tuned_thorough_shape(int s, int c, uint32_t flags, bool zero0) {
+  const bool sliding = !(flags & EPA_FLAG_RAXML_BLO);
+  const bool dna_groups = s == 4 && (c & 3) == 0 && c <= 16;
+  const bool tuned_local = (s == 4 && zero0) || s == 20;
+  const bool tuned_cats = c == 4 || (dna_groups && sliding && zero0) || (s == 20 && c == 8);
+  return tuned_cats && (sliding || tuned_local) &&
+         !(flags & (EPA_FLAG_NEWTON_SLOW_BISECT | EPA_FLAG_NEWTON_STRICT_DF | EPA_FLAG_KEEP_EIGENVALUES));
+}
+
+static std::atomic<uint64_t> g_mem_cap{0};
+extern "C" void epa_dev_set_mem_cap(uint64_t bytes) { g_mem_cap.store(bytes, std::memory_order_relaxed); }
+
+constexpr uint32_t EPA_BLOCK_DEFAULT = 1024;   // branches per block buffer: cfg2's 1021 branches are one block
+constexpr int EPA_PLAN_BANKS = 4;              // banks create plans for: the slots of the CLI's chunk loop
+
+extern "C" int epa_dev_footprint(uint32_t states, uint32_t rate_cats, uint64_t sites, uint64_t branches, int flags,
+                                 int from_tree, uint32_t block_branches, int banks, epa_footprint* out) {
+  if (!out || !(states == 4 || states == 20) || rate_cats < 1 || rate_cats > EPA_MAX_CATS || !sites || !branches ||
+      sites > 0xffffffffull || branches > 0xffffffffull || banks < 0 || (block_branches & 63u))
+    return epa_fail(nullptr, EPA_ERR_INVALID_ARG, "footprint: bad shape");
+  const uint64_t s = states, W = sites, B = branches;
+  const uint64_t c = (uint64_t)padded_cats((int)states, (int)rate_cats, (uint32_t)flags, from_tree != 0);
+  const bool blocks = (flags & EPA_FLAG_LOOKUP_BLOCKS) != 0;
+  const bool tuned = tuned_thorough_shape((int)s, (int)c, (uint32_t)flags, !(flags & EPA_FLAG_KEEP_EIGENVALUES));
+  epa_footprint f;
+  memset(&f, 0, sizeof(f));
+  f.reft = 8 * 2 * B * c * s * W;
+  f.scsum = 4 * B * W;
+  if (!blocks) {
+    f.lookup = 8 * B * W * (s == 4 ? 16 : 24);
+    f.lookup2 = s == 4 ? 8 * B * 2 * ((W + 1) / 2) * 36 : 0;
+    f.refi = tuned ? 8 * B * c * s * W + B * W : 0;
+  } else {
+    const uint64_t blk = std::min<uint64_t>(block_branches ? block_branches : EPA_BLOCK_DEFAULT, (B + 63) & ~(uint64_t)63);
+    f.bank = 8 * blk * W * (s == 4 ? 16 : 24) + (s == 4 ? 8 * blk * 2 * ((W + 1) / 2) * 36 : 0);
+  }
+  f.misc = 8 * B + sizeof(ModelDev) + 256 * (uint64_t)epa_ctx::N_BANKS;
+  if (from_tree) {   // precompute_from_tree: tip rows, records, per-side scaler counts, tip of branch
+    const uint64_t n = (B + 3) / 2, cdim = (flags & EPA_FLAG_RATE_SCALERS) ? c : 1;
+    f.create_temp = n * W + 32 * 3 * (n - 2) + 4 * 2 * B * cdim * W + 4 * B;
+  }
+  f.reference = f.reft + f.scsum + f.lookup + f.lookup2 + f.refi + f.misc;
+  f.steady = f.reference + (uint64_t)banks * f.bank;
+  f.peak = std::max(f.steady, f.reference + f.create_temp);
+  *out = f;
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_lookup_plan(uint64_t usable_bytes, uint32_t states, uint32_t rate_cats, uint64_t sites,
+                                   uint64_t branches, int flags, int from_tree, int banks, int* mode,
+                                   uint32_t* block_branches) {
+  if (!mode || !block_branches) return epa_fail(nullptr, EPA_ERR_INVALID_ARG, "lookup_plan: null argument");
+  epa_footprint f;
+  const int base = flags & ~(int)(EPA_FLAG_LOOKUP_BLOCKS | EPA_FLAG_LOOKUP_AUTO);
+  int rc = epa_dev_footprint(states, rate_cats, sites, branches, base, from_tree, 0, banks, &f);
+  if (rc) return rc;
+  if (!(flags & EPA_FLAG_LOOKUP_BLOCKS) && f.peak <= usable_bytes) {
+    *mode = EPA_LOOKUP_RESIDENT;
+    *block_branches = 0;
+    return EPA_OK;
+  }
+  for (uint32_t blk = EPA_BLOCK_DEFAULT; blk >= 64; blk -= 64) {
+    rc = epa_dev_footprint(states, rate_cats, sites, branches, base | (int)EPA_FLAG_LOOKUP_BLOCKS, from_tree, blk, banks, &f);
+    if (rc) return rc;
+    if (f.peak <= usable_bytes) {
+      *mode = EPA_LOOKUP_BLOCKS;
+      *block_branches = blk;
+      return EPA_OK;
+    }
+  }
+  return epa_fail(nullptr, EPA_ERR_NO_MEMORY,
+                  "the reference does not fit the device: " + std::to_string(f.peak) + " bytes needed (blocked lookup layout, blocks of 64 branches, " +
+                      std::to_string(banks) + " banks), " + std::to_string(usable_bytes) + " bytes usable");
+}
+
+extern "C" int epa_dev_lookup_mode(const epa_ctx* ctx, int* mode, uint32_t* block_branches) {
+  if (!ctx) return EPA_ERR_INVALID_ARG;
+  if (mode) *mode = ctx->lookup_blocks ? EPA_LOOKUP_BLOCKS : EPA_LOOKUP_RESIDENT;
+  if (block_branches) *block_branches = ctx->lookup_blocks ? ctx->lookup_block : 0u;
+  return EPA_OK;
+}
 __global__ void k_align_rates(const ModelDev* __restrict__ m, double* __restrict__ refT,
                               const uint32_t* __restrict__ sc_side, uint32_t* __restrict__ scSum, uint32_t W, uint32_t b0);
 
@@ -642,19 +799,7 @@ static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const ep
   const int s = (int)d->states, c_in = (int)d->rate_cats;
   if (!(s == 4 || s == 20)) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "states must be 4 or 20");
   if (c_in < 1 || c_in > EPA_MAX_CATS) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rate_cats out of range");
-  // The tuned thorough kernels work on groups of 4 rate categories.  1 or 2 categories (no +G, +G2)
-  // are replicated to 4 with the weights divided accordingly: sum_k w_k L_k is unchanged.  Nucleotide
-  // models with 3 or 5 .. 16 categories (+G8, +R5, ...) are padded to the next multiple of 4 with copies
-  // of the last category at weight 0: every weighted sum gains exact zeros, the per-site rescale
-  // test (all entries < 2^-256) sees values it has already seen -- results are those of the
-  // unpadded model, and k_thorough_dna serves them with one wave per group of four.
-  int c = (c_in == 1 || c_in == 2) ? 4 : c_in;
-  if (s == 4 && c_in >= 3 && (c_in & 3)) c = (c_in + 3) & ~3;
-  // 20 states: 3 -> 4, 5 .. 7 -> 8 (k_thorough_aa_mfma serves 4 and 8 categories; more go to the general kernel)
-  if (s == 20 && (c_in == 3 || (c_in >= 5 && c_in <= 7))) c = (c_in + 3) & ~3;
-  // per-rate scaler rows from the caller ([W][c_in]) cannot be padded here: such a context keeps its category
-  // count and runs on the general kernel (as before the category groups existed)
-  if (c_in >= 3 && c != c_in && (d->flags & EPA_FLAG_RATE_SCALERS) && !tree) c = c_in;
+  const int c = padded_cats(s, c_in, d->flags, tree != nullptr);
   if (c_in != c && (d->flags & EPA_FLAG_RATE_SCALERS) && !tree)
     return epa_fail(ctx, EPA_ERR_UNSUPPORTED,
                     "per-rate scaler arrays of a 1- or 2-category model (replicated to four): use epa_dev_create_from_tree");
@@ -743,35 +888,64 @@ static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const ep
   ctx->blo.newton_variant = ((d->flags & EPA_FLAG_NEWTON_SLOW_BISECT) ? 1u : 0u) |
                             ((d->flags & EPA_FLAG_NEWTON_STRICT_DF) ? 2u : 0u);
   ctx->rate_scalers = (d->flags & EPA_FLAG_RATE_SCALERS) != 0;
-  // the tuned thorough kernels are built for 4 categories (the Newton-variant switches exist to pin
-  // parity once a reference build is at hand, not for production runs: they are served by the general
-  // kernel too, the tuned kernels cost 1.7 % with them).  --raxml-blo has tuned instantiations for
-  // nucleotide models with an exact zero eigenvalue, with or without +I (k_thorough_dna<.., INV, .., LOCAL>),
-  // and for 20-state models (k_thorough_aa_mfma<.., LOCAL>); everything else local goes general.
-  const bool tuned_local = (s == 4 && ctx->dna_zero0) || s == 20;
-  // (more than 4 categories: tuned for nucleotide models, sliding rule, zero eigenvalue -- the class
-  // launcher of thorough_dna.hip sends what it does not serve to the general kernel itself)
-  const bool tuned_cats = c == 4 || (dna_groups && ctx->blo.sliding && ctx->dna_zero0) ||
-                          (s == 20 && c == 8);   // k_thorough_aa_mfma<.., NC = 8>
-  ctx->generic_thorough = !tuned_cats || (!ctx->blo.sliding && !tuned_local) || ctx->blo.newton_variant != 0 ||
-                          (d->flags & EPA_FLAG_KEEP_EIGENVALUES) != 0;     // every term as libpll: the general kernel
+  ctx->generic_thorough = !tuned_thorough_shape(s, c, d->flags, ctx->dna_zero0);
   ctx->generic_native = ctx->generic_thorough;
   // (epa_dev_set_option "thorough_generic" sends a context that has tuned kernels to the general one as well)
+
+  // Lookup layout.  flags 0: everything resident, as ever.  _BLOCKS / _AUTO: the plan decides
+  // (and sizes the blocks) against the device's free memory, or the process-wide cap in its place.
+  const bool planned = (d->flags & (EPA_FLAG_LOOKUP_BLOCKS | EPA_FLAG_LOOKUP_AUTO)) != 0;
+  auto usable_bytes = [&]() -> uint64_t {   // what the plan works with; flags 0 never look at the cap
+    const uint64_t cap = planned ? g_mem_cap.load(std::memory_order_relaxed) : 0;
+    if (cap) return cap;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return fr;
+  };
+  const int fp_flags = (int)(d->flags & ~(EPA_FLAG_LOOKUP_BLOCKS | EPA_FLAG_LOOKUP_AUTO));
+  if (planned) {
+    int mode = EPA_LOOKUP_RESIDENT;
+    uint32_t blk = 0;
+    const int prc = epa_dev_lookup_plan(usable_bytes(), (uint32_t)s, (uint32_t)c_in, d->sites, d->branches, (int)d->flags,
+                                        tree ? 1 : 0, EPA_PLAN_BANKS, &mode, &blk);
+    if (prc) return epa_fail(ctx, prc, g_create_err);
+    ctx->lookup_blocks = mode == EPA_LOOKUP_BLOCKS;
+    if (ctx->lookup_blocks) ctx->lookup_block = blk;
+  }
+  // a reference-sized allocation that fails: needed against usable bytes instead of a bare HIP error
+  auto ref_alloc = [&](void** p, size_t bytes, const char* what) -> int {
+    if (hipMalloc(p, bytes) == hipSuccess) return EPA_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    epa_footprint f;
+    memset(&f, 0, sizeof(f));
+    (void)epa_dev_footprint((uint32_t)s, (uint32_t)c_in, d->sites, d->branches,
+                            fp_flags | (ctx->lookup_blocks ? (int)EPA_FLAG_LOOKUP_BLOCKS : 0), tree ? 1 : 0,
+                            ctx->lookup_blocks ? ctx->lookup_block : 0, EPA_PLAN_BANKS, &f);
+    return epa_fail(ctx, EPA_ERR_NO_MEMORY,
+                    std::string("the reference does not fit the device (hipMalloc of ") + what + ", " + std::to_string(bytes) +
+                        " bytes): " + std::to_string(f.peak) + " bytes needed (" + (ctx->lookup_blocks ? "blocked" : "resident") +
+                        " lookup layout), " + std::to_string(usable_bytes()) + " bytes usable");
+  };
+#define REF_ALLOC(p, bytes, what) do { const int a__ = ref_alloc((void**)&(p), (bytes), (what)); if (a__) return a__; } while (0)
 
   EPA_HIP(ctx, hipMalloc(&ctx->dmodel, sizeof(ModelDev)));
   EPA_HIP(ctx, hipMemcpy(ctx->dmodel, &m, sizeof(ModelDev), hipMemcpyHostToDevice));
 
   const size_t W = ctx->W, B = ctx->B, cs = (size_t)c * s;
-  EPA_HIP(ctx, hipMalloc(&ctx->refT, sizeof(double) * 2 * B * cs * W));
+  REF_ALLOC(ctx->refT, sizeof(double) * 2 * B * cs * W, "refT");
   EPA_HIP(ctx, hipMalloc(&ctx->th_ctr, 256 * epa_ctx::N_BANKS));
-  EPA_HIP(ctx, hipMalloc(&ctx->scSum, sizeof(uint32_t) * B * W));
+  REF_ALLOC(ctx->scSum, sizeof(uint32_t) * B * W, "scSum");
   EPA_HIP(ctx, hipMemset(ctx->scSum, 0, sizeof(uint32_t) * B * W));
   EPA_HIP(ctx, hipMalloc(&ctx->blen, sizeof(double) * B));
-  EPA_HIP(ctx, hipMalloc(&ctx->lookup, sizeof(double) * B * W * ctx->ncols));
-  if (!ctx->generic_thorough) {  // starting vectors of the tuned thorough kernels
-    EPA_HIP(ctx, hipMalloc(&ctx->refI, sizeof(double) * B * cs * W));
-    EPA_HIP(ctx, hipMalloc(&ctx->resc0, B * W));
+  if (!ctx->lookup_blocks) {
+    REF_ALLOC(ctx->lookup, sizeof(double) * B * W * ctx->ncols, "lookup");
+    if (!ctx->generic_thorough) {  // starting vectors of the tuned thorough kernels
+      REF_ALLOC(ctx->refI, sizeof(double) * B * cs * W, "refI");
+      REF_ALLOC(ctx->resc0, B * W, "resc0");
+    }
   }
+#undef REF_ALLOC
   ctx->h_blen.assign(d->branch_length, d->branch_length + B);
   EPA_HIP(ctx, hipMemcpy(ctx->blen, d->branch_length, sizeof(double) * B, hipMemcpyHostToDevice));
 
@@ -1105,13 +1279,22 @@ static int precompute_from_tree(epa_ctx* ctx, const epa_tree_desc* t, const uint
   uint8_t* d_tips = nullptr;
   RecDev* d_recs = nullptr;
   uint32_t *d_sc = nullptr, *d_tob = nullptr;
+  std::string tree_oom;   // needed against free bytes, for a precompute buffer that does not fit
+  {
+    epa_footprint f;
+    size_t fr = 0, tot = 0;
+    if (epa_dev_footprint((uint32_t)ctx->s, (uint32_t)ctx->c_in, W, B, (ctx->rate_scalers ? (int)EPA_FLAG_RATE_SCALERS : 0) |
+                          (ctx->lookup_blocks ? (int)EPA_FLAG_LOOKUP_BLOCKS : 0), 1, ctx->lookup_blocks ? ctx->lookup_block : 0,
+                          EPA_PLAN_BANKS, &f) == EPA_OK && hipMemGetInfo(&fr, &tot) == hipSuccess)
+      tree_oom = " (reference precompute: " + std::to_string(f.peak) + " bytes needed, " + std::to_string(fr) + " bytes free now)";
+  }
   auto cleanup = [&]() {
     if (d_tips) (void)hipFree(d_tips);
     if (d_recs) (void)hipFree(d_recs);
     if (d_sc) (void)hipFree(d_sc);
     if (d_tob) (void)hipFree(d_tob);
   };
-#define TREE_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return epa_fail(ctx, EPA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
+#define TREE_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); (void)hipGetLastError(); return epa_fail(ctx, e__ == hipErrorOutOfMemory ? EPA_ERR_NO_MEMORY : EPA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__) + (e__ == hipErrorOutOfMemory ? tree_oom : std::string())); } } while (0)
   TREE_HIP(hipMalloc(&d_tips, (size_t)n * W));
   TREE_HIP(hipMemcpy(d_tips, t->tipchars, (size_t)n * W, hipMemcpyHostToDevice));
   TREE_HIP(hipMalloc(&d_recs, sizeof(RecDev) * recs.size()));
@@ -1258,7 +1441,7 @@ extern "C" int epa_dev_create(const epa_ref_desc* desc, int device, epa_ctx** ou
 
 extern "C" int epa_dev_build_lookup(epa_ctx* ctx) {
   if (!ctx) return EPA_ERR_INVALID_ARG;
-  if (ctx->lookup_built) return EPA_OK;
+  if (ctx->lookup_built || ctx->lookup_blocks) return EPA_OK;   // blocked layout: built inside the chunk body
   EPA_HIP(ctx, hipSetDevice(ctx->device));
   int rc = launch_build_lookup(ctx);
   if (rc) return rc;
@@ -1302,12 +1485,29 @@ static int check_windows(epa_ctx* ctx, const uint32_t* hb, const uint32_t* hs, u
 
 extern "C" int epa_dev_preplace(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
                                 const uint32_t* win_span, uint32_t Q, double* lnl) {
+  return epa_dev_preplace_bounded(ctx, q_codes, win_begin, win_span, Q, 0, lnl, nullptr);
+}
+
+extern "C" int epa_dev_preplace_bounded(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
+                                        const uint32_t* win_span, uint32_t Q, uint32_t max_span, double* lnl,
+                                        uint64_t* seg_keys) {
   if (!ctx || !q_codes || !win_begin || !win_span || !lnl)
     return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
   if (Q == 0) return EPA_OK;
   EPA_HIP(ctx, hipSetDevice(ctx->device));
   int rc = epa_dev_build_lookup(ctx);
   if (rc) return rc;
+  if (max_span > ctx->W) max_span = ctx->W;
+  if (max_span && !epa_is_device_ptr(win_span))   // the single-chunk kernels trust the bound
+    for (uint32_t q = 0; q < Q; ++q)
+      if (win_span[q] > max_span) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "preplace: a window is longer than max_span");
+  const uint32_t nseg = (ctx->B + 63) / 64, segp = (nseg + 7u) & ~7u;
+  unsigned long long* d_seg = nullptr;
+  if (seg_keys) {   // the by-product the fused chunk body's selection reads (chunk_body_begin)
+    if (nseg > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "preplace: segment maxima exist up to 4096 branches");
+    d_seg = (unsigned long long*)epa_scratch(ctx, 10, sizeof(unsigned long long) * (size_t)Q * segp);
+    if (!d_seg) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(segment maxima)");
+  }
   const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
   const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
   const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
@@ -1315,11 +1515,21 @@ extern "C" int epa_dev_preplace(epa_ctx* ctx, const uint8_t* q_codes, const uint
   const bool out_dev = epa_is_device_ptr(lnl);
   double* d_lnl = out_dev ? lnl : (double*)epa_scratch(ctx, 3, sizeof(double) * (size_t)Q * ctx->B);
   if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(lnl)");
-  rc = launch_preplace(ctx, d_codes, d_begin, d_span, Q, d_lnl, 0);
+  if (d_seg) {
+    ctx->segmax = d_seg;
+    ctx->segp = segp;
+    ctx->segmax_zero_bytes = sizeof(unsigned long long) * (size_t)Q * segp;
+  }
+  rc = launch_preplace(ctx, d_codes, d_begin, d_span, Q, d_lnl, max_span);
+  ctx->segmax = nullptr;
+  ctx->segmax_zero_bytes = 0;
   if (rc) return rc;
   if (!out_dev)
     EPA_HIP(ctx, hipMemcpyAsync(lnl, d_lnl, sizeof(double) * (size_t)Q * ctx->B,
                                 hipMemcpyDeviceToHost, ctx->stream));
+  if (d_seg)
+    EPA_HIP(ctx, hipMemcpyAsync(seg_keys, d_seg, sizeof(unsigned long long) * (size_t)Q * segp,
+                                epa_is_device_ptr(seg_keys) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
   EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return preplace_check_status(ctx);  // windows are validated on device (k_make_groups)
 }
@@ -2341,6 +2551,21 @@ extern "C" double epa_dev_last_sclk_mhz(const epa_ctx* ctx) { return ctx ? ctx->
 extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) {
   if (!ctx || !which) return -1.0;
   const EvTimer* t = nullptr;
+  if (!strcmp(which, "lookup_block") || (ctx->lookup_blocks && !strcmp(which, "preplace"))) {
+    // blocked layout: events e[0] build e[1] preplace e[2] build ... of the last chunk body on the bank
+    const int bank = ctx->t_last[epa_ctx::T_PREPLACE];
+    const uint32_t n = ctx->blk_ev_n[bank];
+    if (!ctx->lookup_blocks || n < 3) return -1.0;
+    const std::vector<hipEvent_t>& ev = ctx->blk_ev[bank];
+    if (hipEventSynchronize(ev[n - 1]) != hipSuccess) return -1.0;
+    double sum = 0.0;
+    for (uint32_t i = (which[0] == 'l' ? 0u : 1u); i + 1 < n; i += 2) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) return -1.0;
+      sum += (double)ms;
+    }
+    return sum;
+  }
   if (!strcmp(which, "preplace")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_PREPLACE]][epa_ctx::T_PREPLACE];
   else if (!strcmp(which, "thorough")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_THOROUGH]][epa_ctx::T_THOROUGH];
   else if (!strcmp(which, "lookup")) t = &ctx->t_lookup;

@@ -194,6 +194,11 @@ struct epa_ctx {
   double inv_w0 = 0.0;        // 1 / w_0: folds cinv into the zero-eigenvalue sumtable entry (thorough)
   double* lookup2 = nullptr;  // DNA only: [B][2][ceil(W/2)][36] site-pair sums (preplace.hip, k_preplace_pairs)
   bool lookup_built = false;
+  // Blocked lookup layout (EPA_FLAG_LOOKUP_BLOCKS): lookup / lookup2 / refI / resc0 stay null; every scratch bank that
+  // runs a preplacement owns one block buffer -- lookup [blk][W][ncols], then (4 states) lookup2 [blk][2][ceil(W/2)][36]
+  // -- rebuilt block by block inside launch_preplace (allocated exactly, on first use: epa_block_buffer)
+  bool lookup_blocks = false;
+  uint32_t lookup_block = 1024;   // branches per block, a multiple of 64
   std::vector<double> h_blen;
 
   // per-call scratch (grown on demand)
@@ -235,6 +240,11 @@ struct epa_ctx {
   // before slot k records its stop; t_last = the bank whose timer was stopped last
   enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2 };
   EvTimer t_lookup;
+  // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
+  std::vector<hipEvent_t> blk_ev[N_BANKS];
+  uint32_t blk_ev_n[N_BANKS] = {};
+  void* blk_buf[N_BANKS] = {};
+  size_t blk_sz[N_BANKS] = {};
   EvTimer t_bank[N_BANKS][3];
   // shares of the branch-sorted pair list the eight XCDs take in the single-wave Newton launches (cumulative, 20-bit
   // fixed point; thorough_dna.hip ThArgs::xcum), adapted to the speeds the XCDs showed: epa_xcd_feedback
@@ -313,6 +323,13 @@ int launch_transform(epa_ctx* ctx, const double* d_clv_or_null, const uint8_t* d
                      const uint32_t* d_tipmap, uint32_t tipmap_size, double* dst);
 int launch_build_lookup(epa_ctx* ctx);
 int launch_build_lookup2(epa_ctx* ctx);  // DNA site-pair table from `lookup` (preplace.hip)
+// blocked layout: branches per block buffer in effect, its bytes (lookup rows first, lookup2 rows at *off2), the
+// current bank's buffer (allocated on first use) and the build of the tables of branches [b0, b0 + nb) into it
+uint32_t epa_block_branches(const epa_ctx* ctx);
+size_t epa_block_bytes(int s, uint32_t W, uint32_t blk, size_t* off2);
+void* epa_block_buffer(epa_ctx* ctx);
+int launch_build_lookup_block(epa_ctx* ctx, uint32_t b0, uint32_t nb, double* blk_lookup);
+int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_lookup, double* blk_lookup2);
 int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin,
                     const uint32_t* d_span, uint32_t Q, double* d_lnl, uint32_t max_span);
 int preplace_check_status(epa_ctx* ctx);

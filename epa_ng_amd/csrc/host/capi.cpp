@@ -241,6 +241,11 @@ uint64_t epa_host_device_chunk_reads(uint64_t free_bytes, uint64_t branches, int
   return (uint64_t)epa::device_chunk_reads(free_bytes, (size_t)branches, slots, (size_t)wanted, (size_t)user_chunk);
 }
 
+uint64_t epa_host_device_chunk_reads_banks(uint64_t free_bytes, uint64_t branches, int slots, uint64_t wanted, uint64_t user_chunk,
+                                           uint64_t bank_bytes) {
+  return (uint64_t)epa::device_chunk_reads(free_bytes, (size_t)branches, slots, (size_t)wanted, (size_t)user_chunk, bank_bytes);
+}
+
 void epa_host_local_seq_package(uint64_t num_sequences, int rank, int world, uint64_t* offset, uint64_t* count) {
   const auto p = epa::local_seq_package((size_t)num_sequences, rank, world);
   *offset = p.first;

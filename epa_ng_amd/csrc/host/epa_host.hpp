@@ -60,6 +60,10 @@ struct Options {  // defaults: src/util/Options.hpp:13-34
   bool rate_scalers(size_t tips) const {
     return scaling == NumericalScaling::kOn || (scaling == NumericalScaling::kAuto && tips > 2000);
   }
+  // --memsave: layout of the device's derived per-branch tables (include/epa_dev.h, EPA_FLAG_LOOKUP_*; no reference
+  // counterpart).  auto = resident when the reference fits the device, rebuilt per branch block and chunk when not
+  enum class Memsave { kAuto, kOn, kOff };
+  Memsave memsave = Memsave::kAuto;
   // one-process-per-GPU mode (place_ranks.cpp; the reference's MPI build has no counterpart of these: mpirun is its launcher)
   std::string comm_nonce;            // --comm-nonce / EPA_COMM_NONCE / TORCHELASTIC_RUN_ID: marks this run's id record in --comm-file
   int comm_rows_per_read = 8;        // --comm-rows-per-read: rows per rank and gather = chunk x this (beyond it: the carry path)
@@ -384,7 +388,15 @@ public:
   std::vector<epa_result>& result_buffer() { return res_buf_; }
   uint64_t& pair_capacity() { return pair_cap_; }  // candidate capacity the chunk pipeline last needed
   double ref_tree_logl(size_t branch = 0) const;  // Tree::ref_tree_logl evaluated on the device
+  // lookup layout the context came out with (epa_dev_lookup_mode): blocks, branches per block (0: resident)
+  bool lookup_blocks() const;
+  uint32_t lookup_block() const;
+  // bytes of one block buffer (0: resident), and the resident layout's need against the bytes create could use
+  uint64_t bank_bytes() const { return bank_bytes_; }
+  uint64_t resident_bytes() const { return resident_bytes_; }
+  uint64_t usable_bytes() const { return usable_bytes_; }
 private:
+  uint64_t bank_bytes_ = 0, resident_bytes_ = 0, usable_bytes_ = 0;
   epa_ctx* ctx_ = nullptr;
   std::vector<epa_pair> pairs_buf_;
   std::vector<epa_result> res_buf_;
@@ -450,12 +462,19 @@ struct Run_Stats {
   // heuristics); and the reads per device chunk after the memory clamp (device_chunk_reads)
   std::string chunk_path;
   size_t device_chunk = 0;
+  // lookup layout of the device context(s): "resident" or "blocks", branches per block (0: resident)
+  std::string lookup_mode = "resident";
+  uint32_t lookup_block = 0;
 };
 // Reads per device chunk that fit a device: `slots` pipeline slots each own a preplacement table of
 // Q x pitch(branches) x 8 bytes (pitch: the row rounded up to 64 bytes), plus a quarter of that for codes, bitmap and
 // candidates, all within half of `free_bytes`.  `wanted` is returned unless that is too much; never 0.  user_chunk:
 // an explicit --chunk-size the result may not exceed (0: none) -- the clamp only ever lowers it.
 size_t device_chunk_reads(uint64_t free_bytes, size_t branches, int slots, size_t wanted, size_t user_chunk);
+// Blocked lookup layout: every slot's bank also owns a block buffer of bank_bytes, allocated with its first chunk;
+// the same clamp on what `slots` of them leave of free_bytes (bank_bytes 0 = the function above).
+size_t device_chunk_reads(uint64_t free_bytes, size_t branches, int slots, size_t wanted, size_t user_chunk,
+                          uint64_t bank_bytes);
 Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const std::string& outdir,
                      const Options& options, const std::string& invocation, int device = 0);
 // same, one worker thread per listed GPU; the jplace does not depend on the device count

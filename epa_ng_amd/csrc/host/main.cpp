@@ -33,6 +33,8 @@ static void usage() {
       "  --no-pre-mask         evaluate all sites of every query\n"
       "  --raxml-blo           radius-1 local branch-length optimisation instead of the sliding rule\n"
       "  --rate-scalers auto|on|off  per-rate-category numerical scaling (auto: on above 2000 tips)\n"
+      "  --memsave auto|on|off  device lookup tables rebuilt per branch block and chunk instead of resident: 3.1 x\n"
+      "                        (nucleotide) / 1.65 x (20 states) larger references fit (auto: only when they have to)\n"
       "  --preserve-rooting on|off  rooted reference tree: report on the rooted tree (default on)\n"
       "  -T,--threads N        upper limit on the host threads (parsing, encoding, LWR / filter, jplace text)\n"
       "  --device N            GPU ordinal (default 0)\n"
@@ -100,6 +102,13 @@ int main(int argc, char** argv) {
       else if (v == "on") opt.scaling = Options::NumericalScaling::kOn;
       else if (v == "off") opt.scaling = Options::NumericalScaling::kOff;
       else { std::cerr << "--rate-scalers: " << v << " not in {auto,on,off}\n"; return 1; }
+    }
+    else if (a == "--memsave") {
+      const std::string v = need(i);
+      if (v == "auto") opt.memsave = Options::Memsave::kAuto;
+      else if (v == "on") opt.memsave = Options::Memsave::kOn;
+      else if (v == "off") opt.memsave = Options::Memsave::kOff;
+      else { std::cerr << "--memsave: " << v << " not in {auto,on,off}\n"; return 1; }
     }
     else if (a == "--preserve-rooting") {  // src/main.cpp:196-199, 410-418
       const std::string v = need(i);
@@ -203,7 +212,8 @@ int main(int argc, char** argv) {
          << ", \"stage_wait_s\": " << st.seconds_stage_wait << ", \"device_calls_s\": " << st.seconds_place + st.seconds_thorough
          << ", \"build_sample_s\": " << st.seconds_sample << ", \"lwr_filter_s\": " << st.seconds_post
          << ", \"jplace_text_s\": " << st.seconds_text << ", \"write_s\": " << st.seconds_write
-         << ", \"chunk_path\": \"" << st.chunk_path << "\", \"device_chunk\": " << st.device_chunk << "}\n";
+         << ", \"chunk_path\": \"" << st.chunk_path << "\", \"device_chunk\": " << st.device_chunk
+         << ", \"lookup_mode\": \"" << st.lookup_mode << "\", \"lookup_block\": " << st.lookup_block << "}\n";
     }
   } catch (const std::exception& e) {
     std::cerr << e.what() << "\nAborting with a failure." << std::endl;

@@ -12,6 +12,7 @@
 #include <deque>
 #include <cstdio>
 #include <fstream>
+#include <iostream>
 #include <mutex>
 #include <thread>
 #include <limits>
@@ -67,7 +68,9 @@ const double kDefaultBranchLength = -std::log(0.9);
 Device_Evaluator::Device_Evaluator(const Tree& tree, const Options& options, int device) {
   const bool rs = options.rate_scalers(tree.nums().tip_nodes);
   const uint32_t flags = (options.sliding_blo ? EPA_FLAG_SLIDING_BLO : EPA_FLAG_RAXML_BLO) |
-                         (rs ? EPA_FLAG_RATE_SCALERS : 0u);
+                         (rs ? EPA_FLAG_RATE_SCALERS : 0u) |
+                         (options.memsave == Options::Memsave::kOn ? EPA_FLAG_LOOKUP_BLOCKS
+                          : options.memsave == Options::Memsave::kAuto ? EPA_FLAG_LOOKUP_AUTO : 0u);
   if (rs && !options.device_precompute)
     throw std::runtime_error{"per-rate scalers need the device-side reference precompute (the host CLV "
                              "path keeps per-site scalers): drop --host-precompute or pass --rate-scalers off"};
@@ -92,6 +95,29 @@ Device_Evaluator::Device_Evaluator(const Tree& tree, const Options& options, int
     rc = epa_dev_create(&d, device, &ctx_);
   }
   if (rc != EPA_OK) throw_dev(nullptr, rc);
+  if (lookup_blocks()) {   // what the blocked layout costs per bank, and what the resident one would have needed
+    const Model& m = tree.model();
+    const int fl = (int)(flags & ~(EPA_FLAG_LOOKUP_BLOCKS | EPA_FLAG_LOOKUP_AUTO));
+    epa_footprint f;
+    if (epa_dev_footprint((uint32_t)m.num_states(), (uint32_t)m.num_ratecats(), tree.num_sites(), tree.num_branches(),
+                          fl | (int)EPA_FLAG_LOOKUP_BLOCKS, options.device_precompute ? 1 : 0, lookup_block(), 1, &f) == EPA_OK)
+      bank_bytes_ = f.bank;
+    if (epa_dev_footprint((uint32_t)m.num_states(), (uint32_t)m.num_ratecats(), tree.num_sites(), tree.num_branches(), fl,
+                          options.device_precompute ? 1 : 0, 0, 0, &f) == EPA_OK)
+      resident_bytes_ = f.peak;
+    uint64_t fr = 0, tot = 0;
+    if (epa_dev_mem_info(ctx_, &fr, &tot) == EPA_OK) usable_bytes_ = fr;
+  }
+}
+
+bool Device_Evaluator::lookup_blocks() const {
+  int mode = EPA_LOOKUP_RESIDENT;
+  return epa_dev_lookup_mode(ctx_, &mode, nullptr) == EPA_OK && mode == EPA_LOOKUP_BLOCKS;
+}
+uint32_t Device_Evaluator::lookup_block() const {
+  uint32_t blk = 0;
+  (void)epa_dev_lookup_mode(ctx_, nullptr, &blk);
+  return blk;
 }
 
 double Device_Evaluator::ref_tree_logl(size_t branch) const {
@@ -503,6 +529,13 @@ size_t device_chunk_reads(uint64_t free_bytes, size_t branches, int slots, size_
   return (size_t)std::max<uint64_t>(reads, 1);
 }
 
+size_t device_chunk_reads(uint64_t free_bytes, size_t branches, int slots, size_t wanted, size_t user_chunk,
+                          uint64_t bank_bytes) {
+  const uint64_t banks = bank_bytes * (uint64_t)std::max(1, slots);
+  return device_chunk_reads(bank_bytes ? (free_bytes > banks ? free_bytes - banks : 0) : free_bytes, branches, slots,
+                            wanted, user_chunk);
+}
+
 Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const std::string& outdir,
                      const Options& options, const std::string& invocation, int device) {
   return simple_mpi(tree, query_file, outdir, options, invocation, std::vector<int>{device});
@@ -532,6 +565,15 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
   for (int d : devices) devs.emplace_back(new Device_Evaluator(tree, options, d));
   st.ref_tree_logl = devs[0]->ref_tree_logl(0);
   st.seconds_setup = std::chrono::duration<double>(clk::now() - ts).count();
+  for (auto& d : devs)
+    if (d->lookup_blocks()) {
+      if (st.lookup_block == 0)
+        std::cout << "Memory-saving mode: lookup tables in blocks of " << d->lookup_block() << " branches, rebuilt per chunk ("
+                  << d->resident_bytes() << " bytes needed resident, " << d->usable_bytes() << " bytes free with the reference loaded)"
+                  << std::endl;
+      st.lookup_mode = "blocks";
+      st.lookup_block = d->lookup_block();
+    }
   const auto t_loop = clk::now();
 
   struct Staged { size_t index = 0, offset = 0; MSA chunk; Encoded_Chunk enc; };
@@ -588,7 +630,8 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
     uint64_t fr = 0, tot = 0;
     if (epa_dev_mem_info(d->ctx(), &fr, &tot) != EPA_OK) continue;
     device_chunk = device_chunk_reads(fr, tree.num_branches(), kSlots, device_chunk,
-                                      options.chunk_size_given && !options.device_min_chunk_given ? options.chunk_size : 0);
+                                      options.chunk_size_given && !options.device_min_chunk_given ? options.chunk_size : 0,
+                                      d->bank_bytes());
   }
   st.device_chunk = device_chunk;
   // Post-processing pool.  The reference hands a finished chunk to an asynchronous writer (src/io/jplace_writer.hpp:58-69);

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <exception>
 #include <fstream>
+#include <iostream>
 #include <thread>
 #include <unordered_map>
 
@@ -144,6 +145,14 @@ Run_Stats simple_mpi_ranks(const Tree& tree, const std::string& query_file, cons
   if (no_heur) per_chunk = std::max<size_t>(1, std::min<size_t>(per_chunk, 0xffffffffull / std::max<size_t>(1, tree.num_branches())));   // B x Q pairs per call < 2^32
   st.chunk_path = no_heur ? "place_all" : "fused";
   st.device_chunk = per_chunk;
+  if (dev.lookup_blocks()) {
+    st.lookup_mode = "blocks";
+    st.lookup_block = dev.lookup_block();
+    if (rank == 0)
+      std::cout << "Memory-saving mode: lookup tables in blocks of " << dev.lookup_block() << " branches, rebuilt per chunk ("
+                << dev.resident_bytes() << " bytes needed resident, " << dev.usable_bytes() << " bytes free with the reference loaded)"
+                << std::endl;
+  }
   const size_t part = (total + (size_t)world - 1) / (size_t)world;
   const size_t nchunks = (part + per_chunk - 1) / per_chunk;   // the SAME on every rank: posts are collective
   // rows per rank and gather: candidates per read average 2 .. 3 under the default heuristic; beyond that

@@ -1877,12 +1877,22 @@ int launch_build_lookup2(epa_ctx* ctx) {
   return EPA_OK;
 }
 
+// blocked layout: the site-pair rows of a block from its lookup rows (both relative to the block buffer)
+int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_lookup, double* blk_lookup2) {
+  for (uint32_t r0 = 0; r0 < nb; r0 += EPA_GRID_Y)
+    hipLaunchKernelGGL(k_build_lookup2, dim3((ctx->W * PE + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, nb - r0)), dim3(256), 0,
+                       ctx->stream, blk_lookup, ctx->W, blk_lookup2, r0);
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}
+
 int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin,
                     const uint32_t* d_span, uint32_t Q, double* d_lnl, uint32_t max_span) {
   const uint32_t pitch = ctx->lnl_pitch ? ctx->lnl_pitch : ctx->B;  // row pitch of d_lnl in doubles
   unsigned long long* const segmax = ctx->segmax;   // per-(query, 64-branch segment) maxima wanted by the fused chunk body, or null
   const uint32_t segp = ctx->segp;
-  const bool pairs = ctx->s == 4 && ctx->lookup2 && !ctx->opt.preplace_generic;
+  const bool blocked = ctx->lookup_blocks;
+  const bool pairs = ctx->s == 4 && (ctx->lookup2 || blocked) && !ctx->opt.preplace_generic;
   const bool sites = ctx->s == 20 && ctx->ncols == 24 && !ctx->opt.preplace_generic;
   const uint32_t crel = ctx->code_stride ? 1u : 0u, cstride = crel ? ctx->code_stride : ctx->W;
   const uint32_t n_buckets = (ctx->W + SPREAD - 1) / SPREAD;
@@ -1957,65 +1967,106 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
                      sizeof(uint32_t) * (2 * (n_blocks + 1) + 4 * (size_t)max_runs + 2), ctx->stream,
                      sorted_keys, Q, pairs ? Wp : 0xffffffffu, n_blocks, class_blocks, gq0, gq1,
                      (uint32_t)(wide ? SPREAD_WIDE : SPREAD), max_runs, groups, max_groups, status);
-  // persistent grids: every resident workgroup slot of the device, work items strided over them
-  const uint32_t ntiles = (ctx->B + NB - 1) / NB;
   // max_span: upper bound of the window spans when the caller knows it (0 = unknown) -> acc, above
-  const size_t lds = sizeof(double) * ((size_t)TROWS * ctx->ncols + (acc ? (size_t)NB * GQ : 0));
-  const size_t lds2 = (size_t)TROWS2 * rowl + sizeof(double) * (acc ? NB2_ACC * GQ2 : NB2_BURST * (GQ2 + 4));  // accs / result staging
-  const uint32_t ntiles2 = (ctx->B + (acc ? NB2_ACC : 16) - 1) / (acc ? NB2_ACC : 16);   // single chunk: choose_tile, >= 16
-  const dim3 grid2((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ntiles2, (uint64_t)ctx->n_cu));  // 1 per CU
-  // generic kernel: with the pair path on it only sees the few groups of queries with rare
-  // ambiguity codes -> persistent grid; as the only kernel (20 states) one workgroup per item,
-  // dispatched dynamically (items differ in cost, partial groups are cheaper)
-  const dim3 grid(pairs ? (uint32_t)std::min<uint64_t>((uint64_t)max_groups * ntiles, (uint64_t)ctx->n_cu * (acc ? 2 : 4))
-                        : max_groups * ntiles);
   const size_t codes_bytes = (size_t)Q * cstride;
   const uint32_t want_cls = pairs ? 1u : 0u;
-  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
-#define PRE2(A, SP, RL, LDSB)                                                                        \
-  do {                                                                                               \
-    EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_preplace_pairs<A, SP, RL>,                       \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSB)));      \
-    hipLaunchKernelGGL((k_preplace_pairs<A, SP, RL>), grid2, dim3(GQ2), (uint32_t)(LDSB), ctx->stream, ctx->lookup2, (const uint16_t*)packed, \
-                       (const uint16_t*)tails, d_begin, d_span, perm, groups, ctx->W, ctx->B, pitch, NP16, status, d_lnl, (A) ? nullptr : segmax, segp);    \
-  } while (0)
-  if (pairs && wide) {
-    const size_t lds2w = (size_t)((CH + SPREAD_WIDE) / 2) * ROWL_PACKED + sizeof(double) * NB2_BURST * (GQ2 + 4);
-    PRE2(false, SPREAD_WIDE, ROWL_PACKED, lds2w);
-  } else if (pairs) {
-    if (acc) PRE2(true, SPREAD, ROWL_PACKED, lds2);
-    else PRE2(false, SPREAD, ROWL_NARROW, lds2);
-  }
-#undef PRE2
+  // LDS sizes and the kernels' dynamic-LDS attribute: once per call, whatever the number of blocks
+  const size_t lds = sizeof(double) * ((size_t)TROWS * ctx->ncols + (acc ? (size_t)NB * GQ : 0));
+  const size_t lds2 = wide ? (size_t)((CH + SPREAD_WIDE) / 2) * ROWL_PACKED + sizeof(double) * NB2_BURST * (GQ2 + 4)
+                           : (size_t)TROWS2 * rowl + sizeof(double) * (acc ? NB2_ACC * GQ2 : NB2_BURST * (GQ2 + 4));  // accs / result staging
+  const bool acc_s = max_span == 0 || max_span > (uint32_t)CHS;
+  const size_t lds_s = (size_t)TROWS_S * 24 * 8 + sizeof(double) * (acc_s ? NB2_ACC_S * GQ2 : NB2_BURST * (GQ2 + 4));  // accs / result staging
+#define PP_LDS_ATTR(K, BYTES) EPA_HIP(ctx, hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
+  if (pairs && wide) PP_LDS_ATTR((k_preplace_pairs<false, SPREAD_WIDE, ROWL_PACKED>), lds2);
+  else if (pairs && acc) PP_LDS_ATTR((k_preplace_pairs<true, SPREAD, ROWL_PACKED>), lds2);
+  else if (pairs) PP_LDS_ATTR((k_preplace_pairs<false, SPREAD, ROWL_NARROW>), lds2);
   if (sites) {
-    const bool acc_s = max_span == 0 || max_span > (uint32_t)CHS;
-    const size_t lds_s = (size_t)TROWS_S * 24 * 8 + sizeof(double) * (acc_s ? NB2_ACC_S * GQ2 : NB2_BURST * (GQ2 + 4));  // accs / result staging
-    const uint32_t ntiles_s = (ctx->B + (acc_s ? NB2_ACC_S : 16) - 1) / (acc_s ? NB2_ACC_S : 16);
-    const dim3 grid_s((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ntiles_s, (uint64_t)ctx->n_cu));
-#define PRES(A)                                                                                      \
-  do {                                                                                               \
-    EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_preplace_sites<24, A>,                           \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));       \
-    hipLaunchKernelGGL((k_preplace_sites<24, A>), grid_s, dim3(GQ2), (uint32_t)lds_s, ctx->stream, ctx->lookup, \
-                       packed, tails, d_begin, d_span, perm, groups, ctx->W, ctx->B, pitch, NP16, status, d_lnl, (A) ? nullptr : segmax, segp); \
-  } while (0)
-    if (acc_s) PRES(true); else PRES(false);
+    if (acc_s) PP_LDS_ATTR((k_preplace_sites<24, true>), lds_s); else PP_LDS_ATTR((k_preplace_sites<24, false>), lds_s);
+  } else if (ctx->ncols == 16) {
+    if (acc) PP_LDS_ATTR((k_preplace<16, true>), lds); else PP_LDS_ATTR((k_preplace<16, false>), lds);
+  } else {
+    if (acc) PP_LDS_ATTR((k_preplace<24, true>), lds); else PP_LDS_ATTR((k_preplace<24, false>), lds);
+  }
+#undef PP_LDS_ATTR
+#define PRE2(A, SP, RL)                                                                                               \
+  hipLaunchKernelGGL((k_preplace_pairs<A, SP, RL>), grid2, dim3(GQ2), (uint32_t)lds2, ctx->stream, lk2, (const uint16_t*)packed, \
+                     (const uint16_t*)tails, d_begin, d_span, perm, groups, ctx->W, nB, pitch, NP16, status, lnl, (A) ? nullptr : sm, segp)
+#define PRES(A)                                                                                                       \
+  hipLaunchKernelGGL((k_preplace_sites<24, A>), grid_s, dim3(GQ2), (uint32_t)lds_s, ctx->stream, lk, packed, tails, d_begin, \
+                     d_span, perm, groups, ctx->W, nB, pitch, NP16, status, lnl, (A) ? nullptr : sm, segp)
+#define PRE(NC, A)                                                                                                    \
+  hipLaunchKernelGGL((k_preplace<NC, A>), grid, dim3(GQ), (uint32_t)lds, ctx->stream, lk, d_codes, d_begin, d_span, perm, \
+                     groups, ctx->W, cstride, crel, nB, pitch, codes_bytes, want_cls, status, lnl)
+  // The preplacement kernels over nB branches whose tables start at lk / lk2 (the resident tables, or a block
+  // buffer), table rows at lnl, segment maxima at sm: the whole tree at once, or one block of it.  Which workgroup sums
+  // which (query, branch) cell follows nB (choose_tile, ntiles); a cell's summation order does not.
+  auto kernels = [&](const double* lk, const double* lk2, uint32_t nB, double* lnl, unsigned long long* sm) {
+    // persistent grids: every resident workgroup slot of the device, work items strided over them
+    const uint32_t ntiles = (nB + NB - 1) / NB;
+    const uint32_t ntiles2 = (nB + (acc ? NB2_ACC : 16) - 1) / (acc ? NB2_ACC : 16);   // single chunk: choose_tile, >= 16
+    const dim3 grid2((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ntiles2, (uint64_t)ctx->n_cu));  // 1 per CU
+    // generic kernel: with the pair path on it only sees the few groups of queries with rare
+    // ambiguity codes -> persistent grid; as the only kernel (20 states) one workgroup per item,
+    // dispatched dynamically (items differ in cost, partial groups are cheaper)
+    const dim3 grid(pairs ? (uint32_t)std::min<uint64_t>((uint64_t)max_groups * ntiles, (uint64_t)ctx->n_cu * (acc ? 2 : 4))
+                          : max_groups * ntiles);
+    if (pairs && wide) PRE2(false, SPREAD_WIDE, ROWL_PACKED);
+    else if (pairs && acc) PRE2(true, SPREAD, ROWL_PACKED);
+    else if (pairs) PRE2(false, SPREAD, ROWL_NARROW);
+    if (sites) {
+      const uint32_t ntiles_s = (nB + (acc_s ? NB2_ACC_S : 16) - 1) / (acc_s ? NB2_ACC_S : 16);
+      const dim3 grid_s((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ntiles_s, (uint64_t)ctx->n_cu));
+      if (acc_s) PRES(true); else PRES(false);
+      return;
+    }
+    if (ctx->ncols == 16) { if (acc) PRE(16, true); else PRE(16, false); }
+    else { if (acc) PRE(24, true); else PRE(24, false); }
+  };
+#undef PRE2
 #undef PRES
+#undef PRE
+  if (!blocked) {
+    epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
+    kernels(ctx->lookup, ctx->lookup2, ctx->B, d_lnl, segmax);
     epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
     EPA_HIP(ctx, hipGetLastError());
     return EPA_OK;
   }
-#define PRE(NC, A)                                                                                  \
-  do {                                                                                              \
-    EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_preplace<NC, A>,                                \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-    hipLaunchKernelGGL((k_preplace<NC, A>), grid, dim3(GQ), (uint32_t)lds, ctx->stream, ctx->lookup, d_codes, \
-                       d_begin, d_span, perm, groups, ctx->W, cstride, crel, ctx->B, pitch, codes_bytes, want_cls, status, d_lnl); \
-  } while (0)
-  if (ctx->ncols == 16) { if (acc) PRE(16, true); else PRE(16, false); }
-  else { if (acc) PRE(24, true); else PRE(24, false); }
-#undef PRE
-  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
+  // Blocked lookup layout: the prologue above ran once (its status words are only read from here on, so a window
+  // error shows whatever the number of blocks); now, block by block on this bank's stream, the tables of the block are
+  // built into the bank's buffer, consumed by the same preplacement kernels, and overwritten by the next block.
+  // Blocks start at multiples of 64 branches: segment maxima and 64-byte result bursts keep their alignment.
+  const uint32_t blk = epa_block_branches(ctx);
+  size_t off2 = 0;
+  (void)epa_block_bytes(ctx->s, ctx->W, blk, &off2);
+  char* buf = (char*)epa_block_buffer(ctx);
+  if (!buf) return epa_fail(ctx, EPA_ERR_NO_MEMORY, "hipMalloc(lookup block buffer): " + std::to_string(epa_block_bytes(ctx->s, ctx->W, blk, nullptr)) +
+                                                    " bytes needed for blocks of " + std::to_string(blk) + " branches (option lookup_block)");
+  double* blk_lookup = reinterpret_cast<double*>(buf);
+  double* blk_lookup2 = ctx->s == 4 ? reinterpret_cast<double*>(buf + off2) : nullptr;
+  const uint32_t nblocks = (ctx->B + blk - 1) / blk;
+  // events e[0] build e[1] kernels e[2] build ...: "lookup_block" and "preplace" of epa_dev_last_kernel_ms
+  std::vector<hipEvent_t>& ev = ctx->blk_ev[ctx->bank];
+  const bool timed = ctx->opt.timers != 0;
+  ctx->blk_ev_n[ctx->bank] = 0;
+  (void)epa_t(ctx, epa_ctx::T_PREPLACE);   // the bank of the last preplacement
+  auto mark = [&](uint32_t i) -> int {
+    if (!timed) return EPA_OK;
+    while (ev.size() <= i) { hipEvent_t e = nullptr; EPA_HIP(ctx, hipEventCreate(&e)); ev.push_back(e); }
+    EPA_HIP(ctx, hipEventRecord(ev[i], ctx->stream));
+    return EPA_OK;
+  };
+  for (uint32_t k = 0; k < nblocks; ++k) {
+    const uint32_t b0 = k * blk, nB = std::min(blk, ctx->B - b0);
+    int rc = mark(2 * k);
+    if (!rc) rc = launch_build_lookup_block(ctx, b0, nB, blk_lookup);
+    if (!rc && pairs) rc = launch_build_lookup2_block(ctx, nB, blk_lookup, blk_lookup2);
+    if (!rc) rc = mark(2 * k + 1);
+    if (rc) return rc;
+    kernels(blk_lookup, blk_lookup2, nB, d_lnl + b0, segmax ? segmax + (b0 >> 6) : nullptr);
+  }
+  { const int rc = mark(2 * nblocks); if (rc) return rc; }
+  if (timed) ctx->blk_ev_n[ctx->bank] = 2 * nblocks + 1;
   EPA_HIP(ctx, hipGetLastError());
   return EPA_OK;
 }

@@ -66,6 +66,8 @@ def host_lib():
                                          u32p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.epa_host_device_chunk_reads.restype = C.c_uint64
         L.epa_host_device_chunk_reads.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64]
+        L.epa_host_device_chunk_reads_banks.restype = C.c_uint64
+        L.epa_host_device_chunk_reads_banks.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64]
         _LIB = L
     return _LIB
 
@@ -197,16 +199,17 @@ class Reference:
                 "dist_scaler": view(p[4], C.c_uint32, (self.W,)), "length": ln.value}
 
     def evaluator(self, device=0, aa_x_as_n=False, device_precompute=True, rate_scalers=False,
-                  raxml_blo=False, newton_variant=0, blo_min_branch=0.0, keep_eigenvalues=False):
+                  raxml_blo=False, newton_variant=0, blo_min_branch=0.0, keep_eigenvalues=False, flags=0):
         """reference -> GPU -> api.Evaluator (epa_ctx created by the C++ host).  By default the
         tree and the tip sequences are sent and all directional CLVs are computed on the device;
         device_precompute=False uploads the host-computed CLVs instead.  rate_scalers: per-rate
         numerical scaling (EPA_FLAG_RATE_SCALERS); raxml_blo: --raxml-blo (EPA_FLAG_RAXML_BLO);
         newton_variant: bit 0 EPA_FLAG_NEWTON_SLOW_BISECT, bit 1 EPA_FLAG_NEWTON_STRICT_DF;
         blo_min_branch: PLLMOD_OPT_MIN_BRANCH_LEN (0 = default 1e-4); keep_eigenvalues:
-        EPA_FLAG_KEEP_EIGENVALUES (the stationary eigenvalue is not snapped to 0)."""
+        EPA_FLAG_KEEP_EIGENVALUES (the stationary eigenvalue is not snapped to 0); flags: further EPA_FLAG_*
+        bits, e.g. api.FLAG_LOOKUP_BLOCKS / api.FLAG_LOOKUP_AUTO (lookup tables per branch block and chunk)."""
         h = C.c_void_p()
-        flags = ((0x2 if rate_scalers else 0) | (0x4 if raxml_blo else 0) | (0x8 if newton_variant & 1 else 0) |
+        flags = int(flags) | ((0x2 if rate_scalers else 0) | (0x4 if raxml_blo else 0) | (0x8 if newton_variant & 1 else 0) |
                  (0x10 if newton_variant & 2 else 0) | (0x20 if keep_eigenvalues else 0))
         rc = host_lib().epa_host_dev_create_opts(self.h, device, int(aa_x_as_n), int(device_precompute),
                                                  flags, float(blo_min_branch), C.byref(h))
@@ -228,10 +231,14 @@ class Reference:
         return nq.value, npairs.value
 
 
-def device_chunk_reads(free_bytes, branches, slots, wanted, user_chunk=0):
+def device_chunk_reads(free_bytes, branches, slots, wanted, user_chunk=0, bank_bytes=0):
     """reads per device chunk of the CLI's chunk loop after its memory clamp: `slots` preplacement tables of
     Q x pitch(branches) x 8 bytes plus a quarter fit half of `free_bytes`; at least 1; never above an explicit
-    --chunk-size (user_chunk, 0 = none)"""
+    --chunk-size (user_chunk, 0 = none).  bank_bytes: blocked lookup layout, every slot also owns a block buffer
+    of that many bytes (api.footprint(...)["bank"])"""
+    if bank_bytes:
+        return int(host_lib().epa_host_device_chunk_reads_banks(int(free_bytes), int(branches), int(slots), int(wanted),
+                                                                int(user_chunk), int(bank_bytes)))
     return int(host_lib().epa_host_device_chunk_reads(int(free_bytes), int(branches), int(slots), int(wanted),
                                                       int(user_chunk)))
 

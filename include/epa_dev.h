@@ -45,8 +45,10 @@ typedef enum {
                                *   reference does not validate; this library does on ingest)   */
   EPA_ERR_NEG_INF = -7,       /* "-INF logl at branch ..." Tiny_Tree.cpp:209-212               */
   EPA_ERR_UNSUPPORTED = -8,   /* feature marked "next" in SURVEY.md section 8f                 */
-  EPA_ERR_PAIR_OVERFLOW = -9  /* the candidate selection found more pairs than max_pairs: call    *
+  EPA_ERR_PAIR_OVERFLOW = -9, /* the candidate selection found more pairs than max_pairs: call    *
                                *   again with larger buffers (a staged chunk stays staged)       */
+  EPA_ERR_NO_MEMORY = -10     /* the reference does not fit the device (or the cap of            *
+                               *   epa_dev_set_mem_cap): the message names needed and usable bytes */
 } epa_status;
 
 /* flags of epa_ref_desc.flags */
@@ -71,6 +73,19 @@ typedef enum {
                                     * above 2000 tips, src/io/file_io.cpp:211-214, or with            *
                                     * --rate-scalers).  prox_scaler / dist_scaler rows are then      *
                                     * [W][rate_cats] (libpll layout)                                  */
+
+/* Layout of the derived per-branch tables (lookup, lookup2, refI / resc0).  Neither bit: all of
+ * them resident, [B]-sized, built once (805 B per branch x site for a 4-state, 4-category reference, 2117 B for 20
+ * states).  EPA_FLAG_LOOKUP_BLOCKS: only refT / scSum stay resident (260 / 1284 B); every scratch bank that runs a
+ * preplacement owns ONE block buffer of `lookup_block` branches, whose tables are rebuilt block by block inside every
+ * chunk body, and the Newton kernels compute their own starting vectors.  Preplacement tables and candidate lists are the
+ * same bits either way; the Newton results are not: a kernel that forms its starting vector itself rounds differently
+ * from the lookup build that stores it -- measured, lnL within 3.4e-12 and lengths within 2.5e-14 of the resident layout
+ * (a few ulp; both within the 1e-6 the tests hold against the oracle).
+ * EPA_FLAG_LOOKUP_AUTO: resident when epa_dev_lookup_plan() says it fits the device's free memory (or the cap of
+ * epa_dev_set_mem_cap), blocks otherwise. */
+#define EPA_FLAG_LOOKUP_BLOCKS 0x40u
+#define EPA_FLAG_LOOKUP_AUTO 0x80u
 
 /*
  * Reference-side inputs: what Tiny_Tree's constructor pulls out of `Tree` per branch
@@ -216,6 +231,9 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
  *   "xcd_balance"       0: the eight XCDs keep equal shares of a Newton launch (default 1: epa_dev_xcd_shares)
  *   "aa_valu"           1: 20-state windows on the lane = site VALU kernel instead of the matrix-core kernel
  *   "timers"            0: no hipEvent records around the kernel families (epa_dev_last_kernel_ms returns < 0)
+ *   "lookup_block"      n: branches per block buffer of a context in the blocked lookup layout (default 1024, or what
+ *                          epa_dev_lookup_plan shrank it to); a positive multiple of 64, before the first preplacement.
+ *                          EPA_ERR_INVALID_ARG on a resident context
  *   "newton_lds"        1: the single-wave 4-state Newton kernels (windows up to 256 sites, exact zero eigenvalue,
  *                          sliding BLO) read their per-evaluation table through LDS instead of broadcasting it from registers
  *                          by DPP (default 0: DPP; bit-identical results)
@@ -224,8 +242,49 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
 int epa_dev_set_option(epa_ctx* ctx, const char* key, int value);
 
 /* Builds T[b][site][col] for all branches (idempotent).  Replaces precompute_sites_static x C
- * + Lookup_Store::init_branch (Tiny_Tree.cpp:18-46,114-128). */
+ * + Lookup_Store::init_branch (Tiny_Tree.cpp:18-46,114-128).  A context in the blocked lookup layout
+ * builds its tables inside the chunk body: the call does nothing there and returns EPA_OK. */
 int epa_dev_build_lookup(epa_ctx* ctx);
+
+/*
+ * Device memory of a reference, computed on the host (no device needed) with create's own padding rules:
+ * nucleotide categories padded to a multiple of four, 1 or 2 categories replicated to four, lookup2 over
+ * ceil(W / 2) site pairs.  flags: the EPA_FLAG_* the context would be created with (the lookup bits choose the
+ * layout that is priced: EPA_FLAG_LOOKUP_BLOCKS = blocks, anything else = resident); from_tree: priced for
+ * epa_dev_create_from_tree, whose per-side scaler counts and tip rows live until create returns;
+ * block_branches: branches per block buffer (0 = the default 1024; at most B rounded up to 64 are allocated);
+ * banks: scratch banks that will run a preplacement (the direct entry points are one, every pipeline slot in
+ * use another).  refi is counted for the shapes the tuned Newton kernels serve (a proper GTR is assumed).
+ */
+typedef struct {
+  uint64_t reft;          /* both CLVs of every branch in the eigenbasis                                  */
+  uint64_t scsum;         /* per-site scaler counts                                                       */
+  uint64_t lookup;        /* resident layout only: lookup [B][W][16 or 24]                                */
+  uint64_t lookup2;       /* resident layout, 4 states only: lookup2 [B][2][ceil(W/2)][36]                */
+  uint64_t refi;          /* resident layout, tuned Newton kernels only: refI + resc0                     */
+  uint64_t misc;          /* branch lengths, model block, work counters                                   */
+  uint64_t create_temp;   /* from_tree: buffers of the precompute, released before create returns         */
+  uint64_t reference;     /* reft + scsum + lookup + lookup2 + refi + misc                                */
+  uint64_t bank;          /* blocked layout: one block buffer (lookup + lookup2 rows of a block)          */
+  uint64_t steady;        /* reference + banks x bank                                                     */
+  uint64_t peak;          /* max(steady, reference + create_temp)                                         */
+} epa_footprint;
+int epa_dev_footprint(uint32_t states, uint32_t rate_cats, uint64_t sites, uint64_t branches, int flags, int from_tree,
+                      uint32_t block_branches, int banks, epa_footprint* out);
+
+/* Chooses the layout for `usable_bytes`: *mode = EPA_LOOKUP_RESIDENT when the resident peak fits (and flags do not
+ * force blocks); else EPA_LOOKUP_BLOCKS with the largest *block_branches <= 1024 (a multiple of 64, at least 64)
+ * whose peak fits; else EPA_ERR_NO_MEMORY (epa_dev_last_error(NULL) names needed and usable bytes).
+ * Non-decreasing in usable_bytes. */
+#define EPA_LOOKUP_RESIDENT 0
+#define EPA_LOOKUP_BLOCKS 1
+int epa_dev_lookup_plan(uint64_t usable_bytes, uint32_t states, uint32_t rate_cats, uint64_t sites, uint64_t branches,
+                        int flags, int from_tree, int banks, int* mode, uint32_t* block_branches);
+/* Process-wide bound of what epa_dev_create* may plan with, in place of the device's free memory (0 = none).  It
+ * bounds the plan's decision under EPA_FLAG_LOOKUP_AUTO / _BLOCKS, not hipMalloc: for shared devices and tests. */
+void epa_dev_set_mem_cap(uint64_t bytes);
+/* What a context uses: *mode = EPA_LOOKUP_*, *block_branches = branches per block buffer (0 when resident). */
+int epa_dev_lookup_mode(const epa_ctx* ctx, int* mode, uint32_t* block_branches);
 
 /*
  * Query encoding (one byte per site, Q x W row-major): the lookup-column index of the
@@ -282,6 +341,15 @@ int epa_dev_set_query_packing(epa_ctx* ctx, int bits);
  */
 int epa_dev_preplace(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
                      const uint32_t* win_span, uint32_t Q, double* lnl);
+
+/* epa_dev_preplace with what the fused chunk body adds to it.  max_span: an upper bound of win_span[] (0 = unknown, as
+ * epa_dev_preplace; a longer window is EPA_ERR_INVALID_ARG when win_span is a host array) -- with a bound of at most
+ * 160 sites (4 states) / 128 (20 states) the single-chunk kernels run, as in epa_dev_place_chunk.  seg_keys: NULL, or
+ * (up to 4096 branches) [Q][pitch] with pitch = ceil(B / 64) rounded up to 8: the per-(query, 64-branch segment) maxima
+ * of the table those kernels leave for the candidate selection, as order-preserving keys (a double's bits, negative:
+ * inverted, else the sign bit set), 0 = not written (query served by another kernel, or max_span not bounded). */
+int epa_dev_preplace_bounded(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
+                             const uint32_t* win_span, uint32_t Q, uint32_t max_span, double* lnl, uint64_t* seg_keys);
 
 /*
  * Replaces place_thorough() (src/core/place.cpp:97-171) = Tiny_Tree::place with opt_branches
@@ -529,7 +597,9 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select"); < 0 if never run. */
+ * measured with HIP events ("preplace", "thorough", "lookup", "select"); < 0 if never run.
+ * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
+ * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
 
 #ifdef __cplusplus
