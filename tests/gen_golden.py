@@ -154,7 +154,7 @@ def numbered_newick(root, prec):
 
 # ---------------------------------------------------------------- model
 class Model:
-    def __init__(self, s, subst, freqs, alpha, cats=4, rates=None, pinv=0.0):
+    def __init__(self, s, subst, freqs, alpha, cats=4, rates=None, pinv=0.0, weights=None):
         self.s = s
         self.pinv = pinv          # +I: rates / (1 - p) in P(t); site lk = (1-p) L + p pi_inv
         self.cinv = None          # [W] p * pi_inv per site (set by make_case from the reference tips)
@@ -174,7 +174,10 @@ class Model:
             cuts = [0.0] + [g.ppf(i / cats) for i in range(1, cats)] + [np.inf]
             rates = [cats * (g1.cdf(cuts[i + 1]) - g1.cdf(cuts[i])) for i in range(cats)]
         self.rates = np.asarray(rates, float)
-        self.weights = np.full(len(self.rates), 1.0 / len(self.rates))
+        if weights is None:       # equal weights: +G; anything else: free rates (+R)
+            weights = np.full(len(self.rates), 1.0 / len(self.rates))
+        self.weights = np.asarray(weights, float)
+        assert self.weights.shape == self.rates.shape
 
     def P(self, t):
         return np.stack([expm(self.Q * (r * t / (1.0 - self.pinv))) for r in self.rates])  # [c][i][j]
