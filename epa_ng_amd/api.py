@@ -112,6 +112,8 @@ def dev_lib():
                                                C.c_void_p, C.c_void_p]
         L.epa_dev_thorough.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(_Stats)]
+        L.epa_dev_score_at.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.epa_dev_set_heuristic.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.epa_dev_set_query_packing.argtypes = [C.c_void_p, C.c_int]
         L.epa_pack_codes_4bit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -422,6 +424,20 @@ class Evaluator:
                                             _ptr(win_span), Q, _ptr(out), C.byref(st)))
         self.last_stats = {"pairs": st.pairs, "rounds": st.rounds,
                            "newton_evals": st.newton_evals, "reverts": st.reverts}
+        return out
+
+    def score_at(self, pairs, pendant, distal, codes, win_begin, win_span, proximal=None, Q=None, out=None):
+        """lnL of the placements `pairs` (PAIR_DTYPE) at the GIVEN lengths, no optimiser (epa_dev_score_at) -> float64
+        [n].  proximal None: branch length - distal.  Host arrays are converted to float64; device buffers pass as is."""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
+        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        if out is None:
+            out = np.empty(n, np.float64)
+        self._layout(codes)
+        self._check(self.L.epa_dev_score_at(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                            _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(out)))
         return out
 
     def set_heuristic(self, mode="dynamic", param=0.0):

@@ -1466,10 +1466,10 @@ static const uint32_t* host_view(const uint32_t* p, size_t n, std::vector<uint32
 }
 
 static int check_windows(epa_ctx* ctx, const uint32_t* hb, const uint32_t* hs, uint32_t Q,
-                         uint32_t* max_span) {
+                         uint32_t* max_span, bool allow_empty = false) {
   uint32_t mx = 0;
   for (uint32_t q = 0; q < Q; ++q) {
-    if (hs[q] == 0)
+    if (hs[q] == 0 && !allow_empty)
       return epa_fail(ctx, EPA_ERR_QUERY_ALL_GAP,
                       "Sequence " + std::to_string(q) + " does not appear to have any non-gap sites!");
     if ((uint64_t)hb[q] + hs[q] > ctx->W)
@@ -1591,6 +1591,55 @@ extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_
                       "-INF logl at branch " + std::to_string((uint32_t)(hst[4] >> 32)) +
                           " with sequence " + std::to_string((uint32_t)(hst[4] & 0xffffffffu)));
   }
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                const double* proximal, uint64_t n, const uint8_t* q_codes,
+                                const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, double* lnl) {
+  if (!ctx || (n && (!pairs || !pendant || !distal || !lnl || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (n == 0) return EPA_OK;
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> hb_buf, hs_buf;
+  const uint32_t* hb = host_view(win_begin, Q, hb_buf, ctx->stream);
+  const uint32_t* hs = host_view(win_span, Q, hs_buf, ctx->stream);
+  if (!hb || !hs) return epa_fail(ctx, EPA_ERR_HIP, "cannot read window arrays");
+  uint32_t max_span = 0;
+  int rc = check_windows(ctx, hb, hs, Q, &max_span, true);   // an empty window is the empty sum: lnL 0
+  if (rc) return rc;
+  // host arrays are validated (device arrays are the caller's responsibility): the first offending entry is named
+  const bool hp = !epa_is_device_ptr(pairs), hpe = !epa_is_device_ptr(pendant), hd = !epa_is_device_ptr(distal);
+  const bool hx = proximal && !epa_is_device_ptr(proximal);
+  auto bad = [&](uint64_t i, const char* what) {
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "score_at: entry " + std::to_string(i) + ": " + what);
+  };
+  for (uint64_t i = 0; i < n; ++i) {
+    if (hp && pairs[i].branch_id >= ctx->B) return bad(i, "branch id out of range");
+    if (hp && pairs[i].seq_id >= Q) return bad(i, "sequence id out of range");
+    if (hpe && !(std::isfinite(pendant[i]) && pendant[i] >= 0.0)) return bad(i, "pendant length is negative or not finite");
+    if (hd && !(std::isfinite(distal[i]) && distal[i] >= 0.0)) return bad(i, "distal length is negative or not finite");
+    if (hx && !(std::isfinite(proximal[i]) && proximal[i] >= 0.0)) return bad(i, "proximal length is negative or not finite");
+    if (!proximal && hp && hd && distal[i] > ctx->h_blen[pairs[i].branch_id])
+      return bad(i, "distal length beyond the branch's length");
+  }
+  const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
+  const epa_pair* d_pairs = (const epa_pair*)epa_to_device(ctx, 4, pairs, sizeof(epa_pair) * n);
+  const double* d_pen = (const double*)epa_to_device(ctx, 7, pendant, sizeof(double) * n);
+  const double* d_dis = (const double*)epa_to_device(ctx, 8, distal, sizeof(double) * n);
+  const double* d_prx = proximal ? (const double*)epa_to_device(ctx, 9, proximal, sizeof(double) * n) : nullptr;
+  if (!d_codes || !d_begin || !d_span || !d_pairs || !d_pen || !d_dis || (proximal && !d_prx))
+    return epa_fail(ctx, EPA_ERR_HIP, "score_at input upload failed");
+  const bool out_dev = epa_is_device_ptr(lnl);
+  double* d_lnl = out_dev ? lnl : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
+  if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(score_at out)");
+  rc = launch_score_at(ctx, d_pairs, d_pen, d_dis, d_prx, n, d_codes, d_begin, d_span, d_lnl);
+  if (rc) return rc;
+  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(lnl, d_lnl, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  // host inputs were staged from pageable memory: they must not change before the copies ran
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return EPA_OK;
 }
 
@@ -2570,6 +2619,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "thorough")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_THOROUGH]][epa_ctx::T_THOROUGH];
   else if (!strcmp(which, "lookup")) t = &ctx->t_lookup;
   else if (!strcmp(which, "select")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SELECT]][epa_ctx::T_SELECT];
+  else if (!strcmp(which, "score_at")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SCORE]][epa_ctx::T_SCORE];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

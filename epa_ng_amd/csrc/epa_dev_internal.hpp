@@ -238,14 +238,14 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, N_TIMERS = 4 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
   uint32_t blk_ev_n[N_BANKS] = {};
   void* blk_buf[N_BANKS] = {};
   size_t blk_sz[N_BANKS] = {};
-  EvTimer t_bank[N_BANKS][3];
+  EvTimer t_bank[N_BANKS][N_TIMERS];
   // shares of the branch-sorted pair list the eight XCDs take in the single-wave Newton launches (cumulative, 20-bit
   // fixed point; thorough_dna.hip ThArgs::xcum), adapted to the speeds the XCDs showed: epa_xcd_feedback
   uint32_t xcd_cum[9] = {0u, 1u << 17, 2u << 17, 3u << 17, 4u << 17, 5u << 17, 6u << 17, 7u << 17, 1u << 20};
@@ -257,7 +257,7 @@ struct epa_ctx {
   // selection (chunk_body_begin: in the shadow of the host's round trip); the launch that uses them clears the mark
   const void* clean_stats[N_BANKS] = {};
   bool clean_ctr[N_BANKS] = {};
-  int t_last[3] = {0, 0, 0};
+  int t_last[N_TIMERS] = {0, 0, 0, 0};
   epa_thorough_stats last_stats{};
 };
 
@@ -350,6 +350,10 @@ int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pa
 int launch_thorough_aa_mfma(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* d_order, uint64_t n_pairs,
                             const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span,
                             uint32_t max_span, epa_result* d_out, unsigned long long* d_stats);
+// lnL of n entries (pair, pendant, distal, proximal or null = blen - distal) at the given lengths (score_at.hip)
+int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                    const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
+                    const uint32_t* d_span, double* d_lnl);
 int launch_select(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold,
                   epa_pair* d_pairs, uint64_t max_pairs, uint64_t* n_pairs,
                   const uint32_t* d_span = nullptr);  // d_span: also histogram the span classes

@@ -375,6 +375,14 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision,
 void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_texts, const std::string& newick,
                        const std::string& invocation);
 
+// jplace (version 3) reader for --rescore: per placement object its single name ("n": [name] or "nm": [[name,
+// multiplicity]]) and of every row edge_num, distal_length and pendant_length; "fields" may come in any order, every
+// other field is read and ignored.  Throws std::runtime_error naming the file and the problem (malformed JSON, a missing
+// required field, not exactly one name).
+struct Jplace_Row { uint32_t edge_num; double distal_length, pendant_length; };
+struct Jplace_PQuery { std::string name; std::vector<Jplace_Row> rows; };
+std::vector<Jplace_PQuery> read_jplace(const std::string& path);
+
 // ---- device-backed evaluator: one epa_ctx, RAII
 class Device_Evaluator {
 public:
@@ -443,6 +451,7 @@ size_t place_all(const MSA& chunk, const Encoded_Chunk& enc, const Tree& tree, D
                  Sample& sample, const Options& options, size_t seq_id_offset = 0);
 
 void compute_and_set_lwr(Sample& sample);            // src/set_manipulators.cpp:43-69
+void sort_by_lwr(PQuery& pq);                        // :71-74, with the device's tie rule (place.cpp)
 void filter(Sample& sample, const Options& options);  // :192-204
 
 // The chunk loop (src/core/place.cpp:173-251): reads `query_file` in chunks, writes
@@ -485,6 +494,13 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const std:
 Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_Info& msa_info,
                      const std::string& outdir, const Options& options, const std::string& invocation,
                      const std::vector<int>& devices);
+
+// --rescore: the placements of `jplace_file` (edge, distal, pendant as read) evaluated again under this tree and model
+// (epa_dev_score_at: no optimiser, no heuristic, no filter); likelihood and like_weight_ratio are recomputed, rows
+// LWR-descending, pqueries in input order -> <outdir>/epa_result.jplace.  The jplace is read and validated before the
+// device is created; any error leaves no output file.
+Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::string& query_file, const MSA_Info& msa_info,
+                  const std::string& outdir, const Options& options, const std::string& invocation, int device = 0);
 
 // one process per GPU: rank's contiguous slice of the query file on `device`, results gathered to rank 0
 // over the product library's RCCL gather (place_ranks.cpp; src/net/epa_mpi_util.cpp:10-30)

@@ -5,6 +5,7 @@
 #include <charconv>
 #include <system_error>
 #include <fstream>
+#include <iterator>
 #include <ostream>
 
 #include <cctype>
@@ -468,6 +469,197 @@ size_t format_fixed(char* buf, size_t cap, double v, unsigned int precision) {
   if (r.ec == std::errc()) return (size_t)(r.ptr - buf);
   const int len = std::snprintf(buf, cap, "%.*f", (int)precision, v);
   return (size_t)std::max(0, std::min(len, (int)cap - 1));
+}
+
+// ---- jplace reader (version 3; the format of src/io/jplace_util.cpp read back): a small recursive-descent JSON
+// parser over the whole file, then the "fields" / "placements" members.  Everything it does not need is parsed (so
+// that malformed JSON anywhere is an error) and dropped.
+namespace {
+struct Json {
+  enum Kind { kNull, kBool, kNumber, kString, kArray, kObject } kind = kNull;
+  double num = 0.0;
+  std::string str;
+  std::vector<Json> items;                               // array elements / object values
+  std::vector<std::string> keys;                         // object keys, parallel to items
+  const Json* member(const char* k) const {
+    for (size_t i = 0; i < keys.size(); ++i) if (keys[i] == k) return &items[i];
+    return nullptr;
+  }
+};
+
+class Json_Parser {
+public:
+  Json_Parser(const std::string& text, const std::string& path) : p_(text.data()), b_(text.data()), e_(text.data() + text.size()), path_(path) {}
+  Json parse() {
+    Json v = value(0);
+    ws();
+    if (p_ != e_) fail("text after the end of the document");
+    return v;
+  }
+  [[noreturn]] void fail(const std::string& what) const {
+    throw std::runtime_error{path_ + ": malformed JSON at byte " + std::to_string((size_t)(p_ - b_)) + ": " + what};
+  }
+private:
+  void ws() { while (p_ < e_ && (*p_ == ' ' || *p_ == '\n' || *p_ == '\t' || *p_ == '\r')) ++p_; }
+  bool lit(const char* s) {
+    const size_t n = std::strlen(s);
+    if ((size_t)(e_ - p_) < n || std::memcmp(p_, s, n) != 0) return false;
+    p_ += n;
+    return true;
+  }
+  std::string string() {
+    std::string o;
+    ++p_;   // opening quote
+    for (;;) {
+      if (p_ >= e_) fail("unterminated string");
+      const char c = *p_++;
+      if (c == '"') return o;
+      if (c != '\\') { o += c; continue; }
+      if (p_ >= e_) fail("unterminated string");
+      const char x = *p_++;
+      switch (x) {
+        case '"': case '\\': case '/': o += x; break;
+        case 'b': o += '\b'; break;
+        case 'f': o += '\f'; break;
+        case 'n': o += '\n'; break;
+        case 'r': o += '\r'; break;
+        case 't': o += '\t'; break;
+        case 'u': {
+          if (e_ - p_ < 4) fail("short \\u escape");
+          unsigned cp = 0;
+          for (int i = 0; i < 4; ++i) {
+            const char h = *p_++;
+            cp = cp * 16 + (unsigned)(h >= '0' && h <= '9' ? h - '0' : h >= 'a' && h <= 'f' ? h - 'a' + 10
+                                      : h >= 'A' && h <= 'F' ? h - 'A' + 10 : (fail("bad \\u escape"), 0));
+          }
+          if (cp < 0x80) o += (char)cp;   // UTF-8 (surrogate pairs are kept as two code units: names are compared as bytes)
+          else if (cp < 0x800) { o += (char)(0xc0 | (cp >> 6)); o += (char)(0x80 | (cp & 0x3f)); }
+          else { o += (char)(0xe0 | (cp >> 12)); o += (char)(0x80 | ((cp >> 6) & 0x3f)); o += (char)(0x80 | (cp & 0x3f)); }
+          break;
+        }
+        default: fail("unknown escape");
+      }
+    }
+  }
+  Json value(int depth) {
+    if (depth > 64) fail("nested too deeply");
+    ws();
+    if (p_ >= e_) fail("unexpected end of file");
+    Json v;
+    const char c = *p_;
+    if (c == '{') {
+      v.kind = Json::kObject;
+      ++p_;
+      ws();
+      if (p_ < e_ && *p_ == '}') { ++p_; return v; }
+      for (;;) {
+        ws();
+        if (p_ >= e_ || *p_ != '"') fail("expected a member name");
+        v.keys.push_back(string());
+        ws();
+        if (p_ >= e_ || *p_ != ':') fail("expected ':'");
+        ++p_;
+        v.items.push_back(value(depth + 1));
+        ws();
+        if (p_ < e_ && *p_ == ',') { ++p_; continue; }
+        if (p_ < e_ && *p_ == '}') { ++p_; return v; }
+        fail(p_ >= e_ ? "unexpected end of file" : "expected ',' or '}'");
+      }
+    }
+    if (c == '[') {
+      v.kind = Json::kArray;
+      ++p_;
+      ws();
+      if (p_ < e_ && *p_ == ']') { ++p_; return v; }
+      for (;;) {
+        v.items.push_back(value(depth + 1));
+        ws();
+        if (p_ < e_ && *p_ == ',') { ++p_; continue; }
+        if (p_ < e_ && *p_ == ']') { ++p_; return v; }
+        fail(p_ >= e_ ? "unexpected end of file" : "expected ',' or ']'");
+      }
+    }
+    if (c == '"') { v.kind = Json::kString; v.str = string(); return v; }
+    if (lit("true")) { v.kind = Json::kBool; v.num = 1.0; return v; }
+    if (lit("false")) { v.kind = Json::kBool; return v; }
+    if (lit("null")) return v;
+    if (c == '-' || (c >= '0' && c <= '9')) {
+      const char* q = p_;
+      while (q < e_ && (std::isdigit((unsigned char)*q) || *q == '-' || *q == '+' || *q == '.' || *q == 'e' || *q == 'E')) ++q;
+      const std::string tok(p_, q);
+      char* end = nullptr;
+      v.kind = Json::kNumber;
+      v.num = std::strtod(tok.c_str(), &end);   // out of range: +-inf, refused by the caller's checks
+      if (end != tok.c_str() + tok.size()) fail("bad number '" + tok + "'");
+      p_ = q;
+      return v;
+    }
+    fail("unexpected character");
+  }
+  const char *p_, *b_, *e_;
+  const std::string& path_;
+};
+}  // namespace
+
+std::vector<Jplace_PQuery> read_jplace(const std::string& path) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw std::runtime_error{path + ": cannot open the jplace file"};
+  std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  const Json doc = Json_Parser(text, path).parse();
+  auto fail = [&](const std::string& what) -> void { throw std::runtime_error{path + ": " + what}; };
+  if (doc.kind != Json::kObject) fail("not a jplace document (no top-level object)");
+  const Json* fields = doc.member("fields");
+  const Json* pls = doc.member("placements");
+  if (!fields || fields->kind != Json::kArray) fail("no \"fields\" array");
+  if (!pls || pls->kind != Json::kArray) fail("no \"placements\" array");
+  int col_edge = -1, col_distal = -1, col_pendant = -1;
+  for (size_t i = 0; i < fields->items.size(); ++i) {
+    if (fields->items[i].kind != Json::kString) fail("\"fields\" holds something that is not a string");
+    const std::string& n = fields->items[i].str;
+    if (n == "edge_num") col_edge = (int)i;
+    else if (n == "distal_length") col_distal = (int)i;
+    else if (n == "pendant_length") col_pendant = (int)i;
+  }
+  if (col_edge < 0) fail("required field \"edge_num\" is missing from \"fields\"");
+  if (col_distal < 0) fail("required field \"distal_length\" is missing from \"fields\"");
+  if (col_pendant < 0) fail("required field \"pendant_length\" is missing from \"fields\"");
+  const size_t ncol = fields->items.size();
+  std::vector<Jplace_PQuery> out;
+  out.reserve(pls->items.size());
+  for (size_t i = 0; i < pls->items.size(); ++i) {
+    const Json& o = pls->items[i];
+    const std::string where = "placement object " + std::to_string(i) + ": ";
+    if (o.kind != Json::kObject) fail(where + "not an object");
+    Jplace_PQuery pq;
+    const Json *n = o.member("n"), *nm = o.member("nm"), *p = o.member("p");
+    if ((n != nullptr) == (nm != nullptr)) fail(where + "needs exactly one of \"n\" and \"nm\"");
+    const Json& names = n ? *n : *nm;
+    if (names.kind != Json::kArray || names.items.size() != 1)
+      fail(where + "must carry exactly one name (" + std::to_string(names.kind == Json::kArray ? names.items.size() : 0) + " given)");
+    const Json& first = names.items[0];
+    if (n) {
+      if (first.kind != Json::kString) fail(where + "the name is not a string");
+      pq.name = first.str;
+    } else {   // [name, multiplicity]: the multiplicity is ignored
+      if (first.kind != Json::kArray || first.items.empty() || first.items[0].kind != Json::kString)
+        fail(where + "\"nm\" entries are [name, multiplicity]");
+      pq.name = first.items[0].str;
+    }
+    if (!p || p->kind != Json::kArray) fail(where + "no \"p\" array");
+    for (size_t r = 0; r < p->items.size(); ++r) {
+      const Json& row = p->items[r];
+      const std::string rw = where + "row " + std::to_string(r) + ": ";
+      if (row.kind != Json::kArray || row.items.size() != ncol)
+        fail(rw + "does not have one value per field");
+      for (int c : {col_edge, col_distal, col_pendant})
+        if (row.items[(size_t)c].kind != Json::kNumber) fail(rw + "\"" + fields->items[(size_t)c].str + "\" is not a number");
+      const double e = row.items[(size_t)col_edge].num;
+      if (!(e >= 0.0 && e <= 4294967295.0) || e != std::floor(e)) fail(rw + "edge_num is not a non-negative integer");
+      pq.rows.push_back(Jplace_Row{(uint32_t)e, row.items[(size_t)col_distal].num, row.items[(size_t)col_pendant].num});
+    }
+    out.push_back(std::move(pq));
+  }
+  return out;
 }
 
 // One chunk of the "placements" array as text (sample_to_jplace_string, src/io/jplace_util.cpp:

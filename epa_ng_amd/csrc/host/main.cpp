@@ -26,6 +26,10 @@ static void usage() {
       "  --baseball-heur       baseball heuristic\n"
       "  --no-heur             thorough placement on every branch\n"
       "  --filter-acc-lwr X | --filter-min-lwr X | --filter-min N | --filter-max N\n"
+      "  --rescore FILE.jplace  no placement: evaluate the placements of FILE (jplace version 3: edge_num, distal_length,\n"
+      "                        pendant_length of every row) again under this tree, alignment and model; likelihood and\n"
+      "                        like_weight_ratio are recomputed, everything else is kept.  No heuristic, optimiser or\n"
+      "                        filter flag applies (they are refused); one device; --preserve-rooting off for rooted trees\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -56,7 +60,8 @@ int main(int argc, char** argv) {
   const auto start = std::chrono::steady_clock::now();
   std::string invocation;
   for (int i = 0; i < argc; ++i) { invocation += argv[i]; invocation += " "; }
-  std::string tree_file, ref_file, query_file, outdir = "./", model_desc = "GTR+G", stats_json;
+  std::string tree_file, ref_file, query_file, outdir = "./", model_desc = "GTR+G", stats_json, rescore_file;
+  std::vector<std::string> placing_flags;   // flags that steer heuristic, optimiser or filter: meaningless with --rescore
   Options opt;
   int device = 0;
   bool device_given = false;
@@ -78,6 +83,9 @@ int main(int argc, char** argv) {
   };
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
+    if (a == "-g" || a == "--dyn-heur" || a == "-G" || a == "--fix-heur" || a == "--baseball-heur" || a == "--no-heur" ||
+        a == "--raxml-blo" || a.rfind("--filter-", 0) == 0)
+      placing_flags.push_back(a);
     if (a == "-t" || a == "--tree") tree_file = need(i);
     else if (a == "-s" || a == "--ref-msa" || a == "--msa") ref_file = need(i);
     else if (a == "-q" || a == "--query") query_file = need(i);
@@ -91,6 +99,7 @@ int main(int argc, char** argv) {
     else if (a == "--filter-min-lwr") { opt.support_threshold = std::stod(need(i)); opt.acc_threshold = false; }
     else if (a == "--filter-min") opt.filter_min = (unsigned)std::stoul(need(i));
     else if (a == "--filter-max") opt.filter_max = (unsigned)std::stoul(need(i));
+    else if (a == "--rescore") rescore_file = need(i);
     else if (a == "--precision") opt.precision = (unsigned)std::stoul(need(i));
     else if (a == "--chunk-size") { opt.chunk_size = (unsigned)std::stoul(need(i)); opt.chunk_size_given = true; }
     else if (a == "--device-min-chunk") { opt.device_min_chunk = (unsigned)std::stoul(need(i)); opt.device_min_chunk_given = true; }
@@ -152,6 +161,18 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (opt.filter_min > opt.filter_max) { std::cerr << "filter-min must not exceed filter-max!\n"; return 1; }
+  if (!rescore_file.empty()) {   // what --rescore does not do is refused, not silently ignored
+    if (!placing_flags.empty()) {
+      std::cerr << "--rescore evaluates the file's placements as they are: " << placing_flags[0]
+                << " does not apply and cannot be combined with it\n";
+      return 1;
+    }
+    if (devices.size() > 1) { std::cerr << "--rescore runs on one device: --devices with several GPUs is not supported with it\n"; return 1; }
+    if (world > 1 || !comm_file.empty()) {
+      std::cerr << "--rescore runs in one process: --rank / --world / --comm-file are not supported with it\n";
+      return 1;
+    }
+  }
   try {
     std::ifstream tf(tree_file);
     if (!tf) throw std::runtime_error{"file_check failed: " + tree_file};
@@ -188,7 +209,9 @@ int main(int argc, char** argv) {
     const double secs_tree = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tree).count();
     if (devices.empty()) devices.push_back(device);
     const bool rank_mode = world > 1 || !comm_file.empty();   // a 1-rank communicator is legal (tests, 1-GPU nodes)
-    const Run_Stats st = rank_mode
+    const Run_Stats st = !rescore_file.empty()
+        ? rescore(tree, rescore_file, query_file, qry_info, outdir, opt, invocation, devices[0])
+        : rank_mode
         ? simple_mpi_ranks(tree, query_file, qry_info, outdir, opt, invocation, device_given ? device : local_rank, rank, world, comm_file)
         : simple_mpi(tree, query_file, qry_info, outdir, opt, invocation, devices);
     if (rank_mode && rank != 0) {

@@ -426,7 +426,7 @@ void compute_and_set_lwr(Sample& sample) {
 // descending, then lnL descending, then the lowest branch id.  LWR is monotone in lnL, so for LWRs computed from
 // the lnLs (compute_and_set_lwr) this is "lnL descending, then branch id": equal LWRs of different lnL (both 0
 // after underflow) are ordered by lnL, not by their position in the pquery
-static void sort_by_lwr(PQuery& pq) {
+void sort_by_lwr(PQuery& pq) {
   std::sort(pq.begin(), pq.end(), [](const Placement& a, const Placement& b) {
     if (a.lwr() != b.lwr()) return a.lwr() > b.lwr();
     if (a.likelihood() != b.likelihood()) return a.likelihood() > b.likelihood();

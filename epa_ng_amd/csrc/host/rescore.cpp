@@ -1,0 +1,150 @@
+// --rescore FILE.jplace: the placements of an existing jplace evaluated again at their own branch lengths under
+// this run's tree, alignment and model.  The device call is epa_dev_score_at (Tiny_Tree::place with opt_branches ==
+// false, src/tree/Tiny_Tree.cpp:186-204); the chunk loop around it reads the query file like simple_mpi (place.cpp)
+// does -- same reader, same premasking -- and picks the sequences the jplace names.
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <fstream>
+#include <iostream>
+#include <unordered_map>
+
+#include "epa_host.hpp"
+
+namespace epa {
+
+namespace {
+// a writer that rounded distal_length to a few digits may have pushed it over the branch's length by this much
+constexpr double kDistalSlack = 1e-6;
+}  // namespace
+
+Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::string& query_file, const MSA_Info& msa_info,
+                  const std::string& outdir, const Options& options, const std::string& invocation, int device) {
+  using clk = std::chrono::steady_clock;
+  // ---- everything that can be refused without a device
+  if (tree.mapper())
+    throw std::runtime_error{"--rescore: the reference tree is rooted and --preserve-rooting is on: the file's edge numbers "
+                             "are the rooted tree's, which cannot be mapped back to the unrooted working tree in this "
+                             "version; run with --preserve-rooting off"};
+  std::vector<Jplace_PQuery> input = read_jplace(jplace_file);
+  const size_t B = tree.num_branches();
+  std::vector<double> blen;
+  {
+    epa_tree_desc d;
+    Tree::Tree_Desc_Storage store;
+    tree.fill_tree_desc(d, store);
+    blen.swap(store.blen);
+  }
+  std::unordered_map<std::string, size_t> by_name;
+  size_t n_rows = 0;
+  for (size_t i = 0; i < input.size(); ++i) {
+    Jplace_PQuery& pq = input[i];
+    const std::string where = jplace_file + ": placement of '" + pq.name + "': ";
+    if (!by_name.emplace(pq.name, i).second) throw std::runtime_error{where + "the name occurs in more than one placement object"};
+    for (Jplace_Row& r : pq.rows) {
+      if (r.edge_num >= B)
+        throw std::runtime_error{where + "edge_num " + std::to_string(r.edge_num) + " is not a branch of the reference tree (" +
+                                 std::to_string(B) + " branches)"};
+      if (!std::isfinite(r.pendant_length) || r.pendant_length < 0.0)
+        throw std::runtime_error{where + "pendant_length " + std::to_string(r.pendant_length) + " is negative or not finite"};
+      if (!std::isfinite(r.distal_length) || r.distal_length < 0.0)
+        throw std::runtime_error{where + "distal_length " + std::to_string(r.distal_length) + " is negative or not finite"};
+      if (r.distal_length > blen[r.edge_num]) {
+        if (r.distal_length > blen[r.edge_num] + kDistalSlack)
+          throw std::runtime_error{where + "distal_length " + std::to_string(r.distal_length) + " lies beyond the length of edge " +
+                                   std::to_string(r.edge_num) + " (" + std::to_string(blen[r.edge_num]) + ")"};
+        r.distal_length = blen[r.edge_num];
+      }
+      ++n_rows;
+    }
+  }
+
+  // ---- device
+  Run_Stats st;
+  st.host_threads = configure_host_threads();
+  st.chunk_path = "rescore";
+  auto ts = clk::now();
+  Device_Evaluator dev(tree, options, device);
+  st.ref_tree_logl = dev.ref_tree_logl(0);
+  st.seconds_setup = std::chrono::duration<double>(clk::now() - ts).count();
+  if (dev.lookup_blocks()) { st.lookup_mode = "blocks"; st.lookup_block = dev.lookup_block(); }
+  const auto t_loop = clk::now();
+
+  Sample sample(input.size());
+  std::vector<char> seen(input.size(), 0);
+  const bool premask = options.premasking && msa_info.gap_count() > 0;
+  Fasta_Stream reader(query_file);
+  const size_t per_chunk = std::max<size_t>(1, options.chunk_size);
+  st.device_chunk = per_chunk;
+  size_t skipped = 0;
+  for (;;) {
+    ts = clk::now();
+    MSA chunk;
+    if (reader.read_next(chunk, per_chunk) == 0) break;
+    st.seconds_read += std::chrono::duration<double>(clk::now() - ts).count();
+    // the sequences of this chunk that the jplace names, in file order
+    MSA named;
+    std::vector<size_t> target;
+    for (Sequence& s : chunk) {
+      const auto it = by_name.find(s.header());
+      if (it == by_name.end() || seen[it->second]) { ++skipped; continue; }
+      seen[it->second] = 1;
+      target.push_back(it->second);
+      named.emplace_back(s.header(), premask ? subset_sequence(s.sequence(), msa_info.gap_mask()) : s.sequence());
+    }
+    if (named.empty()) continue;
+    ts = clk::now();
+    const Encoded_Chunk enc = encode_chunk(named, tree, options);
+    st.seconds_encode += std::chrono::duration<double>(clk::now() - ts).count();
+    std::vector<epa_pair> pairs;
+    std::vector<double> pendant, distal;
+    for (size_t q = 0; q < named.size(); ++q)
+      for (const Jplace_Row& r : input[target[q]].rows) {
+        pairs.push_back(epa_pair{r.edge_num, (uint32_t)q});
+        pendant.push_back(r.pendant_length);
+        distal.push_back(r.distal_length);
+      }
+    std::vector<double> lnl(pairs.size());
+    ts = clk::now();
+    epa_dev_set_query_layout(dev.ctx(), enc.stride);
+    epa_dev_set_query_packing(dev.ctx(), enc.bits);
+    const int rc = epa_dev_score_at(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
+                                    enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
+                                    lnl.data());
+    if (rc != EPA_OK)
+      throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+    st.seconds_place += std::chrono::duration<double>(clk::now() - ts).count();
+    size_t k = 0;
+    for (size_t q = 0; q < named.size(); ++q) {
+      PQuery pq(target[q], named[q].header());
+      for (const Jplace_Row& r : input[target[q]].rows) pq.emplace_back(r.edge_num, lnl[k++], r.pendant_length, r.distal_length);
+      sample[target[q]] = std::move(pq);
+    }
+    st.queries += named.size();
+    st.pairs += pairs.size();
+  }
+  for (size_t i = 0; i < input.size(); ++i)
+    if (!seen[i])
+      throw std::runtime_error{"--rescore: sequence '" + input[i].name + "' of " + jplace_file + " does not occur in " + query_file};
+  std::cout << "Rescored " << n_rows << " placements of " << st.queries << " sequences; " << skipped
+            << " sequences of the query file are not named in " << jplace_file << " and were skipped." << std::endl;
+
+  ts = clk::now();
+  compute_and_set_lwr(sample);
+  for (PQuery& pq : sample) sort_by_lwr(pq);
+  st.seconds_post = std::chrono::duration<double>(clk::now() - ts).count();
+  ts = clk::now();
+  std::string dir = outdir;
+  if (!dir.empty() && dir.back() != '/') dir += "/";
+  const std::string out_path = dir + "epa_result.jplace";
+  std::ofstream os(out_path);
+  if (!os) throw std::runtime_error{"cannot open " + out_path};
+  write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision);
+  os.flush();
+  if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }
+  st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();
+  st.seconds_loop = std::chrono::duration<double>(clk::now() - t_loop).count();
+  return st;
+}
+
+}  // namespace epa

@@ -361,6 +361,32 @@ int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_pairs,
                      uint32_t Q, epa_result* out, epa_thorough_stats* stats);
 
 /*
+ * Log-likelihood of given placements at GIVEN branch lengths; no optimiser runs.  This is what Tiny_Tree::place
+ * returns with opt_branches == false once the triplet's lengths are set (src/tree/Tiny_Tree.cpp:186-204:
+ * pll_update_prob_matrices on the three edges, pll_update_partials of the inner node toward the query,
+ * pll_compute_edge_loglikelihood on the pendant edge, summed over the sites of the query's window, scaler counts and
+ * the +I term included), i.e. the `likelihood` of a jplace row at that row's own lengths.
+ * entry i: pairs[i], pendant[i], distal[i], proximal[i].  proximal == NULL: branch_length[b] - distal[i]
+ * (the sliding rule's convention and what a jplace row means).  One double per entry, in entry order.
+ * Queries are staged as for epa_dev_thorough (query layout / packing of the context); entry arrays and lnl may be host
+ * or device pointers; n == 0 returns EPA_OK.  Host arrays are validated, EPA_ERR_INVALID_ARG names the first offending
+ * entry: branch_id >= B, seq_id >= Q, a non-finite or negative length, and with proximal == NULL a distal length beyond
+ * the branch's.  A length of exactly 0 is valid (P = I).  An entry on a query with win_span == 0 gets 0.0 (the empty sum).
+ * Reads only the transformed CLVs and scaler counts: the same bits in the resident and the blocked lookup layout.
+ * Accuracy: P(t) is formed through the eigenbasis, where exp(lambda r t) cancels for tiny t: the absolute error of lnL
+ * grows roughly like 1 / pendant below 1e-4.  The CLVs live in the eigenbasis too; an entry of a CLV brought back to
+ * state space that does not exceed the rounding-error bound of its own sum (32 unit roundoffs of the sum of its terms'
+ * magnitudes) is taken as 0, which is what libpll holds there: a state that a tip excludes, at a distal or proximal
+ * length of exactly 0 (P(0) is the identity matrix).  Without that cut the residue of ~1e-16 was divided by a tiny
+ * pendant length wherever the query shows such a state (up to 2.2e-6 at pendant 1e-4; tests/test_gpu_score_at.py).
+ * Timer: "score_at" of epa_dev_last_kernel_ms.
+ */
+int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                     const double* proximal /* may be NULL */, uint64_t n,
+                     const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                     double* lnl);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -597,7 +623,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
