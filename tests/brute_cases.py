@@ -9,6 +9,18 @@ Every configuration is the smallest shape that still reaches its code path:
   S  ladder trees deep enough that every site is rescaled (asserted by the tests), 4 Gamma categories
   L  a window beyond 1536 sites (the long-window kernel)
   X  branch lengths drawn from [1e-8, 20]: the two trees reach 9e-7 and 11.9
+
+OPT_NAMES adds the inputs of the end-point tests (tests/test_endpoints_cpu.py, tests/test_gpu_endpoints.py), which
+compare where the branch-length optimiser ENDS with BruteForce.optimise through the fixtures of tests/golden/endpoints:
+  T4 / T4I  group D's shape with four unequal categories, pinv 0 / 0.2: the main tuned nucleotide kernel (one wave
+            group) in span classes 0, 1, 2, 3 and the half-chunk classes 10, 11
+  M / MI    8 tips (B = 13), 1600 sites, four unequal categories, pinv 0 / 0.2, windows on both sides of every step
+            between span classes 3 .. 8 (1 / 2 / 4 / 8 waves per pair)
+  AL        20 states, 6 tips, 420 sites, four categories, windows of 384, 385 and 420 residues.  A thorough call is
+            dispatched by its LONGEST window, so all of AL (420) runs on the lane-per-site kernel with its HBM slab
+            under the sliding rule and on the general kernel under --raxml-blo
+  AL384     AL's tree and alignment with windows of 258, 383, 384 and 384 residues: the call's longest window is 384,
+            the matrix-core kernel's last, under both rules
 """
 import functools
 
@@ -21,8 +33,13 @@ D_READS = (1, 3, 30, 64, 65, 96, 97, 128, 129, 160, 161, 192, 193, 200)
 A_CATS = (1, 2, 3, 4, 6, 8, 9)
 A_READS = (1, 30, 64, 65, 102, 103, 128, 129, 192, 193, 256, 257)
 
+M_READS = (256, 257, 384, 385, 512, 513, 768, 769, 1024, 1025, 1536)
+AL_READS = (384, 384, 385, 385, 420, 420)
+AL384_READS = (258, 383, 384, 384)
+
 NAMES = (["D%d" % c for c in D_CATS] + ["A%d" % c for c in A_CATS]
          + ["S4", "S20", "L", "Xlong", "Xshort"])
+OPT_NAMES = ("T4", "T4I", "M", "MI", "AL", "AL384") + tuple(NAMES)
 
 AMBIG = {4: "RYKMSWBDHVN-", 20: "BZX-"}
 
@@ -156,6 +173,18 @@ def case(name):
         c = _simulated(4, 9, 130, (3, 65), 5100, mean_bl=1e-5, lo=1e-8, hi=1.0)
         c["rates"], c["weights"] = free_rates(7, 5107)
         c.update(pinv=0.35, branch_step=1, variants=(plain,))
+    elif name in ("T4", "T4I"):
+        c = _simulated(4, 12, 200, D_READS, 1100)
+        c["rates"], c["weights"] = free_rates(4, 1104)
+        c.update(pinv=0.2 if name == "T4I" else 0.0, branch_step=1, variants=())
+    elif name in ("M", "MI"):
+        c = _simulated(4, 8, 1600, M_READS, 6000)
+        c["rates"], c["weights"] = free_rates(4, 6004)
+        c.update(pinv=0.2 if name == "MI" else 0.0, branch_step=1, variants=())
+    elif name in ("AL", "AL384"):
+        c = _simulated(20, 6, 420, AL_READS if name == "AL" else AL384_READS, 7000)
+        c["rates"], c["weights"] = free_rates(4, 7004)
+        c.update(pinv=0.0, branch_step=1, variants=())
     else:
         raise KeyError(name)
     c["name"] = name
@@ -180,3 +209,36 @@ def pair_lists(c, B):
 
 def variant_ids():
     return [(n, i) for n in NAMES for i in range(len(case(n)["variants"]))]
+
+
+# ---- end-point tests: evaluator settings per configuration.  A variant is a setting of the DEVICE; the expected end
+# points depend on the configuration, the rule ("sliding" / "raxml") and the lower length bound alone.
+def opt_variants(name):
+    """-> list of dicts: mode, min_branch, and the evaluator settings (device_precompute, rate_scalers, blocks,
+    keep_eigenvalues, chunk, options) -- both rules on every configuration, the further settings on T4, A4, S4, S20"""
+    base = dict(device_precompute=True, rate_scalers=False, min_branch=1e-4)
+    extra = [{}]
+    if name == "T4":
+        extra += [dict(device_precompute=False), dict(blocks=True), dict(keep_eigenvalues=True),
+                  dict(min_branch=1e-6), dict(chunk=True)]
+    elif name == "A4":
+        extra += [dict(blocks=True), dict(options=(("aa_valu", 1),))]
+    elif name in ("S4", "S20"):
+        extra += [dict(rate_scalers=True)]
+    # aa_valu switches kernels under the sliding rule only: under --raxml-blo it would repeat the plain item
+    return [dict(base, mode=mode, **e) for e in extra for mode in ("sliding", "raxml")
+            if not (mode == "raxml" and e.get("options"))]
+
+
+def opt_variant_ids():
+    def label(v):
+        tags = [k for k in ("blocks", "keep_eigenvalues", "chunk", "rate_scalers") if v.get(k)]
+        tags += ["host"] if not v["device_precompute"] else []
+        tags += ["min%g" % v["min_branch"]] if v["min_branch"] != 1e-4 else []
+        tags += [k for k, _ in v.get("options", ())]
+        return "-".join([v["mode"]] + tags)
+    return [(n, i, "%s-%s" % (n, label(v))) for n in OPT_NAMES for i, v in enumerate(opt_variants(n))]
+
+
+def endpoint_key(mode, min_branch):
+    return "%s@%g" % (mode, min_branch)

@@ -7,7 +7,7 @@ It shares no machinery with the kernels or with the C restatement of their desig
   * categories are combined with logsumexp(log w_k + ...), any weights (+R) -- no padded categories;
   * a query is scored by physically forming the three-branch star at the insertion point -- no lookup columns.
 From tests/gen_golden.py it takes the alphabet and the tree helpers only (char_vec, parse_newick, branches_postorder,
-valid_range, DEFAULT_BL) and the rate-matrix construction of its Model.
+valid_range, DEFAULT_BL), the rate-matrix construction of its Model and, for optimise() alone, its 1-D solver newton.
 
 Linear time: one downward partial per node and one upward partial per branch, each computed once in the constructor
 (gen_golden.reroot_partials recomputes subtrees per branch and gen_golden.prune normalises per site ACROSS categories,
@@ -22,7 +22,8 @@ import numpy as np
 from scipy.linalg import expm
 from scipy.special import logsumexp
 
-from gen_golden import DEFAULT_BL, Model, branches_postorder, char_vec, parse_newick, valid_range, walk
+from gen_golden import (DEF_OPT_BL, DEFAULT_BL, MAX_BL, Model, branches_postorder, char_vec, newton, parse_newick,
+                        valid_range, walk)
 
 _ALPHABET = {4: "ACGTURYSWKMBDHVNOX-?.", 20: "ARNDCQEGHILKMFPSTWYVBZX-?*"}
 
@@ -138,12 +139,13 @@ class BruteForce:
         lik = np.einsum("i,wci,wci->wc", self.m.freqs, d, self._push(self.P(n.length), u))
         return float(self._site_lnl(lik, ld + lu, self.log_cinv).sum())
 
-    def _star(self, branch, tipv, pendant, distal, lo, n):
-        """per-site lnL of query state sets tipv [..][n][s] hung on `branch` over the window [lo, lo + n)"""
+    def _star(self, branch, tipv, pendant, distal, lo, n, proximal=None):
+        """per-site lnL of query state sets tipv [..][n][s] hung on `branch` over the window [lo, lo + n); proximal
+        None: branch length - distal"""
         sl = slice(lo, lo + n)
         (d, ld), (u, lu) = self.down[branch], self.up[branch]
         x = (self.m.freqs * self._push(self._expm(distal), d[sl])
-             * self._push(self._expm(self.lengths[branch] - distal), u[sl]))
+             * self._push(self._expm(self.lengths[branch] - distal if proximal is None else proximal), u[sl]))
         lik = np.einsum("cij,...wj,wci->...wc", self._expm(pendant), tipv, x)
         return self._site_lnl(lik, (ld + lu)[sl], self.log_cinv[sl])
 
@@ -163,13 +165,111 @@ class BruteForce:
             out[:, b] = np.where(mask, self._site_lnl(lik, ld + lu, self.log_cinv), 0.0).sum(1)
         return out
 
-    def score_at(self, branch, query, pendant, distal):
+    def score_at(self, branch, query, pendant, distal, proximal=None):
         """lnL over the query's window at given lengths; distal is measured from the node below the edge, the
-        proximal length is original - distal"""
+        proximal length is original - distal unless given (the star at three free lengths)"""
         lo, n = valid_range(query)
-        return float(self._star(branch, self.tip_vectors(query)[lo:lo + n], float(pendant), float(distal), lo, n).sum())
+        return float(self._star(branch, self.tip_vectors(query)[lo:lo + n], float(pendant), float(distal), lo, n,
+                                None if proximal is None else float(proximal)).sum())
 
     def score_pairs(self, branches, seq_ids, queries, pendant, distal):
         """score_at over many (branch, query) pairs"""
         return np.array([self.score_at(int(b), queries[int(q)], pendant[i], distal[i])
                          for i, (b, q) in enumerate(zip(branches, seq_ids))])
+
+    # ---------------------------------------------------------------- the optimiser
+    def _deriv_logw(self):
+        """log category weights as the derivatives see them (a hook for the teeth tests)"""
+        return self.logw
+
+    def _deriv_log_cinv(self, sl):
+        """log(p pi_inv) per site as the derivatives see it (a hook for the teeth tests)"""
+        return self.log_cinv[sl]
+
+    def _derivatives(self, branch, tipv, lo, n, lens, which):
+        """-> deriv(t) = (f, f') of -lnL over the window in the length `which` (0 pendant, 1 distal, 2 proximal) of
+        the star on `branch`, the two other lengths fixed at lens.  P' = r / (1 - p) Q P and P'' likewise, on the
+        rate matrix; per site the categories are combined after subtracting the site's largest log factor; +I
+        adds p pi_inv to the site likelihood alone"""
+        sl = slice(lo, lo + n)
+        (d, ld), (u, lu) = self.down[branch], self.up[branch]
+        sides = [np.repeat(tipv[:, None, :], self.c, 1), d[sl], u[sl]]
+        other = self.m.freqs * np.prod([self._push(self._expm(lens[j]), sides[j]) for j in range(3) if j != which], 0)
+        lf = self._deriv_logw() + (ld + lu)[sl]
+        top = lf.max(1)
+        e = np.exp(lf - top[:, None])
+        with np.errstate(over="ignore"):
+            cinv = np.exp(self._deriv_log_cinv(sl) - top) if self.pinv > 0.0 else 0.0
+        rq = (self.m.rates / (1.0 - self.pinv))[:, None, None] * self.m.Q
+
+        def deriv(t):
+            P0 = self._expm(t)
+            P1 = rq @ P0
+            P2 = rq @ P1
+            l0, l1, l2 = ((e * np.einsum("wci,wci->wc", other, self._push(P, sides[which]))).sum(1) for P in (P0, P1, P2))
+            if self.pinv > 0.0:
+                l0, l1, l2 = (1.0 - self.pinv) * l0 + cinv, (1.0 - self.pinv) * l1, (1.0 - self.pinv) * l2
+            d1 = -l1 / l0
+            return float(d1.sum()), float((d1 * d1 - l2 / l0).sum())
+        return deriv
+
+    def optimise(self, branch, query, mode="sliding", min_branch=1e-4):
+        """Branch-length optimisation of one (branch, query) pair -> dict lnl, pendant, distal, rounds, reverted.
+
+        Shared with the C oracle (oracle/epa_oracle.c) and the kernels: the RECOLLECTED control flow alone --
+          sliding  opt_branch_lengths_pplacer (reference src/core/pll/optimize.cpp:60-248) as gen_golden.thorough
+                   states it: pendant solve on [MIN, MAX], distal solve on [min(MIN / 2, orig / 2), orig - xtol] with
+                   the proximal length orig - distal taken up afterwards, the revert test new - old > new 1e-14 and
+                   the 0.1 stop, at most 32 rounds;
+          raxml    pllmod_opt_optimize_branch_lengths_local(radius 1) as the project documents it: per round pendant,
+                   distal, proximal, pendant on [MIN, MAX]; a length is replaced when the solver moved it by more than
+                   1e-10; three independent lengths; the distal is rescaled by orig / (distal + proximal) at the end;
+          and the 1-D solver gen_golden.newton (imported, not copied).
+        NOT shared: all arithmetic.  f and f' come from Q^k expm(Q r t / (1 - p)) products on this class's normalised
+        partials with their per-(site, category) log factors -- no eigenbasis, no sumtable, no scaler counts, no
+        padded categories -- and the reported lnL is this class's own score_at at the returned lengths."""
+        assert mode in ("sliding", "raxml")
+        lo, n = valid_range(query)
+        tipv = self.tip_vectors(query)[lo:lo + n]
+        orig = float(self.lengths[branch])
+        MIN = float(min_branch)
+        lens = [DEFAULT_BL, orig / 2.0, orig / 2.0]
+        smoothings, rounds, reverted = 32, 0, False
+        if mode == "sliding":
+            negll = -self.score_at(branch, query, lens[0], lens[1])
+            while smoothings:
+                old = list(lens)
+                xmin, xmax = MIN, MAX_BL
+                xguess = lens[0] if xmin <= lens[0] <= xmax else DEF_OPT_BL
+                lens[0] = newton(xmin, xguess, xmax, xmin / 10.0, 30, self._derivatives(branch, tipv, lo, n, lens, 0))
+                xmin = min(MIN / 2.0, orig / 2.0)
+                xtol = xmin / 10.0
+                xmax = orig - xtol
+                xguess = lens[1] if xmin <= lens[1] <= xmax else orig / 2.0
+                lens[1] = newton(xmin, xguess, xmax, xtol, 30, self._derivatives(branch, tipv, lo, n, lens, 1))
+                lens[2] = orig - lens[1]                                  # the proximal P was still the old one
+                new = -self.score_at(branch, query, lens[0], lens[1])
+                rounds += 1
+                if new - negll > new * 1e-14:
+                    lens, reverted = old, True
+                    break
+                smoothings -= 1
+                if abs(new - negll) < 0.1:
+                    smoothings = 0
+                negll = new
+        else:
+            negll = -self.score_at(branch, query, *lens)
+            while smoothings:
+                for which in (0, 1, 2, 0):
+                    xguess = lens[which] if MIN <= lens[which] <= MAX_BL else DEF_OPT_BL
+                    r = newton(MIN, xguess, MAX_BL, MIN / 10.0, 30, self._derivatives(branch, tipv, lo, n, lens, which))
+                    if np.isfinite(r) and abs(lens[which] - r) > 1e-10:
+                        lens[which] = r
+                new = -self.score_at(branch, query, *lens)
+                rounds += 1
+                smoothings -= 1
+                if abs(new - negll) < 0.1:
+                    smoothings = 0
+                negll = new
+        return {"lnl": -negll, "pendant": lens[0], "distal": (orig / (lens[1] + lens[2])) * lens[1], "rounds": rounds,
+                "reverted": reverted}
