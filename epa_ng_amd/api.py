@@ -114,6 +114,11 @@ def dev_lib():
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(_Stats)]
         L.epa_dev_score_at.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.epa_dev_site_lnl.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.epa_dev_rell_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                           C.c_uint64, C.c_void_p]
         L.epa_dev_set_heuristic.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.epa_dev_set_query_packing.argtypes = [C.c_void_p, C.c_int]
         L.epa_pack_codes_4bit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -438,6 +443,44 @@ class Evaluator:
         self._layout(codes)
         self._check(self.L.epa_dev_score_at(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                             _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(out)))
+        return out
+
+    def site_lnl(self, pairs, pendant, distal, codes, win_begin, win_span, proximal=None, pitch=None, Q=None, out=None):
+        """per-site log-likelihoods of the placements `pairs` at the GIVEN lengths (epa_dev_site_lnl) -> float64
+        [n][pitch]: row i, column j < win_span[seq_id] is the log of the site likelihood at window position j (scaler
+        counts and the +I term included: the row's sum is score_at's lnL), the columns beyond the span are 0.0.
+        pitch None: the longest window (host win_span)."""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
+        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        if pitch is None:
+            pitch = int(np.max(np.asarray(win_span)[:Q])) if Q else 0
+        if out is None:
+            out = np.empty((n, int(pitch)), np.float64)
+        self._layout(codes)
+        self._check(self.L.epa_dev_site_lnl(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                            _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, int(pitch), _ptr(out)))
+        return out
+
+    def rell_support(self, pairs, pendant, distal, codes, win_begin, win_span, replicates, seed=1, stream_id=None,
+                     proximal=None, Q=None, out=None):
+        """RELL bootstrap support (epa_dev_rell_support) -> float64 [n]: the entries of one query compete; support[i]
+        is the fraction of the `replicates` resamplings of the query's sites that entry i wins.  The resampling is
+        specified exactly in include/epa_dev.h (Philox4x32-10, key = seed, stream_id[q] selects the query's stream;
+        None: the query's index)."""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
+        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        if isinstance(stream_id, (np.ndarray, list, tuple)):
+            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
+        if out is None:
+            out = np.empty(n, np.float64)
+        self._layout(codes)
+        self._check(self.L.epa_dev_rell_support(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                                _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
+                                                int(replicates), int(seed), _ptr(out)))
         return out
 
     def set_heuristic(self, mode="dynamic", param=0.0):

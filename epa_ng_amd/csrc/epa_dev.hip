@@ -1594,25 +1594,31 @@ extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_
   return EPA_OK;
 }
 
-extern "C" int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
-                                const double* proximal, uint64_t n, const uint8_t* q_codes,
-                                const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, double* lnl) {
-  if (!ctx || (n && (!pairs || !pendant || !distal || !lnl || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (n == 0) return EPA_OK;
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
+// What epa_dev_score_at, epa_dev_site_lnl and epa_dev_rell_support share: the entries' arguments checked (host arrays;
+// the first offending entry is named after `who`) and staged on the device.  hs: the host's view of win_span.
+struct EntryStage {
   std::vector<uint32_t> hb_buf, hs_buf;
-  const uint32_t* hb = host_view(win_begin, Q, hb_buf, ctx->stream);
-  const uint32_t* hs = host_view(win_span, Q, hs_buf, ctx->stream);
-  if (!hb || !hs) return epa_fail(ctx, EPA_ERR_HIP, "cannot read window arrays");
+  const uint32_t* hs = nullptr;
   uint32_t max_span = 0;
-  int rc = check_windows(ctx, hb, hs, Q, &max_span, true);   // an empty window is the empty sum: lnL 0
+  const uint8_t* d_codes = nullptr;
+  const uint32_t *d_begin = nullptr, *d_span = nullptr;
+  const epa_pair* d_pairs = nullptr;
+  const double *d_pen = nullptr, *d_dis = nullptr, *d_prx = nullptr;
+};
+
+static int stage_entries(epa_ctx* ctx, const char* who, const epa_pair* pairs, const double* pendant, const double* distal,
+                         const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
+                         const uint32_t* win_span, uint32_t Q, EntryStage& st) {
+  const uint32_t* hb = host_view(win_begin, Q, st.hb_buf, ctx->stream);
+  st.hs = host_view(win_span, Q, st.hs_buf, ctx->stream);
+  if (!hb || !st.hs) return epa_fail(ctx, EPA_ERR_HIP, "cannot read window arrays");
+  int rc = check_windows(ctx, hb, st.hs, Q, &st.max_span, true);   // an empty window is the empty sum: lnL 0
   if (rc) return rc;
   // host arrays are validated (device arrays are the caller's responsibility): the first offending entry is named
   const bool hp = !epa_is_device_ptr(pairs), hpe = !epa_is_device_ptr(pendant), hd = !epa_is_device_ptr(distal);
   const bool hx = proximal && !epa_is_device_ptr(proximal);
   auto bad = [&](uint64_t i, const char* what) {
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "score_at: entry " + std::to_string(i) + ": " + what);
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": entry " + std::to_string(i) + ": " + what);
   };
   for (uint64_t i = 0; i < n; ++i) {
     if (hp && pairs[i].branch_id >= ctx->B) return bad(i, "branch id out of range");
@@ -1623,22 +1629,92 @@ extern "C" int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const doubl
     if (!proximal && hp && hd && distal[i] > ctx->h_blen[pairs[i].branch_id])
       return bad(i, "distal length beyond the branch's length");
   }
-  const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
-  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
-  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
-  const epa_pair* d_pairs = (const epa_pair*)epa_to_device(ctx, 4, pairs, sizeof(epa_pair) * n);
-  const double* d_pen = (const double*)epa_to_device(ctx, 7, pendant, sizeof(double) * n);
-  const double* d_dis = (const double*)epa_to_device(ctx, 8, distal, sizeof(double) * n);
-  const double* d_prx = proximal ? (const double*)epa_to_device(ctx, 9, proximal, sizeof(double) * n) : nullptr;
-  if (!d_codes || !d_begin || !d_span || !d_pairs || !d_pen || !d_dis || (proximal && !d_prx))
-    return epa_fail(ctx, EPA_ERR_HIP, "score_at input upload failed");
+  st.d_codes = epa_codes_to_device(ctx, q_codes, Q);
+  st.d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
+  st.d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
+  st.d_pairs = (const epa_pair*)epa_to_device(ctx, 4, pairs, sizeof(epa_pair) * n);
+  st.d_pen = (const double*)epa_to_device(ctx, 7, pendant, sizeof(double) * n);
+  st.d_dis = (const double*)epa_to_device(ctx, 8, distal, sizeof(double) * n);
+  st.d_prx = proximal ? (const double*)epa_to_device(ctx, 9, proximal, sizeof(double) * n) : nullptr;
+  if (!st.d_codes || !st.d_begin || !st.d_span || !st.d_pairs || !st.d_pen || !st.d_dis || (proximal && !st.d_prx))
+    return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                const double* proximal, uint64_t n, const uint8_t* q_codes,
+                                const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, double* lnl) {
+  if (!ctx || (n && (!pairs || !pendant || !distal || !lnl || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (n == 0) return EPA_OK;
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  EntryStage st;
+  int rc = stage_entries(ctx, "score_at", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
+  if (rc) return rc;
   const bool out_dev = epa_is_device_ptr(lnl);
   double* d_lnl = out_dev ? lnl : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
   if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(score_at out)");
-  rc = launch_score_at(ctx, d_pairs, d_pen, d_dis, d_prx, n, d_codes, d_begin, d_span, d_lnl);
+  rc = launch_score_at(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, d_lnl);
   if (rc) return rc;
   if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(lnl, d_lnl, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   // host inputs were staged from pageable memory: they must not change before the copies ran
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
+                                const uint32_t* win_span, uint32_t Q, uint32_t pitch, double* site_lnl) {
+  if (!ctx || (n && (!pairs || !pendant || !distal || !site_lnl || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (n == 0) return EPA_OK;
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  EntryStage st;
+  int rc = stage_entries(ctx, "site_lnl", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
+  if (rc) return rc;
+  // the pitch must hold the longest window among the entries' queries (of all queries when the pairs live on the device)
+  uint32_t need = 0;
+  if (!epa_is_device_ptr(pairs)) for (uint64_t i = 0; i < n; ++i) need = std::max(need, st.hs[pairs[i].seq_id]);
+  else need = st.max_span;
+  if (pitch < need)
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "site_lnl: pitch " + std::to_string(pitch) + " is smaller than the longest window (" +
+                                                  std::to_string(need) + ")");
+  if (pitch == 0) return EPA_OK;   // every window is empty: there is nothing to write
+  const bool out_dev = epa_is_device_ptr(site_lnl);
+  const size_t bytes = sizeof(double) * (size_t)n * pitch;
+  double* d_rows = out_dev ? site_lnl : (double*)epa_scratch(ctx, 3, bytes);
+  if (!d_rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(site_lnl out)");
+  rc = launch_site_lnl(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, nullptr, n, st.d_codes, st.d_begin, st.d_span, pitch,
+                       true, d_rows, true);
+  if (rc) return rc;
+  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(site_lnl, d_rows, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_rell_support(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                    const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
+                                    const uint32_t* win_span, uint32_t Q, const uint64_t* stream_id, uint32_t replicates,
+                                    uint64_t seed, double* support) {
+  if (!ctx || (n && (!pairs || !pendant || !distal || !support || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (replicates == 0 || replicates > (1u << 20))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_support: replicates must be 1 .. 2^20");
+  if (n == 0) return EPA_OK;
+  if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_support: more than 2^32 - 1 entries in one call");
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  EntryStage st;
+  int rc = stage_entries(ctx, "rell_support", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
+  if (rc) return rc;
+  const uint64_t* d_sid = stream_id ? (const uint64_t*)epa_to_device(ctx, 17, stream_id, sizeof(uint64_t) * Q) : nullptr;
+  if (stream_id && !d_sid) return epa_fail(ctx, EPA_ERR_HIP, "rell_support input upload failed");
+  const bool out_dev = epa_is_device_ptr(support);
+  double* d_sup = out_dev ? support : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
+  if (!d_sup) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_support out)");
+  rc = launch_rell(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, st.hs, Q, d_sid,
+                   replicates, seed, d_sup);
+  if (rc) return rc;
+  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(support, d_sup, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return EPA_OK;
 }
@@ -2620,6 +2696,8 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "lookup")) t = &ctx->t_lookup;
   else if (!strcmp(which, "select")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SELECT]][epa_ctx::T_SELECT];
   else if (!strcmp(which, "score_at")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SCORE]][epa_ctx::T_SCORE];
+  else if (!strcmp(which, "site_lnl")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SITES]][epa_ctx::T_SITES];
+  else if (!strcmp(which, "rell")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL]][epa_ctx::T_RELL];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

@@ -205,7 +205,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 13;
+  static constexpr int N_SCRATCH = 18;   // 13 .. 17: epa_dev_rell_support (rell.hip, epa_dev.hip)
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -238,7 +238,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, N_TIMERS = 4 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, N_TIMERS = 6 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -257,7 +257,7 @@ struct epa_ctx {
   // selection (chunk_body_begin: in the shadow of the host's round trip); the launch that uses them clears the mark
   const void* clean_stats[N_BANKS] = {};
   bool clean_ctr[N_BANKS] = {};
-  int t_last[N_TIMERS] = {0, 0, 0, 0};
+  int t_last[N_TIMERS] = {};
   epa_thorough_stats last_stats{};
 };
 
@@ -354,6 +354,18 @@ int launch_thorough_aa_mfma(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_
 int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
                     const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
                     const uint32_t* d_span, double* d_lnl);
+// per-site log-likelihoods of the same entries (k_score_at<S, true>): row i of d_rows [n_rows][pitch] takes entry
+// d_order[i] (null: entry i), columns [0, span); pad: the columns from the span up to the pitch are written as 0.0.
+// timed: records the "site_lnl" timer (the RELL driver times the whole call as "rell" instead)
+int launch_site_lnl(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                    const double* d_proximal, const uint32_t* d_order, uint64_t n_rows, const uint8_t* d_codes,
+                    const uint32_t* d_begin, const uint32_t* d_span, uint32_t pitch, bool pad, double* d_rows,
+                    bool timed);
+// RELL bootstrap support of n entries competing per query (rell.hip); h_span: the host's view of the spans
+int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
+                const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
+                uint32_t replicates, uint64_t seed, double* d_support);
 int launch_select(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold,
                   epa_pair* d_pairs, uint64_t max_pairs, uint64_t* n_pairs,
                   const uint32_t* d_span = nullptr);  // d_span: also histogram the span classes

@@ -72,6 +72,8 @@ struct Options {  // defaults: src/util/Options.hpp:13-34
   bool comm_self_send = false;       // --comm-self-send (test hook): rank 0's own rows travel through ncclSend / ncclRecv
   bool host_heuristic = false;       // --host-heuristic (diagnostic): candidate selection on the host from the Q x B table
   bool no_pipeline = false;          // --no-pipeline (diagnostic): one chunk at a time, no read-ahead / staged slots
+  unsigned int rell_replicates = 0;  // --rell N (with --rescore): RELL bootstrap support from N resamplings; 0: none
+  unsigned long long rell_seed = 1;  // --rell-seed
 };
 
 class Sequence {
@@ -127,9 +129,11 @@ public:
   double distal_length() const { return distal_length_; }
   size_t branch_id() const { return branch_id_; }
   void lwr(double v) { lwr_ = v; }
+  double rell_support() const { return rell_support_; }   // --rescore --rell only
+  void rell_support(double v) { rell_support_ = v; }
 private:
   size_t branch_id_ = 0;
-  double likelihood_ = 0, lwr_ = 0, pendant_length_ = 0, distal_length_ = 0;
+  double likelihood_ = 0, lwr_ = 0, pendant_length_ = 0, distal_length_ = 0, rell_support_ = 0;
 };
 
 class PQuery {  // src/sample/PQuery.hpp:12-92
@@ -367,13 +371,14 @@ private:
 size_t format_fixed(char* buf, size_t cap, double v, unsigned int precision);
 void write_jplace(std::ostream& os, const std::vector<Sample>& chunks, const std::string& newick,
                   const std::string& invocation, unsigned int precision,
-                  const Rtree_Mapper* mapper = nullptr);
+                  const Rtree_Mapper* mapper = nullptr, bool rell = false);
 // the same in two steps: every chunk is turned into text as soon as it is done (by the device
 // worker that produced it), the file is assembled at the end
+// rell: a sixth field "rell_support" (Placement::rell_support) follows pendant_length in every row and in "fields"
 std::string jplace_chunk_text(const Sample& sample, unsigned int precision,
-                              const Rtree_Mapper* mapper = nullptr);
+                              const Rtree_Mapper* mapper = nullptr, bool rell = false);
 void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_texts, const std::string& newick,
-                       const std::string& invocation);
+                       const std::string& invocation, bool rell = false);
 
 // jplace (version 3) reader for --rescore: per placement object its single name ("n": [name] or "nm": [[name,
 // multiplicity]]) and of every row edge_num, distal_length and pendant_length; "fields" may come in any order, every

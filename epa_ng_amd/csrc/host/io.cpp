@@ -665,7 +665,7 @@ std::vector<Jplace_PQuery> read_jplace(const std::string& path) {
 // One chunk of the "placements" array as text (sample_to_jplace_string, src/io/jplace_util.cpp:
 // 60-98): formatted per pquery in parallel with snprintf into per-thread strings, then joined.
 // Numbers are fixed-point with `precision` digits like the reference's stream settings.
-std::string jplace_chunk_text(const Sample& sample, unsigned int precision, const Rtree_Mapper* mapper) {
+std::string jplace_chunk_text(const Sample& sample, unsigned int precision, const Rtree_Mapper* mapper, bool rell) {
   const bool remap = mapper && (bool)*mapper;  // placement_to_jplace_string, jplace_util.cpp:20-26
   const int nt_max = std::max(1, configure_host_threads());
   const long n = (long)sample.size();
@@ -678,7 +678,7 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
     const long i0 = n * t / nthr, i1 = n * (t + 1) / nthr;
     std::string& o = part[(size_t)t];
     size_t est = 0;
-    for (long i = i0; i < i1; ++i) est += 48 + sample[i].header().size() + sample[i].size() * (24 + 4 * (size_t)(precision + 12));
+    for (long i = i0; i < i1; ++i) est += 48 + sample[i].header().size() + sample[i].size() * (24 + (rell ? 5 : 4) * (size_t)(precision + 12));
     o.reserve(est);
     char line[1024];
     for (long i = i0; i < i1; ++i) {
@@ -696,8 +696,8 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
         char* w = line;
         std::memcpy(w, "      [", 7); w += 7;
         w = std::to_chars(w, line + 64, edge).ptr;
-        const double vals[4] = {p.likelihood(), p.lwr(), distal, p.pendant_length()};
-        for (int k = 0; k < 4; ++k) {
+        const double vals[5] = {p.likelihood(), p.lwr(), distal, p.pendant_length(), p.rell_support()};
+        for (int k = 0; k < (rell ? 5 : 4); ++k) {
           *w++ = ','; *w++ = ' ';
           w += format_fixed(w, (size_t)(line + sizeof(line) - w) - 8, vals[k], precision);
         }
@@ -723,7 +723,7 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
 }
 
 void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_texts, const std::string& newick,
-                       const std::string& invocation) {
+                       const std::string& invocation, bool rell) {
   os << "{\n  \"tree\": \"" << newick << "\",\n  \"placements\": \n  [\n";
   bool first_chunk = true;
   for (const auto& t : chunk_texts) {
@@ -734,15 +734,15 @@ void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_t
   }
   os << "  ],\n  \"metadata\": {\"invocation\": \"" << invocation << "\"},\n  \"version\": 3,\n"
      << "  \"fields\": [\"edge_num\", \"likelihood\", \"like_weight_ratio\", \"distal_length\""
-     << ", \"pendant_length\"]\n}\n";
+     << ", \"pendant_length\"" << (rell ? ", \"rell_support\"" : "") << "]\n}\n";
 }
 
 void write_jplace(std::ostream& os, const std::vector<Sample>& chunks, const std::string& newick,
-                  const std::string& invocation, unsigned int precision, const Rtree_Mapper* mapper) {
+                  const std::string& invocation, unsigned int precision, const Rtree_Mapper* mapper, bool rell) {
   std::vector<std::string> texts;
   texts.reserve(chunks.size());
-  for (const auto& sample : chunks) texts.push_back(jplace_chunk_text(sample, precision, mapper));
-  write_jplace_text(os, texts, newick, invocation);
+  for (const auto& sample : chunks) texts.push_back(jplace_chunk_text(sample, precision, mapper, rell));
+  write_jplace_text(os, texts, newick, invocation, rell);
 }
 
 }  // namespace epa

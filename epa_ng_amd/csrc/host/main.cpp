@@ -30,6 +30,10 @@ static void usage() {
       "                        pendant_length of every row) again under this tree, alignment and model; likelihood and\n"
       "                        like_weight_ratio are recomputed, everything else is kept.  No heuristic, optimiser or\n"
       "                        filter flag applies (they are refused); one device; --preserve-rooting off for rooted trees\n"
+      "  --rell N              with --rescore: RELL bootstrap support of every row among the rows of its placement object,\n"
+      "                        from N (1 .. 1048576) resamplings of the per-site log-likelihoods; written as a sixth\n"
+      "                        field \"rell_support\".  Two steps: place first, then --rescore out.jplace --rell N\n"
+      "  --rell-seed S         seed of the resampling (default 1); the result depends on N, S and the input file alone\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -64,7 +68,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> placing_flags;   // flags that steer heuristic, optimiser or filter: meaningless with --rescore
   Options opt;
   int device = 0;
-  bool device_given = false;
+  bool device_given = false, rell_given = false;
   std::vector<int> devices;
   // one process per GPU (place_ranks.cpp): --rank / --world / --comm-file, or what torchrun / mpirun export
   auto env_int = [](const char* a, const char* b, int dflt) {
@@ -100,6 +104,8 @@ int main(int argc, char** argv) {
     else if (a == "--filter-min") opt.filter_min = (unsigned)std::stoul(need(i));
     else if (a == "--filter-max") opt.filter_max = (unsigned)std::stoul(need(i));
     else if (a == "--rescore") rescore_file = need(i);
+    else if (a == "--rell") { opt.rell_replicates = (unsigned)std::stoul(need(i)); rell_given = true; }
+    else if (a == "--rell-seed") { opt.rell_seed = std::stoull(need(i)); rell_given = true; }
     else if (a == "--precision") opt.precision = (unsigned)std::stoul(need(i));
     else if (a == "--chunk-size") { opt.chunk_size = (unsigned)std::stoul(need(i)); opt.chunk_size_given = true; }
     else if (a == "--device-min-chunk") { opt.device_min_chunk = (unsigned)std::stoul(need(i)); opt.device_min_chunk_given = true; }
@@ -161,6 +167,15 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (opt.filter_min > opt.filter_max) { std::cerr << "filter-min must not exceed filter-max!\n"; return 1; }
+  if (rell_given && rescore_file.empty()) {
+    std::cerr << "--rell / --rell-seed work on an existing result: place first, then run again with "
+                 "--rescore out.jplace --rell N\n";
+    return 1;
+  }
+  if (rell_given && (opt.rell_replicates == 0 || opt.rell_replicates > (1u << 20))) {
+    std::cerr << "--rell: the number of replicates must be 1 .. 1048576 (--rell-seed needs --rell N)\n";
+    return 1;
+  }
   if (!rescore_file.empty()) {   // what --rescore does not do is refused, not silently ignored
     if (!placing_flags.empty()) {
       std::cerr << "--rescore evaluates the file's placements as they are: " << placing_flags[0]

@@ -1,7 +1,9 @@
 // --rescore FILE.jplace: the placements of an existing jplace evaluated again at their own branch lengths under
 // this run's tree, alignment and model.  The device call is epa_dev_score_at (Tiny_Tree::place with opt_branches ==
 // false, src/tree/Tiny_Tree.cpp:186-204); the chunk loop around it reads the query file like simple_mpi (place.cpp)
-// does -- same reader, same premasking -- and picks the sequences the jplace names.
+// does -- same reader, same premasking -- and picks the sequences the jplace names.  With --rell N the same rows also
+// get their RELL bootstrap support (epa_dev_rell_support) among the rows of their placement object; the object's index
+// in the input file is its random stream, so the result does not depend on --chunk-size.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -113,11 +115,25 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
                                     lnl.data());
     if (rc != EPA_OK)
       throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+    std::vector<double> support;
+    if (options.rell_replicates) {
+      std::vector<uint64_t> stream_id(target.begin(), target.end());
+      support.resize(pairs.size());
+      const int rrc = epa_dev_rell_support(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
+                                           enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
+                                           stream_id.data(), options.rell_replicates, options.rell_seed, support.data());
+      if (rrc != EPA_OK)
+        throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rrc) + ")"};
+    }
     st.seconds_place += std::chrono::duration<double>(clk::now() - ts).count();
     size_t k = 0;
     for (size_t q = 0; q < named.size(); ++q) {
       PQuery pq(target[q], named[q].header());
-      for (const Jplace_Row& r : input[target[q]].rows) pq.emplace_back(r.edge_num, lnl[k++], r.pendant_length, r.distal_length);
+      for (const Jplace_Row& r : input[target[q]].rows) {
+        pq.emplace_back(r.edge_num, lnl[k], r.pendant_length, r.distal_length);
+        if (!support.empty()) pq[pq.size() - 1].rell_support(support[k]);
+        ++k;
+      }
       sample[target[q]] = std::move(pq);
     }
     st.queries += named.size();
@@ -139,7 +155,8 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
   const std::string out_path = dir + "epa_result.jplace";
   std::ofstream os(out_path);
   if (!os) throw std::runtime_error{"cannot open " + out_path};
-  write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision);
+  write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision, nullptr,
+               options.rell_replicates != 0);
   os.flush();
   if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }
   st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();

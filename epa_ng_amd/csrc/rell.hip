@@ -1,0 +1,271 @@
+// RELL bootstrap support of placements (resampling of estimated log-likelihoods): per query the site log-likelihoods
+// of its competing placements are resampled with replacement `replicates` times; the support of a placement is the
+// fraction of replicates it wins.  The per-site values come from k_score_at<S, true> (score_at.hip).
+//
+// The resampling is specified exactly (include/epa_dev.h, epa_dev_rell_support), so that a result can be reproduced
+// anywhere:
+//   generator  Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments
+//              0x9E3779B9 / 0xBB67AE85), key = (seed low word, seed high word)
+//   draws      replicate r of a query with stream id t and span n_q makes n_q draws; draw d uses output word d % 4 of
+//              counter (d / 4, r, t low word, t high word); the drawn site is j = (word * n_q) >> 32
+//   score      starts at 0.0 and adds, for d = 0 .. n_q - 1 in this order, the entry's site value at the drawn j:
+//              plain fp64 adds, no centring, no reassociation
+//   winner     the largest score; ties go to the smaller branch id, then to the smaller entry index
+//
+// Host side (launch_rell): the entries are grouped by query with a stable radix sort of their indices, so a group
+// keeps the caller's entry order; the groups are worked off in batches of whole queries whose site rows fit a fixed
+// scratch budget (one query alone may exceed it: its rows are then allocated as they are).
+//
+// k_rell: one 256-thread workgroup per query, thread = replicate (in rounds of 256).  The entries are taken in tiles
+// of TE = 4: the tile's [site][4] matrix is staged in LDS (32 bytes per site: a draw reads its four values with two
+// ds_read_b128), every thread regenerates the same draws for every tile -- the point of a counter-based generator --
+// and carries its running best (score, branch, position) across the tiles.  A window longer than LDS_SITES does not
+// fit the LDS tile; its draws gather from the rows in HBM / L2 instead.  Wins are counted with LDS atomics for up to
+// WINS_LDS entries per query, beyond that with global atomics.
+#include "epa_dev_internal.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <vector>
+
+// digit passes, never rocprim's merge-sort fallback (thorough_dna.hip)
+using epa_radix_cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
+                                                 rocprim::default_config, 0>;
+
+namespace {
+
+constexpr int RELL_THREADS = 256;
+constexpr int TE = 4;                    // entries per tile
+constexpr uint32_t LDS_SITES = 1536;     // 1536 sites x 4 entries x 8 B = 48 KiB
+constexpr uint32_t WINS_LDS = 1024;      // entries per query whose wins are counted in LDS
+constexpr size_t ROWS_BUDGET = (size_t)128 << 20;   // bytes of site rows per batch
+
+struct RellGroup {
+  uint32_t q, start, count;   // query, first sorted position, entries
+};
+
+struct RellArgs {
+  const RellGroup* groups;
+  uint32_t n_groups;
+  const uint32_t* order;      // sorted position -> entry
+  const epa_pair* pairs;
+  const uint32_t* span;
+  const uint64_t* stream_id;  // null: the query's index
+  const double* rows;         // [batch positions][pitch], row = position - pos0
+  uint32_t pos0, pitch;
+  uint32_t R, k0, k1;
+  uint32_t* wins;             // [n] by sorted position
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__global__ void __launch_bounds__(256) k_rell_keys(const epa_pair* __restrict__ pairs, uint32_t n,
+                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  keys[i] = pairs[i].seq_id;
+  idx[i] = i;
+}
+
+// first and one-past-last sorted position of every query that has entries (bounds [2][Q], zeroed before)
+__global__ void __launch_bounds__(256) k_rell_bounds(const uint32_t* __restrict__ sorted, uint32_t n, uint32_t Q,
+                                                     uint32_t* __restrict__ bounds) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t q = sorted[i];
+  if (q >= Q) return;
+  if (i == 0 || sorted[i - 1] != q) bounds[q] = i;
+  if (i + 1 == n || sorted[i + 1] != q) bounds[Q + q] = i + 1;
+}
+
+__global__ void __launch_bounds__(256) k_rell_support(const uint32_t* __restrict__ wins, const uint32_t* __restrict__ order,
+                                                      uint32_t n, double R, double* __restrict__ support) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) support[order[i]] = (double)wins[i] / R;
+}
+
+__global__ void __launch_bounds__(RELL_THREADS) k_rell(const RellArgs a) {
+  __shared__ __attribute__((aligned(16))) double mat[LDS_SITES * TE];   // [site][TE]
+  __shared__ uint32_t wins_l[WINS_LDS];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+    const RellGroup grp = a.groups[g];
+    const uint32_t E = grp.count, nq = a.span[grp.q];
+    const uint64_t t = a.stream_id ? a.stream_id[grp.q] : (uint64_t)grp.q;
+    const uint32_t tlo = (uint32_t)t, thi = (uint32_t)(t >> 32);
+    const double* __restrict__ rows = a.rows + (size_t)(grp.start - a.pos0) * a.pitch;
+    const uint32_t* __restrict__ ord = a.order + grp.start;
+    const bool in_lds = nq <= LDS_SITES, wins_lds = E <= WINS_LDS;   // workgroup-uniform
+    const uint32_t ntiles = (E + TE - 1) / TE;
+    __syncthreads();   // the previous query's tile and counters are no longer read
+    if (wins_lds)
+      for (uint32_t i = tid; i < E; i += RELL_THREADS) wins_l[i] = 0;
+    __syncthreads();
+    for (uint32_t rbase = 0; rbase < a.R; rbase += RELL_THREADS) {
+      const uint32_t r = rbase + tid;
+      const bool active = r < a.R;
+      double best_sc = 0.0;
+      uint32_t best_br = 0, best_k = 0;
+      for (uint32_t tile = 0; tile < ntiles; ++tile) {
+        const uint32_t e0 = tile * TE, te = min((uint32_t)TE, E - e0);
+        // a query of one tile keeps it for all rounds of replicates; more tiles are staged again every round
+        if (in_lds && (ntiles > 1 || rbase == 0)) {
+          __syncthreads();
+          for (uint32_t i = tid; i < nq * TE; i += RELL_THREADS) {
+            const uint32_t k = i / nq, j = i - k * nq;   // consecutive threads read consecutive sites of one row
+            mat[j * TE + k] = k < te ? rows[(size_t)(e0 + k) * a.pitch + j] : 0.0;
+          }
+          __syncthreads();
+        }
+        if (!active) continue;
+        double sc[TE];
+#pragma unroll
+        for (int k = 0; k < TE; ++k) sc[k] = 0.0;
+        for (uint32_t d = 0; d < nq; d += 4) {
+          uint32_t w[4];
+          philox4x32_10(d >> 2, r, tlo, thi, a.k0, a.k1, w);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (d + u < nq) {
+              const uint32_t j = __umulhi(w[u], nq);
+              if (in_lds) {
+#pragma unroll
+                for (int k = 0; k < TE; ++k) sc[k] += mat[j * TE + k];   // padded entries add 0.0 to unused scores
+              } else {
+#pragma unroll
+                for (int k = 0; k < TE; ++k)
+                  if ((uint32_t)k < te) sc[k] += rows[(size_t)(e0 + k) * a.pitch + j];
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < TE; ++k) {
+          if ((uint32_t)k < te) {
+            const uint32_t br = a.pairs[ord[e0 + k]].branch_id;
+            // positions of a group ascend with the entry index (stable sort): an equal branch keeps the earlier entry
+            if ((tile == 0 && k == 0) || sc[k] > best_sc || (sc[k] == best_sc && br < best_br)) {
+              best_sc = sc[k];
+              best_br = br;
+              best_k = e0 + k;
+            }
+          }
+        }
+      }
+      if (active) {
+        if (wins_lds) atomicAdd(&wins_l[best_k], 1u);
+        else atomicAdd(&a.wins[grp.start + best_k], 1u);
+      }
+    }
+    __syncthreads();
+    if (wins_lds)
+      for (uint32_t i = tid; i < E; i += RELL_THREADS) a.wins[grp.start + i] = wins_l[i];
+  }
+}
+
+}  // namespace
+
+int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
+                const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
+                uint32_t replicates, uint64_t seed, double* d_support) {
+  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32
+  const dim3 ngrid((n + 255) / 256);
+  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL));
+  // ---- group by query: stable sort of the entry indices by seq_id
+  int bits = 1;
+  while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)Q) ++bits;
+  size_t temp_bytes = 0;
+  (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                 (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0, bits, ctx->stream);
+  const size_t nb = (sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255;
+  // scratch 13: [keys n | idx n | sorted keys n | order n | wins n | rocprim temp]
+  char* base = (char*)epa_scratch(ctx, 13, 5 * nb + temp_bytes);
+  uint32_t* d_bounds = (uint32_t*)epa_scratch(ctx, 14, sizeof(uint32_t) * 2 * (size_t)Q);
+  if (!base || !d_bounds) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell grouping)");
+  uint32_t *d_keys = (uint32_t*)base, *d_idx = (uint32_t*)(base + nb), *d_sorted = (uint32_t*)(base + 2 * nb);
+  uint32_t *d_order = (uint32_t*)(base + 3 * nb), *d_wins = (uint32_t*)(base + 4 * nb);
+  void* temp = base + 5 * nb;
+  hipLaunchKernelGGL(k_rell_keys, ngrid, dim3(256), 0, ctx->stream, d_pairs, n, d_keys, d_idx);
+  EPA_HIP(ctx, rocprim::radix_sort_pairs<epa_radix_cfg>(temp, temp_bytes, d_keys, d_sorted, d_idx, d_order, (size_t)n, 0, bits,
+                                                        ctx->stream));
+  EPA_HIP(ctx, hipMemsetAsync(d_bounds, 0, sizeof(uint32_t) * 2 * (size_t)Q, ctx->stream));
+  EPA_HIP(ctx, hipMemsetAsync(d_wins, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+  hipLaunchKernelGGL(k_rell_bounds, ngrid, dim3(256), 0, ctx->stream, d_sorted, n, Q, d_bounds);
+  std::vector<uint32_t> bounds(2 * (size_t)Q);
+  EPA_HIP(ctx, hipMemcpyAsync(bounds.data(), d_bounds, sizeof(uint32_t) * 2 * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<RellGroup> groups;
+  uint64_t covered = 0;
+  for (uint32_t q = 0; q < Q; ++q)
+    if (bounds[Q + q] > bounds[q]) {
+      groups.push_back(RellGroup{q, bounds[q], bounds[Q + q] - bounds[q]});
+      covered += groups.back().count;
+    }
+  if (covered != n) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_support: a sequence id is out of range");
+  RellGroup* d_groups = (RellGroup*)epa_scratch(ctx, 15, sizeof(RellGroup) * groups.size());
+  if (!d_groups) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell groups)");
+  EPA_HIP(ctx, hipMemcpyAsync(d_groups, groups.data(), sizeof(RellGroup) * groups.size(), hipMemcpyHostToDevice, ctx->stream));
+
+  // ---- batches of whole queries: rows [positions][pitch], pitch = the batch's longest window
+  RellArgs a;
+  a.order = d_order;
+  a.pairs = d_pairs;
+  a.span = d_span;
+  a.stream_id = d_stream_id;
+  a.R = replicates;
+  a.k0 = (uint32_t)seed;
+  a.k1 = (uint32_t)(seed >> 32);
+  a.wins = d_wins;
+  struct Batch { size_t g0, g1; uint64_t rows; uint32_t pitch; };
+  std::vector<Batch> batches;
+  size_t rows_bytes = 0;
+  for (size_t g0 = 0; g0 < groups.size();) {
+    Batch b{g0, g0, 0, 1};
+    while (b.g1 < groups.size()) {
+      const uint32_t p = std::max(b.pitch, h_span[groups[b.g1].q]);
+      if (b.g1 > g0 && (b.rows + groups[b.g1].count) * (uint64_t)p * sizeof(double) > ROWS_BUDGET) break;
+      b.rows += groups[b.g1].count;
+      b.pitch = p;
+      ++b.g1;
+    }
+    rows_bytes = std::max(rows_bytes, (size_t)b.rows * b.pitch * sizeof(double));
+    batches.push_back(b);
+    g0 = b.g1;
+  }
+  double* d_rows = (double*)epa_scratch(ctx, 16, rows_bytes);
+  if (!d_rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell site rows)");
+  for (const Batch& b : batches) {
+    const uint32_t pos0 = groups[b.g0].start;
+    int rc = launch_site_lnl(ctx, d_pairs, d_pendant, d_distal, d_proximal, d_order + pos0, b.rows, d_codes, d_begin, d_span,
+                             b.pitch, false, d_rows, false);
+    if (rc) return rc;
+    a.groups = d_groups + b.g0;
+    a.n_groups = (uint32_t)(b.g1 - b.g0);
+    a.rows = d_rows;
+    a.pos0 = pos0;
+    a.pitch = b.pitch;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(a.n_groups, (uint64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(k_rell, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, a);
+    EPA_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_rell_support, ngrid, dim3(256), 0, ctx->stream, d_wins, d_order, n, (double)replicates, d_support);
+  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL));
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}

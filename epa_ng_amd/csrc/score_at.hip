@@ -8,6 +8,8 @@
 // -- the kernel serves the resident and the blocked lookup layout alike and every shape a context can have (4 / 20
 // states, 1 .. EPA_MAX_CATS categories with padded ones at weight 0, +I, both scaler modes after k_align_rates,
 // verbatim eigenvalues).
+// The SITES instantiation (epa_dev_site_lnl, the site rows of epa_dev_rell_support) stores the per-site terms of that
+// lnL instead of their sum.
 //
 // One wavefront per entry, lane = site of the window (runtime loop over 64-site chunks), a persistent grid over the
 // entries.  Per entry the wave keeps exp(lam_x r_k t) for the distal, the proximal and (times w_k) the pendant length
@@ -39,6 +41,11 @@ struct ScArgs {
   double* lnl;
   uint64_t n;
   uint32_t W;
+  // SITES instantiation only: row i of `rows` ([n][pitch]) takes entry order[i] (null: entry i)
+  const uint32_t* order;
+  double* rows;
+  uint32_t pitch;
+  uint32_t pad;            // 1: the columns from the span up to the pitch are written as 0.0
 };
 
 constexpr double LN2 = 0.6931471805599453094;
@@ -51,7 +58,9 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int S>
+// SITES: instead of the entry's lnL the kernel stores what it is the sum of -- per lane log(l0) - 256 count ln 2, one
+// coalesced 512-byte store per 64-site chunk -- into row i of a.rows; the lnL instantiation is the code it was.
+template <int S, bool SITES>
 __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
   __shared__ __attribute__((aligned(16))) double U[S * S];
   __shared__ __attribute__((aligned(16))) double UiT[S * S];   // [i][x] = U^-1[x][i]
@@ -64,7 +73,9 @@ __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
   const size_t cW = a.W;
   constexpr int UNROLL_I = S == 4 ? 4 : 1;
 
-  for (uint64_t e = blockIdx.x; e < a.n; e += gridDim.x) {
+  for (uint64_t row = blockIdx.x; row < a.n; row += gridDim.x) {
+    uint64_t e = row;
+    if constexpr (SITES) { if (a.order) e = a.order[row]; }
     const epa_pair pr = a.pairs[e];
     const uint32_t b = pr.branch_id, q = pr.seq_id;
     const uint32_t begin = a.win_begin[q], n = a.win_span[q];
@@ -146,23 +157,31 @@ __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
       if (all_small) { l0 *= 0x1p+256; ++count; }
       if (a.cinv)   // +I: p * pi_inv enters L_0 only, unscaled (thorough_generic.hip)
         l0 = fma(a.cinv[begin + s] * a.inv_w0, tab[2][0], l0);
+      if constexpr (SITES) {
+        if (valid) a.rows[row * a.pitch + site] = log(l0) - (double)(256 * (int)count) * LN2;
+        continue;
+      }
       if (!valid) { l0 = 1.0; count = 0; }
       mant *= __builtin_amdgcn_frexp_mant(l0);
       ex += __builtin_amdgcn_frexp_exp(l0) - 256 * (int)count;
       ex += __builtin_amdgcn_frexp_exp(mant);
       mant = __builtin_amdgcn_frexp_mant(mant);
     }
-    const double lnl = wave_sum(log(mant) + (double)ex * LN2);
-    if (lane == 0) a.lnl[e] = lnl;
+    if constexpr (SITES) {
+      if (a.pad)
+        for (uint32_t j = n + lane; j < a.pitch; j += 64) a.rows[row * a.pitch + j] = 0.0;
+    } else {
+      const double lnl = wave_sum(log(mant) + (double)ex * LN2);
+      if (lane == 0) a.lnl[e] = lnl;
+    }
   }
 }
 
 }  // namespace
 
-int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                    const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                    const uint32_t* d_span, double* d_lnl) {
-  ScArgs a;
+static void fill_args(epa_ctx* ctx, ScArgs& a, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                      const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
+                      const uint32_t* d_span) {
   a.m = ctx->dmodel;
   a.refT = ctx->refT;
   a.scSum = ctx->scSum;
@@ -178,15 +197,46 @@ int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_penda
   a.cstride = a.crel ? ctx->code_stride : ctx->W;
   a.win_begin = d_begin;
   a.win_span = d_span;
-  a.lnl = d_lnl;
+  a.lnl = nullptr;
   a.n = n;
   a.W = ctx->W;
+  a.order = nullptr;
+  a.rows = nullptr;
+  a.pitch = 0;
+  a.pad = 0;
+}
+
+int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                    const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
+                    const uint32_t* d_span, double* d_lnl) {
+  ScArgs a;
+  fill_args(ctx, a, d_pairs, d_pendant, d_distal, d_proximal, n, d_codes, d_begin, d_span);
+  a.lnl = d_lnl;
   // persistent grid: neither n nor a branch id reaches a grid dimension
   const uint32_t grid = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->n_cu * 8);
   epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_SCORE));
-  if (ctx->s == 4) hipLaunchKernelGGL(k_score_at<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_score_at<20>, dim3(grid), dim3(64), 0, ctx->stream, a);
+  if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_score_at<20, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
   epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_SCORE));
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}
+
+int launch_site_lnl(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                    const double* d_proximal, const uint32_t* d_order, uint64_t n_rows, const uint8_t* d_codes,
+                    const uint32_t* d_begin, const uint32_t* d_span, uint32_t pitch, bool pad, double* d_rows,
+                    bool timed) {
+  ScArgs a;
+  fill_args(ctx, a, d_pairs, d_pendant, d_distal, d_proximal, n_rows, d_codes, d_begin, d_span);
+  a.order = d_order;
+  a.rows = d_rows;
+  a.pitch = pitch;
+  a.pad = pad ? 1u : 0u;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(n_rows, (uint64_t)ctx->n_cu * 8);
+  if (timed) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_SITES));
+  if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_score_at<20, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  if (timed) epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_SITES));
   EPA_HIP(ctx, hipGetLastError());
   return EPA_OK;
 }

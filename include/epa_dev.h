@@ -387,6 +387,53 @@ int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const double* pendant,
                      double* lnl);
 
 /*
+ * Per-site log-likelihoods of the same entries: what epa_dev_score_at sums.  Arguments, validation, the host-or-device
+ * pointer rule and query staging are epa_dev_score_at's.  site_lnl is [n][pitch] doubles: row i, column j <
+ * win_span[seq_id] holds the log of the site likelihood at window position j of entry i's query (the scaler counts
+ * included as -256 count ln 2, the +I term included); the columns from the span up to pitch are exactly 0.0, an entry
+ * on a query with win_span == 0 gets an all-zero row.  pitch smaller than the longest window among the entries' queries
+ * (pairs on the device: among all Q queries) is EPA_ERR_INVALID_ARG; n == 0 returns EPA_OK.
+ * The kernel is k_score_at with one store per lane in place of the product over the sites: the same noise cut, tables
+ * and operand order, so a row's sum is score_at's lnL up to the rounding of the sum, and the same bits come out of the
+ * resident and the blocked lookup layout.  Timer: "site_lnl".
+ */
+int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                     const double* proximal /* may be NULL */, uint64_t n,
+                     const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                     uint32_t pitch, double* site_lnl /* [n][pitch] */);
+
+/*
+ * RELL bootstrap support (resampling of estimated log-likelihoods).  The entries (as for epa_dev_score_at) of one query
+ * compete, in any order -- branch-major as the chunk body emits them is the normal case: the query's sites are resampled
+ * with replacement `replicates` times, every replicate is won by the entry with the largest resampled lnL, and
+ * support[i] = (replicates entry i wins) / replicates, so the supports of a query add up to 1.
+ * The resampling is specified exactly; a restatement anywhere reaches the same counts from the same site values:
+ *   generator  Philox4x32-10 with the Random123 constants: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl increments
+ *              0x9E3779B9 and 0xBB67AE85; key = (seed low word, seed high word).  Known answers (counter / key -> output):
+ *                0 0 0 0 / 0 0                                                   -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *                ffffffff x 4 / ffffffff x 2                                     -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *                243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0         -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   draws      replicate r of a query with stream id t and span n_q makes n_q draws; draw d uses output word d % 4 of
+ *              counter (d / 4, r, t low word, t high word); the drawn site is j = (word * n_q) >> 32 (a bias of at
+ *              most n_q / 2^32, accepted)
+ *   score      an entry's score starts at 0.0 and adds, for d = 0 .. n_q - 1 in this order, its site value
+ *              (epa_dev_site_lnl) at the drawn j: plain fp64 adds, no centring, no reassociation
+ *   winner     the largest score; ties go to the smaller branch_id, then to the smaller entry index
+ *   span 0     every score is 0.0: the tie rule gives the whole support to one entry
+ * stream_id: [Q] (host or device), or NULL = the query's index seq_id.  A caller that splits its queries over several
+ * calls passes ids that do not depend on the split (epa-ng-amd --rescore: the placement object's index in the file).
+ * replicates: 1 .. 2^20, else EPA_ERR_INVALID_ARG; other errors as epa_dev_score_at (pairs on the device: a seq_id >= Q
+ * is found and refused).  n < 2^32 per call; no bound on the entries per query or on the span.  The site rows live in
+ * device scratch in batches of whole queries of at most 128 MiB (one query whose rows are larger is a batch alone).
+ * Timer: "rell" (grouping, site rows and resampling together).
+ */
+int epa_dev_rell_support(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                         const double* proximal /* may be NULL */, uint64_t n,
+                         const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                         const uint64_t* stream_id /* [Q] or NULL = seq_id */,
+                         uint32_t replicates, uint64_t seed, double* support /* [n] */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -623,7 +670,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
