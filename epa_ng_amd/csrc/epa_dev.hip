@@ -1825,7 +1825,7 @@ static int chunk_body_end(epa_ctx* ctx, SelectPending* sp, const uint8_t* d_code
   *n_out = n;
   // the queued launch ran iff all n pairs are of its class (no overflow / window error: checked above) -- the test
   // k_thorough_dna applied to the same block
-  if (sp->queued_cls >= 0 && sp->rb[9 + sp->queued_cls] == (uint32_t)n) { ctx->cls_hist_pairs = 0; return EPA_OK; }
+  if (sp->queued_cls >= 0 && sp->rb[9 + sp->queued_cls] == (uint32_t)n) return EPA_OK;
   if (ctx->clean_stats[ctx->bank] == d_stats && sp->queued_cls < 0) ctx->clean_stats[ctx->bank] = nullptr;   // cleared behind the selection
   else {
     ctx->clean_stats[ctx->bank] = nullptr;
@@ -1833,7 +1833,9 @@ static int chunk_body_end(epa_ctx* ctx, SelectPending* sp, const uint8_t* d_code
     if (rc) return rc;
   }
   if (n == 0) return EPA_OK;
-  return launch_thorough(ctx, d_pairs, n, d_codes, d_begin, d_span, max_span, d_res, d_stats);
+  // the selection's class histogram travels in *sp: it describes these n pairs and nothing else
+  return launch_thorough(ctx, d_pairs, n, d_codes, d_begin, d_span, max_span, d_res, d_stats,
+                         sp->have_hist ? sp->cls_hist : nullptr);
 }
 
 static int chunk_body(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span,
@@ -2541,7 +2543,6 @@ extern "C" int epa_dev_place_all(epa_ctx* ctx, const uint8_t* q_codes, const uin
   ctx->d_status = nullptr;
   EPA_HIP(ctx, hipMemsetAsync(d_stats, 0, 256, ctx->stream));
   hipLaunchKernelGGL(k_all_pairs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_all, ctx->B, Q);
-  ctx->cls_hist_pairs = 0;
   rc = launch_thorough(ctx, d_all, n, d_codes, d_begin, d_span, max_span, d_res, d_stats);
   if (rc) return rc;
   // filtered output: Q x filter_max slots, staged in scratch 3 when the caller's buffers are on the host

@@ -78,6 +78,11 @@ struct SelectPending {
   const uint32_t* d_rb = nullptr;  // the packed read-back block on the device (bitmap form)
   bool emitted = false;            // k_emit_pairs (guarded by the total) is already queued behind the read-back
   int queued_cls = -1;             // >= 0: a thorough launch for this span class is queued too (launch_thorough_queued)
+  // span-class histogram of the pairs this selection emitted (launch_select_end, when d_span was given): handed to the
+  // launch_thorough of the SAME chunk body (chunk_body_end), which saves that launch's device round trip.  It lives
+  // and dies with the selection: nothing in epa_ctx remembers it, so no other call can be partitioned by it
+  uint32_t cls_hist[16] = {};
+  bool have_hist = false;
   const uint32_t* pre_status = nullptr;   // window-validation words of THIS chunk's preplacement (ctx->d_status may belong
                                           // to another pipeline slot by the time a widened re-run packs the read-back)
 };
@@ -213,10 +218,7 @@ struct epa_ctx {
   size_t scratch_sz[N_BANKS * N_SCRATCH] = {};
 
   uint32_t* d_status = nullptr;   // window-validation words of the last preplace (in scratch 6)
-  // span-class histogram of the candidate pairs of the last select (valid for the thorough call
-  // that follows it in the fused path: saves one device round trip)
-  uint32_t cls_hist[16] = {};
-  uint64_t cls_hist_pairs = 0;  // 0 = not valid
+  // (the span-class histogram of a selection's pairs is NOT context state: SelectPending::cls_hist)
   uint32_t select_cap = 64;       // staging slots per query of the candidate selection
   uint32_t* th_ctr = nullptr;  // work counters of the thorough kernel (one per XCD slice): 256 B per bank,
                                // [0, 64) the counters, [128, 256) the fused chunk's statistics
@@ -335,7 +337,8 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
 int preplace_check_status(epa_ctx* ctx);
 int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, const uint8_t* d_codes,
                     const uint32_t* d_begin, const uint32_t* d_span, uint32_t max_span,
-                    epa_result* d_out, unsigned long long* d_stats);
+                    epa_result* d_out, unsigned long long* d_stats,
+                    const uint32_t* cls_hist = nullptr);   // [EPA_N_CLS] span classes of exactly these pairs, or null: counted here
 int launch_thorough_queued(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* d_spec, uint64_t max_pairs,
                            const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, uint32_t max_span,
                            epa_result* d_out, unsigned long long* d_stats);

@@ -2093,7 +2093,7 @@ int preplace_check_status(epa_ctx* ctx) {
 //          compaction, the stable sort into Work order and the key -> pair conversion.
 int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold, epa_pair* d_pairs,
                         uint64_t max_pairs, const uint32_t* d_span, uint32_t* rb, SelectPending* sp) {
-  ctx->cls_hist_pairs = 0;
+  sp->have_hist = false;
   const uint32_t B = ctx->B;
   const uint32_t pitch = ctx->lnl_pitch ? ctx->lnl_pitch : B;  // row pitch of d_lnl in doubles
   if (!sp->rerun) sp->pre_status = (const uint32_t*)ctx->d_status;
@@ -2277,9 +2277,9 @@ int launch_select_end(epa_ctx* ctx, SelectPending* sp, uint64_t* n_pairs) {
     if (!sp->emitted) epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_SELECT));   // (else stopped behind the queued k_emit_pairs)
     EPA_HIP(ctx, hipGetLastError());
     *n_pairs = total;
-    if (sp->d_span) {
-      for (int c = 0; c < EPA_N_CLS; ++c) ctx->cls_hist[c] = hst[8 + c];
-      ctx->cls_hist_pairs = total;
+    if (sp->d_span) {   // the selected pairs' span classes, for the Newton launch of this chunk body only
+      for (int c = 0; c < EPA_N_CLS; ++c) sp->cls_hist[c] = hst[8 + c];
+      sp->have_hist = true;
     }
     return EPA_OK;
   }

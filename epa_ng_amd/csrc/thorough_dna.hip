@@ -1647,24 +1647,26 @@ int launch_thorough_queued(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t
 
 int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, const uint8_t* d_codes,
                     const uint32_t* d_begin, const uint32_t* d_span, uint32_t max_span,
-                    epa_result* d_out, unsigned long long* d_stats) {
+                    epa_result* d_out, unsigned long long* d_stats, const uint32_t* cls_hist) {
   if (n_pairs > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "thorough: more than 2^32 pairs per call");
   // any category count, Newton variants, --raxml-blo outside the tuned instantiation (20 states, +I,
   // windows beyond the multi-wave classes)
   if (ctx->generic_thorough || (!ctx->blo.sliding && ctx->s == 4 && max_span > 1536u)) {
-    ctx->cls_hist_pairs = 0;
     return launch_thorough_generic(ctx, d_pairs, n_pairs, d_codes, d_begin, d_span, max_span, d_out, d_stats);
   }
   // ---- span classes present in this call
   uint32_t hist[EPA_N_CLS] = {};
   const int cmax = epa_span_class(ctx->s, max_span);
-  const bool cached = ctx->cls_hist_pairs == n_pairs && n_pairs != 0;
+  // cls_hist: the caller's histogram of exactly these pairs (the fused chunk body read it back with the candidate
+  // count: no round trip here); trusted only if it adds up to n_pairs
+  uint64_t given = 0;
+  if (cls_hist) for (int c = 0; c < EPA_N_CLS; ++c) given += cls_hist[c];
+  const bool cached = cls_hist && given == n_pairs && n_pairs != 0;
   if (cached) {
-    for (int c = 0; c < EPA_N_CLS; ++c) hist[c] = ctx->cls_hist[c];
+    for (int c = 0; c < EPA_N_CLS; ++c) hist[c] = cls_hist[c];
   } else if (cmax == 0) {
     hist[0] = (uint32_t)n_pairs;  // every window is in the smallest class
   }
-  ctx->cls_hist_pairs = 0;
   // scratch 8: [hist 64 B | keys n | idx n | keys_out n | order n | rocprim temp]
   size_t temp_bytes = 0;
   (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
