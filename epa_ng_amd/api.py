@@ -19,7 +19,7 @@ __all__ = ["EpaError", "dev_lib", "device_count", "encode_queries", "Evaluator",
            "RESULT_DTYPE", "ROW_DTYPE", "DEV_SO", "Packed4", "pack_codes_4bit", "unpack_codes_4bit", "Comm",
            "comm_unique_id", "mapped_rccl_path", "comm_set_library", "comm_library_path", "comm_set_default_timeout",
            "pci_id_str", "FLAG_LOOKUP_BLOCKS", "FLAG_LOOKUP_AUTO", "LOOKUP_RESIDENT", "LOOKUP_BLOCKS", "ERR_NO_MEMORY",
-           "footprint", "lookup_plan", "set_mem_cap"]
+           "footprint", "lookup_plan", "set_mem_cap", "quadrature_legendre01", "quadrature_laguerre", "posterior_rule"]
 
 # lookup layout of a context (include/epa_dev.h: EPA_FLAG_LOOKUP_*, EPA_LOOKUP_*, EPA_ERR_NO_MEMORY)
 FLAG_LOOKUP_BLOCKS = 0x40
@@ -119,6 +119,11 @@ def dev_lib():
         L.epa_dev_rell_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                            C.c_uint64, C.c_void_p]
+        L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint32, C.c_void_p, C.c_void_p]
+        L.epa_quadrature_legendre01.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
+        L.epa_quadrature_laguerre.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.epa_dev_set_heuristic.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.epa_dev_set_query_packing.argtypes = [C.c_void_p, C.c_int]
         L.epa_pack_codes_4bit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -245,6 +250,39 @@ def unpack_codes_4bit(p):
     out = np.zeros((Q, p.stride), np.uint8)
     dev_lib().epa_unpack_codes_4bit(np.ascontiguousarray(p.data).ctypes.data, Q, p.stride, out.ctypes.data)
     return out
+
+
+def _quadrature(fn, K):
+    K = int(K)
+    nodes, logw = np.empty(max(K, 0), np.float64), np.empty(max(K, 0), np.float64)
+    rc = fn(K if 0 <= K < 2 ** 32 else 0, nodes.ctypes.data, logw.ctypes.data)
+    if rc:
+        raise EpaError(rc, "quadrature: the number of nodes must be 1 .. 64")
+    return nodes, logw
+
+
+def quadrature_legendre01(K):
+    """Gauss-Legendre on [0, 1] (epa_quadrature_legendre01; needs no device) -> (nodes in (0, 1) ascending, log weights;
+    the weights sum to 1)"""
+    return _quadrature(dev_lib().epa_quadrature_legendre01, K)
+
+
+def quadrature_laguerre(K):
+    """Gauss-Laguerre, weight function e^-t on [0, inf) (epa_quadrature_laguerre; needs no device) -> (nodes t_j > 0
+    ascending, log weights; the weights sum to 1)"""
+    return _quadrature(dev_lib().epa_quadrature_laguerre, K)
+
+
+def posterior_rule(prior_mean, Kx=8, Kp=16):
+    """the tensor rule of the marginal likelihood (include/epa_dev.h, epa_dev_marginal_like): attachment point uniform
+    on the edge (Gauss-Legendre), pendant length with an exponential prior of mean `prior_mean` (Gauss-Laguerre, the
+    prior is the weight function) -> (x_frac, x_logw, p_len, p_logw) for Evaluator.marginal_like"""
+    prior_mean = float(prior_mean)
+    if not (np.isfinite(prior_mean) and prior_mean > 0.0):
+        raise ValueError("posterior_rule: the prior mean must be positive and finite")
+    x_frac, x_logw = quadrature_legendre01(Kx)
+    t, p_logw = quadrature_laguerre(Kp)
+    return x_frac, x_logw, prior_mean * t, p_logw
 
 
 def _ptr(a):
@@ -462,6 +500,26 @@ class Evaluator:
         self._check(self.L.epa_dev_site_lnl(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                             _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, int(pitch), _ptr(out)))
         return out
+
+    def marginal_like(self, pairs, codes, win_begin, win_span, x_frac, x_logw, p_len, p_logw, Q=None, out=None, grid=False):
+        """marginal likelihood of the placements `pairs` over a (distal x pendant) tensor rule (epa_dev_marginal_like;
+        posterior_rule() makes the default one) -> M float64 [n], or (M, g) with grid=True: g [n][Kx][Kp] is the lnL
+        (score_at's) at distal x_frac[i] * branch length and pendant p_len[j].  The four rule arrays are host arrays;
+        `out` may be a device buffer for M."""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs)
+        x_frac, x_logw, p_len, p_logw = (np.ascontiguousarray(a, dtype=np.float64) for a in (x_frac, x_logw, p_len, p_logw))
+        if x_frac.shape != x_logw.shape or p_len.shape != p_logw.shape or x_frac.ndim != 1 or p_len.ndim != 1:
+            raise ValueError("marginal_like: nodes and log weights must be 1-d arrays of equal length")
+        Kx, Kp = len(x_frac), len(p_len)
+        if out is None:
+            out = np.empty(n, np.float64)
+        g = np.empty((n, Kx, Kp), np.float64) if grid else None
+        self._layout(codes)
+        self._check(self.L.epa_dev_marginal_like(self.h, _ptr(pairs), n, _ptr(x_frac), _ptr(x_logw), Kx, _ptr(p_len),
+                                                 _ptr(p_logw), Kp, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q,
+                                                 _ptr(out), _ptr(g)))
+        return (out, g) if grid else out
 
     def rell_support(self, pairs, pendant, distal, codes, win_begin, win_span, replicates, seed=1, stream_id=None,
                      proximal=None, Q=None, out=None):

@@ -524,6 +524,93 @@ extern "C" int epa_encode_queries_compact(uint32_t states, uint32_t sites, uint3
                      win_span, bad_query);
 }
 
+// ---- quadrature rules for epa_dev_marginal_like (host only, no device needed)
+// Nodes: the eigenvalues of the rule's Jacobi matrix (symmetric tridiagonal: diagonal d, off-diagonal o) by bisection
+// on the Sturm count, then Newton on the polynomial's three-term recurrence; weights from the closed forms, in logs.
+namespace {
+void tridiag_eigenvalues(const std::vector<double>& d, const std::vector<double>& o, std::vector<double>& ev) {
+  const size_t K = d.size();
+  double lo = d[0], hi = d[0];
+  for (size_t i = 0; i < K; ++i) {   // Gershgorin
+    const double r = (i ? std::fabs(o[i - 1]) : 0.0) + (i + 1 < K ? std::fabs(o[i]) : 0.0);
+    lo = std::min(lo, d[i] - r);
+    hi = std::max(hi, d[i] + r);
+  }
+  auto below = [&](double x) {   // eigenvalues < x
+    size_t n = 0;
+    double q = 1.0;
+    for (size_t i = 0; i < K; ++i) {
+      q = d[i] - x - (i ? o[i - 1] * o[i - 1] / q : 0.0);
+      if (q == 0.0) q = 1e-300;
+      if (q < 0.0) ++n;
+    }
+    return n;
+  };
+  ev.resize(K);
+  for (size_t j = 0; j < K; ++j) {
+    double a = lo, b = hi;
+    for (int it = 0; it < 200 && b - a > 4e-16 * std::max(std::fabs(a), std::fabs(b)); ++it) {
+      const double mid = 0.5 * (a + b);
+      if (below(mid) > j) b = mid; else a = mid;
+    }
+    ev[j] = 0.5 * (a + b);
+  }
+}
+
+// log(sum exp(v)), the terms added in index order
+double log_sum_exp(const double* v, uint32_t K) {
+  double mx = v[0], sum = 0.0;
+  for (uint32_t j = 1; j < K; ++j) mx = std::max(mx, v[j]);
+  for (uint32_t j = 0; j < K; ++j) sum += std::exp(v[j] - mx);
+  return mx + std::log(sum);
+}
+}  // namespace
+
+extern "C" int epa_quadrature_legendre01(uint32_t K, double* nodes, double* log_weights) {
+  if (K < 1 || K > 64 || !nodes || !log_weights) return EPA_ERR_INVALID_ARG;
+  std::vector<double> d(K, 0.0), o(K > 1 ? K - 1 : 0), x;
+  for (uint32_t i = 1; i < K; ++i) o[i - 1] = (double)i / std::sqrt(4.0 * i * i - 1.0);
+  tridiag_eigenvalues(d, o, x);
+  for (uint32_t j = 0; j < K; ++j) {
+    double t = x[j], dp = 1.0;
+    for (int it = 0; it < 3; ++it) {   // P_K and P_K' at t: (n + 1) P_{n+1} = (2n + 1) t P_n - n P_{n-1}
+      double p0 = 1.0, p1 = t;
+      for (uint32_t n = 1; n < K; ++n) { const double p2 = ((2.0 * n + 1.0) * t * p1 - n * p0) / (n + 1.0); p0 = p1; p1 = p2; }
+      dp = K * (t * p1 - p0) / (t * t - 1.0);
+      if (it < 2) t -= p1 / dp;
+    }
+    nodes[j] = 0.5 * (1.0 + t);
+    // weight on [-1, 1]: 2 / ((1 - t^2) P_K'(t)^2); on [0, 1] half of it
+    log_weights[j] = -std::log((1.0 - t) * (1.0 + t)) - 2.0 * std::log(std::fabs(dp));
+  }
+  const double norm = log_sum_exp(log_weights, K);
+  for (uint32_t j = 0; j < K; ++j) log_weights[j] -= norm;
+  return EPA_OK;
+}
+
+extern "C" int epa_quadrature_laguerre(uint32_t K, double* nodes, double* log_weights) {
+  if (K < 1 || K > 64 || !nodes || !log_weights) return EPA_ERR_INVALID_ARG;
+  std::vector<double> d(K), o(K > 1 ? K - 1 : 0), x;
+  for (uint32_t i = 0; i < K; ++i) d[i] = 2.0 * i + 1.0;
+  for (uint32_t i = 1; i < K; ++i) o[i - 1] = (double)i;
+  tridiag_eigenvalues(d, o, x);
+  for (uint32_t j = 0; j < K; ++j) {
+    double t = x[j], lm = 1.0;
+    for (int it = 0; it < 3; ++it) {   // L_K, L_{K-1} at t: (n + 1) L_{n+1} = (2n + 1 - t) L_n - n L_{n-1}
+      double l0 = 1.0, l1 = 1.0 - t;
+      for (uint32_t n = 1; n < K; ++n) { const double l2 = ((2.0 * n + 1.0 - t) * l1 - n * l0) / (n + 1.0); l0 = l1; l1 = l2; }
+      lm = l0;
+      if (it < 2) t -= l1 * t / (K * (l1 - l0));   // t L_K' = K (L_K - L_{K-1})
+    }
+    nodes[j] = t;
+    // w = t / (K^2 L_{K-1}(t)^2), in logs: w reaches e^-109 at K = 32 and would underflow beyond
+    log_weights[j] = std::log(t) - 2.0 * std::log((double)K) - 2.0 * std::log(std::fabs(lm));
+  }
+  const double norm = log_sum_exp(log_weights, K);
+  for (uint32_t j = 0; j < K; ++j) log_weights[j] -= norm;
+  return EPA_OK;
+}
+
 // =============================================================================================
 // C-ABI
 // =============================================================================================
@@ -1596,6 +1683,7 @@ extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_
 
 // What epa_dev_score_at, epa_dev_site_lnl and epa_dev_rell_support share: the entries' arguments checked (host arrays;
 // the first offending entry is named after `who`) and staged on the device.  hs: the host's view of win_span.
+// pendant == distal == NULL (epa_dev_marginal_like): the pairs alone, no per-entry lengths are checked or staged.
 struct EntryStage {
   std::vector<uint32_t> hb_buf, hs_buf;
   const uint32_t* hs = nullptr;
@@ -1615,7 +1703,7 @@ static int stage_entries(epa_ctx* ctx, const char* who, const epa_pair* pairs, c
   int rc = check_windows(ctx, hb, st.hs, Q, &st.max_span, true);   // an empty window is the empty sum: lnL 0
   if (rc) return rc;
   // host arrays are validated (device arrays are the caller's responsibility): the first offending entry is named
-  const bool hp = !epa_is_device_ptr(pairs), hpe = !epa_is_device_ptr(pendant), hd = !epa_is_device_ptr(distal);
+  const bool hp = !epa_is_device_ptr(pairs), hpe = pendant && !epa_is_device_ptr(pendant), hd = distal && !epa_is_device_ptr(distal);
   const bool hx = proximal && !epa_is_device_ptr(proximal);
   auto bad = [&](uint64_t i, const char* what) {
     return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": entry " + std::to_string(i) + ": " + what);
@@ -1633,10 +1721,11 @@ static int stage_entries(epa_ctx* ctx, const char* who, const epa_pair* pairs, c
   st.d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
   st.d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
   st.d_pairs = (const epa_pair*)epa_to_device(ctx, 4, pairs, sizeof(epa_pair) * n);
-  st.d_pen = (const double*)epa_to_device(ctx, 7, pendant, sizeof(double) * n);
-  st.d_dis = (const double*)epa_to_device(ctx, 8, distal, sizeof(double) * n);
+  st.d_pen = pendant ? (const double*)epa_to_device(ctx, 7, pendant, sizeof(double) * n) : nullptr;
+  st.d_dis = distal ? (const double*)epa_to_device(ctx, 8, distal, sizeof(double) * n) : nullptr;
   st.d_prx = proximal ? (const double*)epa_to_device(ctx, 9, proximal, sizeof(double) * n) : nullptr;
-  if (!st.d_codes || !st.d_begin || !st.d_span || !st.d_pairs || !st.d_pen || !st.d_dis || (proximal && !st.d_prx))
+  if (!st.d_codes || !st.d_begin || !st.d_span || !st.d_pairs || (pendant && !st.d_pen) || (distal && !st.d_dis) ||
+      (proximal && !st.d_prx))
     return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
   return EPA_OK;
 }
@@ -1688,6 +1777,52 @@ extern "C" int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const doubl
                        true, d_rows, true);
   if (rc) return rc;
   if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(site_lnl, d_rows, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_marginal_like(epa_ctx* ctx, const epa_pair* pairs, uint64_t n, const double* x_frac,
+                                     const double* x_logw, uint32_t Kx, const double* p_len, const double* p_logw,
+                                     uint32_t Kp, const uint8_t* q_codes, const uint32_t* win_begin,
+                                     const uint32_t* win_span, uint32_t Q, double* marginal, double* grid_lnl) {
+  if (!ctx || !x_frac || !x_logw || !p_len || !p_logw || (n && (!pairs || !marginal || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (Kx < 1 || Kx > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "marginal_like: Kx " + std::to_string(Kx) + " is outside 1 .. 64");
+  if (Kp < 1 || Kp > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "marginal_like: Kp " + std::to_string(Kp) + " is outside 1 .. 64");
+  auto bad = [&](const char* what, uint32_t i, const char* why) {
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string("marginal_like: ") + what + " node " + std::to_string(i) + ": " + why);
+  };
+  for (uint32_t i = 0; i < Kx; ++i) {
+    if (!(std::isfinite(x_frac[i]) && x_frac[i] >= 0.0 && x_frac[i] <= 1.0)) return bad("distal", i, "x_frac is outside [0, 1] or not finite");
+    if (!std::isfinite(x_logw[i])) return bad("distal", i, "the log weight is not finite");
+  }
+  for (uint32_t j = 0; j < Kp; ++j) {
+    if (!(std::isfinite(p_len[j]) && p_len[j] >= 0.0)) return bad("pendant", j, "p_len is negative or not finite");
+    if (!std::isfinite(p_logw[j])) return bad("pendant", j, "the log weight is not finite");
+  }
+  if (n == 0) return EPA_OK;
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  EntryStage st;
+  int rc = stage_entries(ctx, "marginal_like", pairs, nullptr, nullptr, nullptr, n, q_codes, win_begin, win_span, Q, st);
+  if (rc) return rc;
+  std::vector<double> rule;
+  rule.reserve(2 * (size_t)(Kx + Kp));
+  rule.insert(rule.end(), x_frac, x_frac + Kx);
+  rule.insert(rule.end(), x_logw, x_logw + Kx);
+  rule.insert(rule.end(), p_len, p_len + Kp);
+  rule.insert(rule.end(), p_logw, p_logw + Kp);
+  const double* d_rule = (const double*)epa_to_device(ctx, 7, rule.data(), sizeof(double) * rule.size());
+  if (!d_rule) return epa_fail(ctx, EPA_ERR_HIP, "marginal_like input upload failed");
+  const bool out_dev = epa_is_device_ptr(marginal), grid_dev = grid_lnl && epa_is_device_ptr(grid_lnl);
+  const size_t gbytes = sizeof(double) * (size_t)n * Kx * Kp;
+  double* d_m = out_dev ? marginal : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
+  double* d_g = !grid_lnl ? nullptr : grid_dev ? grid_lnl : (double*)epa_scratch(ctx, 8, gbytes);
+  if (!d_m || (grid_lnl && !d_g)) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(marginal_like out)");
+  rc = launch_marginal(ctx, st.d_pairs, n, d_rule, Kx, Kp, st.d_codes, st.d_begin, st.d_span, d_m, d_g);
+  if (rc) return rc;
+  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(marginal, d_m, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (grid_lnl && !grid_dev) EPA_HIP(ctx, hipMemcpyAsync(grid_lnl, d_g, gbytes, hipMemcpyDeviceToHost, ctx->stream));
+  // the rule and host inputs were staged from pageable memory: they must not change before the copies ran
   EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return EPA_OK;
 }
@@ -2699,6 +2834,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "score_at")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SCORE]][epa_ctx::T_SCORE];
   else if (!strcmp(which, "site_lnl")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SITES]][epa_ctx::T_SITES];
   else if (!strcmp(which, "rell")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL]][epa_ctx::T_RELL];
+  else if (!strcmp(which, "marginal")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_MARGINAL]][epa_ctx::T_MARGINAL];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

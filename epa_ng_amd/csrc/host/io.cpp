@@ -665,10 +665,12 @@ std::vector<Jplace_PQuery> read_jplace(const std::string& path) {
 // One chunk of the "placements" array as text (sample_to_jplace_string, src/io/jplace_util.cpp:
 // 60-98): formatted per pquery in parallel with snprintf into per-thread strings, then joined.
 // Numbers are fixed-point with `precision` digits like the reference's stream settings.
-std::string jplace_chunk_text(const Sample& sample, unsigned int precision, const Rtree_Mapper* mapper, bool rell) {
+std::string jplace_chunk_text(const Sample& sample, unsigned int precision, const Rtree_Mapper* mapper, unsigned int extra) {
   const bool remap = mapper && (bool)*mapper;  // placement_to_jplace_string, jplace_util.cpp:20-26
   const int nt_max = std::max(1, configure_host_threads());
   const long n = (long)sample.size();
+  const bool rell = extra & kJplaceRell, posterior = extra & kJplacePosterior;
+  const int n_vals = 4 + (rell ? 1 : 0) + (posterior ? 2 : 0);
   // one contiguous buffer per thread over a contiguous range of pqueries (no string per pquery: 50 000 small heap
   // blocks per chunk were a third of this stage), every placement line assembled in a stack buffer with pointer bumps
   std::vector<std::string> part((size_t)nt_max);
@@ -678,7 +680,7 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
     const long i0 = n * t / nthr, i1 = n * (t + 1) / nthr;
     std::string& o = part[(size_t)t];
     size_t est = 0;
-    for (long i = i0; i < i1; ++i) est += 48 + sample[i].header().size() + sample[i].size() * (24 + (rell ? 5 : 4) * (size_t)(precision + 12));
+    for (long i = i0; i < i1; ++i) est += 48 + sample[i].header().size() + sample[i].size() * (24 + (size_t)n_vals * (size_t)(precision + 12));
     o.reserve(est);
     char line[1024];
     for (long i = i0; i < i1; ++i) {
@@ -696,8 +698,11 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
         char* w = line;
         std::memcpy(w, "      [", 7); w += 7;
         w = std::to_chars(w, line + 64, edge).ptr;
-        const double vals[5] = {p.likelihood(), p.lwr(), distal, p.pendant_length(), p.rell_support()};
-        for (int k = 0; k < (rell ? 5 : 4); ++k) {
+        double vals[7] = {p.likelihood(), p.lwr(), distal, p.pendant_length()};
+        int nv = 4;
+        if (rell) vals[nv++] = p.rell_support();
+        if (posterior) { vals[nv++] = p.marginal_like(); vals[nv++] = p.post_prob(); }
+        for (int k = 0; k < n_vals; ++k) {
           *w++ = ','; *w++ = ' ';
           w += format_fixed(w, (size_t)(line + sizeof(line) - w) - 8, vals[k], precision);
         }
@@ -723,7 +728,7 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
 }
 
 void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_texts, const std::string& newick,
-                       const std::string& invocation, bool rell) {
+                       const std::string& invocation, unsigned int extra) {
   os << "{\n  \"tree\": \"" << newick << "\",\n  \"placements\": \n  [\n";
   bool first_chunk = true;
   for (const auto& t : chunk_texts) {
@@ -734,15 +739,16 @@ void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_t
   }
   os << "  ],\n  \"metadata\": {\"invocation\": \"" << invocation << "\"},\n  \"version\": 3,\n"
      << "  \"fields\": [\"edge_num\", \"likelihood\", \"like_weight_ratio\", \"distal_length\""
-     << ", \"pendant_length\"" << (rell ? ", \"rell_support\"" : "") << "]\n}\n";
+     << ", \"pendant_length\"" << (extra & kJplaceRell ? ", \"rell_support\"" : "")
+     << (extra & kJplacePosterior ? ", \"marginal_like\", \"post_prob\"" : "") << "]\n}\n";
 }
 
 void write_jplace(std::ostream& os, const std::vector<Sample>& chunks, const std::string& newick,
-                  const std::string& invocation, unsigned int precision, const Rtree_Mapper* mapper, bool rell) {
+                  const std::string& invocation, unsigned int precision, const Rtree_Mapper* mapper, unsigned int extra) {
   std::vector<std::string> texts;
   texts.reserve(chunks.size());
-  for (const auto& sample : chunks) texts.push_back(jplace_chunk_text(sample, precision, mapper, rell));
-  write_jplace_text(os, texts, newick, invocation, rell);
+  for (const auto& sample : chunks) texts.push_back(jplace_chunk_text(sample, precision, mapper, extra));
+  write_jplace_text(os, texts, newick, invocation, extra);
 }
 
 }  // namespace epa

@@ -2,6 +2,8 @@
 // (src/main.cpp:96-270).  Flags outside the hot path (binary dump, bfast conversion, --split)
 // are rejected with a message, not silently ignored.
 #include <chrono>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -34,6 +36,12 @@ static void usage() {
       "                        from N (1 .. 1048576) resamplings of the per-site log-likelihoods; written as a sixth\n"
       "                        field \"rell_support\".  Two steps: place first, then --rescore out.jplace --rell N\n"
       "  --rell-seed S         seed of the resampling (default 1); the result depends on N, S and the input file alone\n"
+      "  --posterior           with --rescore: marginal likelihood of every row's edge, integrated over the attachment point\n"
+      "                        (uniform on the edge) and the pendant length (exponential prior), and its normalisation over\n"
+      "                        the rows of the placement object; written as the fields \"marginal_like\" and \"post_prob\"\n"
+      "                        (after \"rell_support\" when --rell is given).  Only edge_num of a row enters them\n"
+      "  --prior-mean M        mean of the pendant prior (default: the mean branch length of the reference tree)\n"
+      "  --posterior-nodes KX,KP  Gauss-Legendre nodes along the edge x Gauss-Laguerre pendant nodes, 1 .. 64 each (default 8,16)\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -68,7 +76,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> placing_flags;   // flags that steer heuristic, optimiser or filter: meaningless with --rescore
   Options opt;
   int device = 0;
-  bool device_given = false, rell_given = false;
+  bool device_given = false, rell_given = false, prior_given = false, nodes_given = false;
   std::vector<int> devices;
   // one process per GPU (place_ranks.cpp): --rank / --world / --comm-file, or what torchrun / mpirun export
   auto env_int = [](const char* a, const char* b, int dflt) {
@@ -106,6 +114,23 @@ int main(int argc, char** argv) {
     else if (a == "--rescore") rescore_file = need(i);
     else if (a == "--rell") { opt.rell_replicates = (unsigned)std::stoul(need(i)); rell_given = true; }
     else if (a == "--rell-seed") { opt.rell_seed = std::stoull(need(i)); rell_given = true; }
+    else if (a == "--posterior") opt.posterior = true;
+    else if (a == "--prior-mean") {
+      const std::string v = need(i);
+      char* end = nullptr;
+      opt.prior_mean = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end) opt.prior_mean = -1.0;   // not a number: refused below
+      prior_given = true;
+    }
+    else if (a == "--posterior-nodes") {
+      const std::string v = need(i);
+      unsigned long kx = 0, kp = 0;
+      char tail = 0;
+      if (std::sscanf(v.c_str(), "%lu,%lu%c", &kx, &kp, &tail) != 2 || v.find('-') != std::string::npos) kx = kp = 0;
+      opt.posterior_kx = kx > 64 ? 0u : (unsigned)kx;
+      opt.posterior_kp = kp > 64 ? 0u : (unsigned)kp;
+      nodes_given = true;
+    }
     else if (a == "--precision") opt.precision = (unsigned)std::stoul(need(i));
     else if (a == "--chunk-size") { opt.chunk_size = (unsigned)std::stoul(need(i)); opt.chunk_size_given = true; }
     else if (a == "--device-min-chunk") { opt.device_min_chunk = (unsigned)std::stoul(need(i)); opt.device_min_chunk_given = true; }
@@ -174,6 +199,22 @@ int main(int argc, char** argv) {
   }
   if (rell_given && (opt.rell_replicates == 0 || opt.rell_replicates > (1u << 20))) {
     std::cerr << "--rell: the number of replicates must be 1 .. 1048576 (--rell-seed needs --rell N)\n";
+    return 1;
+  }
+  if ((prior_given || nodes_given) && !opt.posterior) {
+    std::cerr << "--prior-mean / --posterior-nodes shape the rule of --posterior and need it: --rescore out.jplace --posterior\n";
+    return 1;
+  }
+  if (opt.posterior && rescore_file.empty()) {
+    std::cerr << "--posterior works on an existing result: place first, then run again with --rescore out.jplace --posterior\n";
+    return 1;
+  }
+  if (prior_given && !(std::isfinite(opt.prior_mean) && opt.prior_mean > 0.0)) {
+    std::cerr << "--prior-mean: the mean of the pendant prior must be positive and finite\n";
+    return 1;
+  }
+  if (nodes_given && (opt.posterior_kx < 1 || opt.posterior_kp < 1)) {
+    std::cerr << "--posterior-nodes: KX,KP with both node counts in 1 .. 64\n";
     return 1;
   }
   if (!rescore_file.empty()) {   // what --rescore does not do is refused, not silently ignored

@@ -3,12 +3,15 @@
 // false, src/tree/Tiny_Tree.cpp:186-204); the chunk loop around it reads the query file like simple_mpi (place.cpp)
 // does -- same reader, same premasking -- and picks the sequences the jplace names.  With --rell N the same rows also
 // get their RELL bootstrap support (epa_dev_rell_support) among the rows of their placement object; the object's index
-// in the input file is its random stream, so the result does not depend on --chunk-size.
+// in the input file is its random stream, so the result does not depend on --chunk-size.  With --posterior the rows get
+// their marginal likelihood (epa_dev_marginal_like: only edge_num comes from the row; Gauss-Legendre x Gauss-Laguerre
+// rule, exponential pendant prior) and post_prob, its normalisation over the rows of the placement object.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <unordered_map>
 
 #include "epa_host.hpp"
@@ -59,6 +62,28 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
       }
       ++n_rows;
     }
+  }
+
+  // the rule of --posterior: attachment uniform on the edge, pendant length exponential with mean mu
+  std::vector<double> x_frac, x_logw, p_len, p_logw;
+  if (options.posterior) {
+    const uint32_t kx = options.posterior_kx, kp = options.posterior_kp;
+    x_frac.resize(kx); x_logw.resize(kx); p_len.resize(kp); p_logw.resize(kp);
+    if (epa_quadrature_legendre01(kx, x_frac.data(), x_logw.data()) != EPA_OK ||
+        epa_quadrature_laguerre(kp, p_len.data(), p_logw.data()) != EPA_OK)
+      throw std::runtime_error{"--posterior-nodes: the node counts must be 1 .. 64"};
+    double mu = options.prior_mean;
+    if (mu == 0.0) {   // default: the mean branch length of the reference tree
+      for (const double l : blen) mu += l;
+      mu /= (double)B;
+    }
+    if (!(std::isfinite(mu) && mu > 0.0))
+      throw std::runtime_error{"--posterior: the mean branch length of the reference tree is not positive; give --prior-mean"};
+    for (double& t : p_len) t *= mu;
+    if (p_len[0] < 1e-4)
+      std::cerr << "warning: --posterior: the smallest pendant node is " << p_len[0] << " (prior mean " << mu << "): below 1e-4 "
+                   "the error of a log-likelihood grows like 1 / pendant and marginal_like is not covered by the 1e-6 bound; "
+                   "a larger --prior-mean or fewer pendant nodes (--posterior-nodes) lift it" << std::endl;
   }
 
   // ---- device
@@ -125,6 +150,16 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
       if (rrc != EPA_OK)
         throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rrc) + ")"};
     }
+    std::vector<double> marginal;
+    if (options.posterior) {
+      marginal.resize(pairs.size());
+      const int mrc = epa_dev_marginal_like(dev.ctx(), pairs.data(), pairs.size(), x_frac.data(), x_logw.data(),
+                                            (uint32_t)x_frac.size(), p_len.data(), p_logw.data(), (uint32_t)p_len.size(),
+                                            enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
+                                            marginal.data(), nullptr);
+      if (mrc != EPA_OK)
+        throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(mrc) + ")"};
+    }
     st.seconds_place += std::chrono::duration<double>(clk::now() - ts).count();
     size_t k = 0;
     for (size_t q = 0; q < named.size(); ++q) {
@@ -132,6 +167,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
       for (const Jplace_Row& r : input[target[q]].rows) {
         pq.emplace_back(r.edge_num, lnl[k], r.pendant_length, r.distal_length);
         if (!support.empty()) pq[pq.size() - 1].rell_support(support[k]);
+        if (!marginal.empty()) pq[pq.size() - 1].marginal_like(marginal[k]);
         ++k;
       }
       sample[target[q]] = std::move(pq);
@@ -147,6 +183,13 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
 
   ts = clk::now();
   compute_and_set_lwr(sample);
+  if (options.posterior)   // post_prob: the arithmetic of compute_and_set_lwr on marginal_like
+    for (PQuery& pq : sample) {
+      double mx = -std::numeric_limits<double>::infinity(), total = 0.0;
+      for (const Placement& p : pq) mx = std::max(mx, p.marginal_like());
+      for (Placement& p : pq) { const double e = std::exp(p.marginal_like() - mx); p.post_prob(e); total += e; }
+      for (Placement& p : pq) p.post_prob(p.post_prob() / total);
+    }
   for (PQuery& pq : sample) sort_by_lwr(pq);
   st.seconds_post = std::chrono::duration<double>(clk::now() - ts).count();
   ts = clk::now();
@@ -156,7 +199,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
   std::ofstream os(out_path);
   if (!os) throw std::runtime_error{"cannot open " + out_path};
   write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision, nullptr,
-               options.rell_replicates != 0);
+               (options.rell_replicates ? kJplaceRell : 0u) | (options.posterior ? kJplacePosterior : 0u));
   os.flush();
   if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }
   st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();

@@ -403,6 +403,55 @@ int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const double* pendant,
                      uint32_t pitch, double* site_lnl /* [n][pitch] */);
 
 /*
+ * Marginal likelihood of "read q sits somewhere on edge b", integrated over where it attaches and how long its pendant
+ * branch is.  The definition is this project's own (pplacer's -p mode, which writes the jplace fields marginal_like and
+ * post_prob, is the motivation, not a parity target).  For an entry (branch b of length L_b, query q):
+ *
+ *   M(b,q) = log  int_0^1 dx  int_0^inf dp  (1/mu) e^{-p/mu} * Lik(b, q; pendant = p, distal = x L_b, proximal = L_b - x L_b)
+ *
+ * Lik is exactly what epa_dev_score_at returns the log of: taken over the query's window, scaler counts and the +I term
+ * included.  The attachment point is uniform on the edge; the pendant length has an exponential prior of mean mu.  The
+ * posterior probability of a row is exp(M_i) / sum_rows exp(M_i) over the rows of its placement object: an equal prior
+ * over the object's edges, the normalisation compute_and_set_lwr applies to `likelihood` (the caller's business).
+ * The device does not know about priors or quadrature rules.  The caller hands it a tensor rule and it evaluates exactly:
+ *
+ *   d_i   = x_frac[i] * blen[b]             proximal_i = blen[b] - d_i      (score_at's own expression for proximal == NULL)
+ *   g_ij  = lnL(b, q; p_len[j], d_i, proximal_i)                            i < Kx, j < Kp
+ *   v_ij  = (x_logw[i] + p_logw[j]) + g_ij
+ *   m     = max v_ij ;   M = m + log( sum_{i ascending, then j ascending} exp(v_ij - m) )      plain fp64 adds in that order
+ *
+ * With epa_quadrature_legendre01 for x and epa_quadrature_laguerre for p (p_len[j] = mu t_j, p_logw[j] = log w_j: the
+ * prior is the rule's weight function) this is the integral above; 8 x 16 nodes agree with 16 x 32 to 1e-8 in M on the
+ * suite's references.
+ * x_frac, x_logw, p_len, p_logw are HOST arrays.  pairs, marginal ([n]) and grid_lnl ([n][Kx][Kp] = g_ij, or NULL) may be
+ * host or device pointers; queries are staged as for epa_dev_score_at (query layout / packing of the context).
+ * EPA_ERR_INVALID_ARG, naming the offender: Kx or Kp outside 1 .. 64; an x_frac outside [0, 1] or not finite; a p_len
+ * negative or not finite; a log weight that is not finite; branch_id >= B or seq_id >= Q (host pairs: the first offending
+ * entry).  n == 0 returns EPA_OK.  An entry on a query with win_span == 0 has g_ij = 0.0 everywhere: its M is the log of
+ * the rule's total weight.
+ * k_marginal (marginal.hip) keeps k_score_at's operand order inside a site -- noise cut and tables included -- so g_ij is
+ * score_at at the same point up to the order of the sum over the sites' lanes, and the same bits come out of the
+ * resident and the blocked lookup layout.  Accuracy caveat inherited from epa_dev_score_at: through the eigenbasis the
+ * error of lnL grows like 1 / pendant below 1e-4, so pendant nodes below 1e-4 are accepted but not covered by the 1e-6
+ * bound.  Timer: "marginal".
+ */
+int epa_dev_marginal_like(epa_ctx* ctx, const epa_pair* pairs, uint64_t n,
+                          const double* x_frac, const double* x_logw, uint32_t Kx,      /* host arrays */
+                          const double* p_len,  const double* p_logw, uint32_t Kp,      /* host arrays */
+                          const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                          double* marginal /* [n] */, double* grid_lnl /* [n][Kx][Kp] or NULL */);
+
+/*
+ * Quadrature rules for epa_dev_marginal_like; host only, no device needed.  K: 1 .. 64, else EPA_ERR_INVALID_ARG.  Nodes
+ * ascending; the weights are returned as logarithms and sum to 1.
+ *   legendre01: Gauss-Legendre on [0, 1]: sum_j w_j f(nodes_j) ~ int_0^1 f(x) dx, nodes in (0, 1)
+ *   laguerre:   Gauss-Laguerre: sum_j w_j f(t_j) ~ int_0^inf e^-t f(t) dt, t_j > 0; the weights are formed in log space
+ *               (w_j reaches e^-109 at K = 32)
+ */
+int epa_quadrature_legendre01(uint32_t K, double* nodes, double* log_weights);
+int epa_quadrature_laguerre(uint32_t K, double* nodes, double* log_weights);
+
+/*
  * RELL bootstrap support (resampling of estimated log-likelihoods).  The entries (as for epa_dev_score_at) of one query
  * compete, in any order -- branch-major as the chunk body emits them is the normal case: the query's sites are resampled
  * with replacement `replicates` times, every replicate is won by the entry with the largest resampled lnL, and
@@ -670,7 +719,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
