@@ -11,13 +11,15 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-DEV_SOURCES = ["epa_dev.hip", "preplace.hip", "thorough_dna.hip", "thorough_aa.hip", "thorough_aa_mfma.hip", "thorough_generic.hip", "score_at.hip", "marginal.hip", "rell.hip", "comm.hip"]
+DEV_SOURCES = ["epa_dev.hip", "preplace.hip", "thorough_dna.hip", "thorough_dna_tipd.hip", "thorough_dna_tipd2h.hip", "thorough_aa.hip", "thorough_aa_mfma.hip", "thorough_generic.hip", "score_at.hip", "marginal.hip", "rell.hip", "comm.hip"]
 # Per-file code-generation tuning, measured same-box (round 4, exp/ab.sh / ab_aa.sh, two interleaved rounds):
 # the iterative ILP scheduler removes the dominant nucleotide kernel's scratch (44 -> 0 B per lane) and is worth
 # 5.24 -> 5.17 ms per 262k-pair launch; the 20-state kernel 4.44 -> 4.37 ms per 25.7k pairs.  (iterative-minreg /
 # -maxocc: slower; preplace.hip crashes this compiler's register allocator under the strategy: not used there.)
 EXTRA_FLAGS = {"thorough_dna.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+               "thorough_dna_tipd.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
                "thorough_aa_mfma.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
+EXTRA_DEPS = {"thorough_dna_tipd.hip": ["thorough_dna.hip"], "thorough_dna_tipd2h.hip": ["thorough_dna.hip"]}   # sources a file includes
 DEV_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"),
              "-I", CSRC, "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 
@@ -40,7 +42,7 @@ def build_dev(force=False, verbose=False):
         sp = os.path.join(CSRC, src)
         op = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(op)
-        if force or _newer(op, [sp] + hdrs):
+        if force or _newer(op, [sp] + hdrs + [os.path.join(CSRC, d) for d in EXTRA_DEPS.get(src, [])]):
             cmd = [HIPCC] + DEV_FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", sp, "-o", op]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)

@@ -646,7 +646,7 @@ extern "C" int epa_dev_set_option(epa_ctx* ctx, const char* key, int value) {
       {"select_full_rows", &EpaOptions::select_full_rows}, {"select_sort", &EpaOptions::select_sort},
       {"queued_thorough", &EpaOptions::queued_thorough},   {"xcd_balance", &EpaOptions::xcd_balance},
       {"aa_valu", &EpaOptions::aa_valu},                   {"timers", &EpaOptions::timers},
-      {"newton_lds", &EpaOptions::newton_lds}};
+      {"newton_lds", &EpaOptions::newton_lds},             {"tip_distal", &EpaOptions::tip_distal}};
   for (const Entry& e : table)
     if (strcmp(key, e.name) == 0) {
       ctx->opt.*e.field = value;
@@ -744,6 +744,12 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
   if (ctx->refI) (void)hipFree(ctx->refI);
   if (ctx->cinv) (void)hipFree(ctx->cinv);
   if (ctx->resc0) (void)hipFree(ctx->resc0);
+  if (ctx->tip_row) (void)hipFree(ctx->tip_row);
+  if (ctx->tipmask) (void)hipFree(ctx->tipmask);
+  if (ctx->tipd) (void)hipFree(ctx->tipd);
+  for (hipStream_t st : ctx->side_stream) if (st) (void)hipStreamDestroy(st);
+  for (hipEvent_t e : ctx->ev_fork) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->ev_join) if (e) (void)hipEventDestroy(e);
   if (ctx->dmodel) (void)hipFree(ctx->dmodel);
   for (ChunkSlot& sl : ctx->slots) {
     if (sl.h_in) (void)hipHostFree(sl.h_in);
@@ -1260,6 +1266,21 @@ __global__ void __launch_bounds__(256) k_tip_sides(const ModelDev* __restrict__ 
   }
 }
 
+// what the TIPD Newton kernels read of a tip side (thorough_dna.hip): the state set of every tip character in place of
+// its code, and tipd[mask][x] = U^-1 (state set), summed exactly as k_tip_sides sums it above
+__global__ void __launch_bounds__(256) k_tip_masks(uint8_t* __restrict__ tipchars, const uint32_t* __restrict__ tipmap, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) tipchars[i] = (uint8_t)(tipmap[tipchars[i]] & 15u);
+}
+__global__ void __launch_bounds__(64) k_tip_table(const ModelDev* __restrict__ m, double* __restrict__ tipd) {
+  const int s = m->s;
+  const uint32_t mask = threadIdx.x >> 2;
+  const int x = threadIdx.x & 3;
+  double acc = 0.0;
+  for (int i = 0; i < s; ++i) if ((mask >> i) & 1u) acc += m->Ui[x * s + i];
+  tipd[threadIdx.x] = acc;
+}
+
 __global__ void k_scaler_sum(const uint32_t* __restrict__ sc_side, uint32_t* __restrict__ scSum, size_t n,
                              uint32_t W) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // i = b * W + site
@@ -1416,9 +1437,21 @@ static int precompute_from_tree(epa_ctx* ctx, const epa_tree_desc* t, const uint
     const size_t nbw = (size_t)B * W;
     hipLaunchKernelGGL(k_scaler_sum, dim3((uint32_t)((nbw + 255) / 256)), blk, 0, ctx->stream, d_sc, ctx->scSum, nbw, W);
   }
+  // 4 states, tuned kernels: the tip sequences stay resident as state sets for the TIPD Newton kernels
+  const bool keep_tips = ctx->s == 4 && !ctx->generic_native;
+  if (keep_tips) {
+    TREE_HIP(hipMalloc(&ctx->tipd, sizeof(double) * 64));
+    hipLaunchKernelGGL(k_tip_table, dim3(1), dim3(64), 0, ctx->stream, ctx->dmodel, ctx->tipd);
+    const size_t nt = (size_t)n * W;
+    hipLaunchKernelGGL(k_tip_masks, dim3((uint32_t)((nt + 255) / 256)), blk, 0, ctx->stream, d_tips, d_tipmap, nt);
+  }
   TREE_HIP(hipStreamSynchronize(ctx->stream));
   TREE_HIP(hipGetLastError());
 #undef TREE_HIP
+  if (keep_tips) {
+    ctx->tipmask = d_tips; d_tips = nullptr;
+    ctx->tip_row = d_tob; d_tob = nullptr;
+  }
   cleanup();
   return EPA_OK;
 }
@@ -1960,7 +1993,8 @@ static int chunk_body_end(epa_ctx* ctx, SelectPending* sp, const uint8_t* d_code
   *n_out = n;
   // the queued launch ran iff all n pairs are of its class (no overflow / window error: checked above) -- the test
   // k_thorough_dna applied to the same block
-  if (sp->queued_cls >= 0 && sp->rb[9 + sp->queued_cls] == (uint32_t)n) return EPA_OK;
+  // (both halves of the class where the selection counted its tip-distal pairs apart: the queued launch takes them all)
+  if (sp->queued_cls >= 0 && sp->rb[9 + sp->queued_cls] + sp->rb[9 + epa_tip_class(sp->queued_cls)] == (uint32_t)n) return EPA_OK;
   if (ctx->clean_stats[ctx->bank] == d_stats && sp->queued_cls < 0) ctx->clean_stats[ctx->bank] = nullptr;   // cleared behind the selection
   else {
     ctx->clean_stats[ctx->bank] = nullptr;
@@ -1969,8 +2003,11 @@ static int chunk_body_end(epa_ctx* ctx, SelectPending* sp, const uint8_t* d_code
   }
   if (n == 0) return EPA_OK;
   // the selection's class histogram travels in *sp: it describes these n pairs and nothing else
+  // (a context that forms tip-distal keys needs them in the histogram: a selection that could not split them off --
+  // several span classes, the staging form -- leaves the count to launch_thorough)
+  const bool hist_ok = sp->have_hist && (sp->tip_split || !epa_tipd_active(ctx));
   return launch_thorough(ctx, d_pairs, n, d_codes, d_begin, d_span, max_span, d_res, d_stats,
-                         sp->have_hist ? sp->cls_hist : nullptr);
+                         hist_ok ? sp->cls_hist : nullptr);
 }
 
 static int chunk_body(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span,

@@ -81,8 +81,9 @@ struct SelectPending {
   // span-class histogram of the pairs this selection emitted (launch_select_end, when d_span was given): handed to the
   // launch_thorough of the SAME chunk body (chunk_body_end), which saves that launch's device round trip.  It lives
   // and dies with the selection: nothing in epa_ctx remembers it, so no other call can be partitioned by it
-  uint32_t cls_hist[16] = {};
+  uint32_t cls_hist[24] = {};      // [EPA_N_CLSX]
   bool have_hist = false;
+  bool tip_split = false;          // cls_hist counts the tip-distal pairs apart (classes EPA_N_CLS ..): rb[30]
   const uint32_t* pre_status = nullptr;   // window-validation words of THIS chunk's preplacement (ctx->d_status may belong
                                           // to another pipeline slot by the time a widened re-run packs the read-back)
 };
@@ -157,6 +158,7 @@ struct EpaOptions {
   int aa_valu = 0;            // 20-state windows on the lane = site VALU kernel instead of the matrix-core kernel
   int timers = 1;             // hipEvent records around the kernel families (epa_dev_last_kernel_ms)
   int newton_lds = 0;         // single-wave 4-state Newton kernels read their table through LDS instead of DPP
+  int tip_distal = 1;         // pairs whose branch ends in a tip run the TIPD Newton kernels (0: the row form for all)
 };
 
 struct epa_ctx {
@@ -198,6 +200,12 @@ struct epa_ctx {
   double* cinv = nullptr;     // +I only: [W] p * pi[invariant state of the site] (0 where not invariant)
   double inv_w0 = 0.0;        // 1 / w_0: folds cinv into the zero-eigenvalue sumtable entry (thorough)
   double* lookup2 = nullptr;  // DNA only: [B][2][ceil(W/2)][36] site-pair sums (preplace.hip, k_preplace_pairs)
+  // 4 states, reference built from the tree: tip_row [B] = the tip at the distal end of the branch (its row of tipmask)
+  // or 0xffffffff, tipmask [tips][W] = the 4-bit state set of every tip character, tipd [16][4] = U^-1 (state set) --
+  // what the TIPD instantiations of k_thorough_dna read instead of such a branch's distal block of refT
+  uint32_t* tip_row = nullptr;
+  uint8_t* tipmask = nullptr;
+  double* tipd = nullptr;
   bool lookup_built = false;
   // Blocked lookup layout (EPA_FLAG_LOOKUP_BLOCKS): lookup / lookup2 / refI / resc0 stay null; every scratch bank that
   // runs a preplacement owns one block buffer -- lookup [blk][W][ncols], then (4 states) lookup2 [blk][2][ceil(W/2)][36]
@@ -255,6 +263,10 @@ struct epa_ctx {
   double last_sclk_mhz = 0.0;   // shader clock of the last stamped Newton launch (s_memtime / s_memrealtime)
   bool xstamp_ok = false;   // launch_thorough: this call is ONE kernel launch (one span class): its stamps mean something
   hipEvent_t ev_rb[N_BANKS] = {};   // per bank: behind the selection's read-back copy (SelectPending::ev_rb)
+  // per bank: the stream of the tip-distal Newton launches (beside the bank's own, so that one launch fills the
+  // other's draining tail), forked and joined by these events
+  hipStream_t side_stream[N_BANKS] = {};
+  hipEvent_t ev_fork[N_BANKS] = {}, ev_join[N_BANKS] = {};
   // per bank: the statistics block / the work counters of the NEXT Newton launch were already zeroed behind the
   // selection (chunk_body_begin: in the shadow of the host's round trip); the launch that uses them clears the mark
   const void* clean_stats[N_BANKS] = {};
@@ -273,9 +285,10 @@ inline uint32_t* epa_th_ctr(epa_ctx* ctx) { return ctx->th_ctr ? ctx->th_ctr + 6
 // multiples of 16 bytes (else: hipMemsetAsync).
 int epa_zero_async(epa_ctx* ctx, void* p, size_t bytes, void* p2 = nullptr, size_t bytes2 = 0);
 // the work counters of this bank's next Newton launch: zero them unless chunk_body_begin already did
-inline int epa_th_ctr_reset(epa_ctx* ctx) {
+// (bytes = 32: the first eight only -- the second eight belong to a tip-distal launch on the bank's side stream)
+inline int epa_th_ctr_reset(epa_ctx* ctx, size_t bytes = 64) {
   if (ctx->clean_ctr[ctx->bank]) { ctx->clean_ctr[ctx->bank] = false; return 0; }
-  return epa_zero_async(ctx, epa_th_ctr(ctx), 64);
+  return epa_zero_async(ctx, epa_th_ctr(ctx), bytes);
 }
 bool epa_is_device_ptr(const void* p);
 // returns a device pointer holding `bytes` of *p (copying into scratch slot if p is on the host)
@@ -309,6 +322,18 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
 // 20 states: 0 / 1 / 2 = windows up to 64 / 128 / 192 sites (k_thorough_aa_mfma<1/2/3>: sumtable
 // in registers), 3 = longer (k_thorough_aa with the HBM slab).
 constexpr int EPA_N_CLS = 12;
+// class keys of the thorough launches: the span classes, then the tip-distal halves of the single-wave DNA classes
+// 0, 1, 2, 10, 11 (keys 12 .. 16: pairs whose branch has a tip on the distal side, thorough_dna.hip TIPD)
+constexpr int EPA_N_CLSX = 17;
+__host__ __device__ inline bool epa_tip_class_ok(int cls) { return cls <= 2 || cls == 10 || cls == 11; }
+__host__ __device__ inline int epa_tip_class(int cls) { return cls <= 2 ? 12 + cls : cls == 10 ? 15 : cls == 11 ? 16 : cls; }
+__host__ __device__ inline int epa_base_class(int key) { return key < 12 ? key : key <= 14 ? key - 12 : key == 15 ? 10 : 11; }
+// the context forms tip-distal keys: what the TIPD kernels serve (four categories, exact zero eigenvalue, sliding
+// BLO, no +I) with the tip table of a reference built from the tree, unless the option tip_distal is 0
+inline bool epa_tipd_active(const epa_ctx* ctx) {
+  return ctx->tip_row && ctx->opt.tip_distal && ctx->s == 4 && !ctx->generic_thorough && ctx->dna.ng == 1 &&
+         ctx->dna_zero0 && ctx->blo.sliding && !ctx->cinv;
+}
 constexpr uint32_t EPA_AA_LDS_MAX_SPAN = 102;
 __host__ __device__ inline int epa_span_class(int states, uint32_t span) {
   if (states != 4) return span <= 64 ? 0 : span <= 128 ? 1 : span <= 192 ? 2 : 3;

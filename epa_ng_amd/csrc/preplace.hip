@@ -93,13 +93,19 @@ __global__ void __launch_bounds__(256) k_count_keys(const uint32_t* __restrict__
   const uint32_t q = blockIdx.x * 256 + threadIdx.x;
   if (q < Q) rank[q] = atomicAdd(&cnt[keys[q]], 1u);
 }
-__global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ cnt, uint32_t K) {
+// tip_row (or null): *tip_total = the sum of the counts of the first K - 1 entries k with tip_row[k] != 0xffffffff (the
+// selection's per-branch counters: the candidate pairs whose branch has a tip on the distal side)
+__global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ cnt, uint32_t K,
+                                                      const uint32_t* __restrict__ tip_row = nullptr,
+                                                      uint32_t* __restrict__ tip_total = nullptr) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t carry_s;
+  __shared__ uint32_t tips_s;
   const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-  if (t == 0) carry_s = 0;
+  if (t == 0) { carry_s = 0; tips_s = 0; }
   __syncthreads();
   constexpr uint32_t PER = 8;
+  uint32_t tips = 0;
   for (uint32_t base = 0; base < K; base += 1024 * PER) {
     uint32_t v[PER], tot = 0;
 #pragma unroll
@@ -107,6 +113,7 @@ __global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ cnt
       const uint32_t k = base + t * PER + i;
       v[i] = k < K ? cnt[k] : 0u;
       tot += v[i];
+      if (tip_row && k + 1 < K && tip_row[k] != 0xffffffffu) tips += v[i];
     }
     uint32_t inc = tot;                       // inclusive scan of the thread totals inside the wave
 #pragma unroll
@@ -128,6 +135,11 @@ __global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ cnt
     __syncthreads();
     if (t == 1023) carry_s = run;
     __syncthreads();
+  }
+  if (tip_total) {
+    if (tips) atomicAdd(&tips_s, tips);
+    __syncthreads();
+    if (t == 0) *tip_total = tips_s;
   }
 }
 __global__ void __launch_bounds__(256) k_scatter_sorted(const uint32_t* __restrict__ keys,
@@ -1789,14 +1801,33 @@ __global__ void __launch_bounds__(256) k_class_hist(const uint32_t* __restrict__
 
 // everything the host reads after the selection, in one block: out[0] = total, out[1 ..] = the
 // selection's status words + class histogram, out[32 .. 35] = the preplacement's window validation
+// tip_total (or null): the candidate pairs whose branch has a tip on the distal side.  When all pairs are of ONE span
+// class that has a tip-distal half (epa_tip_class_ok), the class's count is split: out[9 + c] keeps the others,
+// out[9 + epa_tip_class(c)] takes the tip pairs, out[30] = 1 says that the split was made (SelectPending::tip_split).
+// With several span classes present the per-branch counters cannot tell the classes apart: no split, out[30] = 0
 __global__ void __launch_bounds__(64) k_pack_readback(const uint32_t* __restrict__ status,
                                                      const uint32_t* __restrict__ total,
                                                      const uint32_t* __restrict__ pre_status,
-                                                     uint32_t* __restrict__ out) {
+                                                     uint32_t* __restrict__ out,
+                                                     const uint32_t* __restrict__ tip_total = nullptr) {
   const uint32_t t = threadIdx.x;
   if (t == 0) out[0] = *total;
   if (t < 8 + EPA_N_CLS) out[1 + t] = status[t];
+  else if (t < 8 + EPA_N_CLSX) out[1 + t] = 0u;
+  if (t == 30) out[30] = 0u;
   if (t < 4) out[32 + t] = pre_status ? pre_status[t] : 0u;
+  __syncthreads();   // the split below rewrites words other threads have just copied
+  if (tip_total && t == 0) {
+    int one = -1, n = 0;
+    for (int c = 0; c < EPA_N_CLS; ++c)
+      if (status[8 + c]) { one = c; ++n; }
+    if (n == 1 && epa_tip_class_ok(one)) {
+      const uint32_t all = status[8 + one], tips = min(*tip_total, all);
+      out[9 + one] = all - tips;
+      out[9 + epa_tip_class(one)] = tips;
+      out[30] = 1u;
+    }
+  }
 }
 
 __global__ void __launch_bounds__(256) k_compact(const unsigned long long* __restrict__ stage,
@@ -2160,12 +2191,15 @@ int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double th
     else if (nr <= 256) hipLaunchKernelGGL(k_select_wg<64>, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, mode, limit, so, counts, status);
     else hipLaunchKernelGGL(k_select_stream, dim3(Q), dim3(256), 0, ctx->stream, d_lnl, Q, B, pitch, threshold, stream_band, mode, limit, so, counts, status);
 #undef SEL
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, ctx->stream, bcount, B + 1);   // bcount[B] = total
+    // status[40]: the candidate pairs on branches that end in a tip (summed with the scan; split off by k_pack_readback)
+    const bool tipd = epa_tipd_active(ctx) && d_span != nullptr;
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, ctx->stream, bcount, B + 1,   // bcount[B] = total
+                       tipd ? (const uint32_t*)ctx->tip_row : (const uint32_t*)nullptr, tipd ? status + 40 : (uint32_t*)nullptr);
     if (d_span && !seg_hist)
       hipLaunchKernelGGL(k_class_hist, dim3((Q + 255) / 256), dim3(256), 0, ctx->stream, counts, d_span, Q,
                          ctx->s, status + 8);
     hipLaunchKernelGGL(k_pack_readback, dim3(1), dim3(64), 0, ctx->stream, status, bcount + B,
-                       sp->pre_status, status + 64);
+                       sp->pre_status, status + 64, tipd ? (const uint32_t*)(status + 40) : (const uint32_t*)nullptr);
     EPA_HIP(ctx, hipMemcpyAsync(rb, status + 64, sizeof(uint32_t) * 36, hipMemcpyDeviceToHost, ctx->stream));
     sp->have_status = sp->pre_status != nullptr;
     if (!ctx->ev_rb[ctx->bank]) EPA_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_rb[ctx->bank], hipEventDisableTiming));
@@ -2278,8 +2312,9 @@ int launch_select_end(epa_ctx* ctx, SelectPending* sp, uint64_t* n_pairs) {
     EPA_HIP(ctx, hipGetLastError());
     *n_pairs = total;
     if (sp->d_span) {   // the selected pairs' span classes, for the Newton launch of this chunk body only
-      for (int c = 0; c < EPA_N_CLS; ++c) sp->cls_hist[c] = hst[8 + c];
+      for (int c = 0; c < EPA_N_CLSX; ++c) sp->cls_hist[c] = hst[8 + c];
       sp->have_hist = true;
+      sp->tip_split = sp->rb[30] != 0;
     }
     return EPA_OK;
   }

@@ -87,7 +87,13 @@ struct ThArgs {
   // for that feedback; stats[5] / stats[6] = shader cycles / 100 MHz ticks of workgroup 0's first wave (the clock
   // the launch ran at: epa_dev_last_sclk_mhz).
   uint32_t xcum[9];
-  uint32_t xstamp;
+  uint32_t xstamp;         // (2: the XCD exits only -- the tip-distal launch beside the row-form launch of its class, which stamps the rest)
+  // TIPD instantiations (pairs whose branch has a tip on the distal side): tip_row[b] = the branch's row of
+  // tipmask [rows][W], the 4-bit state set of the tip's character per site; tipd [16 masks][4] = U^-1 (state set),
+  // summed as k_tip_sides sums it: the bits the distal block of refT holds for such a branch
+  const uint32_t* tip_row;
+  const uint8_t* tipmask;
+  const double* tipd;
 };
 
 using namespace epa_wave;
@@ -735,11 +741,17 @@ __device__ __forceinline__ double newton(const SiteState<NCH>& st, double* tab, 
   return NAN;
 }
 
-template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL, bool TAILH = false, int NG = 1, bool TDPP = false>
+// TIPD: the distal node of the pair's branch is a tip.  Its block of refT holds, per site, U^-1 (state set of the tip's
+// character) in every category: one of 16 four-vectors.  The phases then read the site's 4-bit mask instead of the 16
+// rows: MODE 0 takes its first factor a = U (e0 o Dt) from a per-wave table of 16 masks x 16 (category, state) entries
+// (built in `qa` exactly as MODE 1 builds the query's), MODE 1 folds with the mask's row of `dts`.  The same operations
+// on the same operands in the same order as the row form: bit-identical results.
+template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL, bool TAILH = false, int NG = 1, bool TDPP = false, bool TIPD = false>
 __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pidx, const int lane,
                                              double* tab, const double* qts, double* qa, const LaneConst& lc,
-                                             Comb<NW, NG>& cb, uint32_t (&wstat)[3]) {
+                                             Comb<NW, NG>& cb, uint32_t (&wstat)[3], const double* dts = nullptr) {
   static_assert(NG == 1 || NW == 1, "category groups and site blocks do not combine");
+  static_assert(!TIPD || (ZERO0 && !INV && NW == 1 && !LOCAL && NG == 1), "TIPD exists for the single-wave sliding kernels");
   const uint32_t site0 = NW > 1 ? (uint32_t)cb.wv * NCH * 64 : 0u;  // first window site of this wave
   const uint32_t grp = NG > 1 ? (uint32_t)cb.wv : 0u;               // this wave's category group
   const uint64_t pid = a.order ? a.order[pidx] : pidx;
@@ -761,6 +773,12 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
   const double orig = a.blen[b];
 
   SiteState<NCH> st;
+  uint32_t tmk[TIPD ? NCH : 1];   // TIPD: state set of the distal tip's character at this lane's site
+  const uint8_t* tmp = nullptr;
+  if constexpr (TIPD) {
+    const uint32_t trow = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tip_row[b]);
+    tmp = a.tipmask + (size_t)trow * cW + begin;
+  }
   // TAILH: the last chunk is a half-chunk, lane = (site = lane & 31, half = lane >> 5)
   const uint32_t half = TAILH ? (uint32_t)lane >> 5 : 0u;
   const uint32_t hoff = half * 8u * W8;            // rows of categories 2 h, 2 h + 1
@@ -778,6 +796,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
     st.sc[ch] = scp[sc];
     st.code[ch] = qc[sc];
     st.resc[ch] = 0;
+    if constexpr (TIPD) tmk[ch] = tmp[sc];
   }
 
   double tp = a.blo.pendant_default, td = orig * 0.5, tx = orig * 0.5;
@@ -820,10 +839,12 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
       soff[ch] = sidx[ch] * 8u + ((TAILH && ch == NCH - 1) ? hoff : 0u);
     }
     uint32_t tok = chain;
-    if constexpr (MODE == 1 || MODE == 3) {
-      // lane = (code = lane >> 2, category = lane & 3): the four entries a_i of (code, category)
+    constexpr bool TIP0 = TIPD && MODE == 0, TIP1 = TIPD && MODE == 1;
+    if constexpr (MODE == 1 || MODE == 3 || TIP0) {
+      // lane = (code = lane >> 2, category = lane & 3): the four entries a_i of (code, category); TIPD, MODE 0: of
+      // (state set of the distal tip, category)
       const int kq = lane & 3;
-      const double* qv = qts + (lane >> 2) * 4;
+      const double* qv = (TIP0 ? dts : qts) + (lane >> 2) * 4;
       const double* e0 = tab + kq * 4;
       double av[4];
 #pragma unroll
@@ -850,7 +871,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
         // hoists all 32 row offsets out of the pair loop and parks them in scratch
         if (MODE == 2) An[sl][x] = *reinterpret_cast<const double*>(refi_s + (s0 + (uint32_t)(k * 4 + x) * W8p));
         else {
-          An[sl][x] = *reinterpret_cast<const double*>(ref + (s0 + (uint32_t)(16 * NG + k * 4 + x) * W8p));
+          if (!TIP0 && !TIP1) An[sl][x] = *reinterpret_cast<const double*>(ref + (s0 + (uint32_t)(16 * NG + k * 4 + x) * W8p));
           Bn[sl][x] = *reinterpret_cast<const double*>(ref + (s0 + (uint32_t)(k * 4 + x) * W8p));
         }
       }
@@ -860,6 +881,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
       if (p < NS) issue(p, tok);
     int mx = 0;
     double qf[4];
+    double df[TIP1 ? 4 : 1];   // TIPD, MODE 1: the distal vector of the site (the same in every category)
 #pragma unroll
     for (int stp = 0; stp < NS; ++stp) {
       const int ch = stp >> 2, k = stp & 3, sl = stp % R;
@@ -869,6 +891,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
       if (k == 0) {
         const double* qv = qts + st.code[ch] * 4;
         qf[0] = qv[0]; qf[1] = qv[1]; qf[2] = qv[2]; qf[3] = qv[3];
+        if constexpr (TIP1) { const double* dv = dts + tmk[ch] * 4; lds_pair(dv, df[0], df[1]); lds_pair(dv + 2, df[2], df[3]); }
       }
       if (stp + DEPTH < NS) issue(stp + DEPTH, tok);
       asm volatile("" ::: "memory");   // the prefetch is issued here, not at its use
@@ -876,18 +899,19 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
       if (MODE == 2) {
 #pragma unroll
         for (int x = 0; x < 4; ++x) It[x] = An[sl][x];
-      } else if (MODE == 0) {
+      } else if (MODE == 0 && !TIP0) {
         cat_inner(pm, An[sl], tb + k * 4 + 2 * tok, Bn[sl], tb + 16 + k * 4 + 2 * tok, It, mx);   // (token in units of 16 bytes)
       } else {
         // this half's categories are 2 h, 2 h + 1 in a half-chunk
-        const double* ap = qa + st.code[ch] * QA_STRIDE + ((halfc ? (int)half * 2 : 0) + k) * 4 + 2 * tok;
+        const uint32_t row = TIP0 ? tmk[ch] : st.code[ch];
+        const double* ap = qa + row * QA_STRIDE + ((halfc ? (int)half * 2 : 0) + k) * 4 + 2 * tok;
         double Ap[4];
         lds_pair(ap, Ap[0], Ap[1]); lds_pair(ap + 2, Ap[2], Ap[3]);
-        cat_inner_pre(pm, Ap, MODE == 1 ? Bn[sl] : An[sl], tb + 16 + k * 4 + 2 * tok, It, mx);
+        cat_inner_pre(pm, Ap, (MODE == 1 || TIP0) ? Bn[sl] : An[sl], tb + 16 + k * 4 + 2 * tok, It, mx);
       }
 #pragma unroll
       for (int x = 0; x < 4; ++x)
-        st.S[ch][k * 4 + x] = It[x] * ((MODE == 0 || MODE == 2) ? qf[x] : (MODE == 1 ? An[sl][x] : Bn[sl][x]));
+        st.S[ch][k * 4 + x] = It[x] * ((MODE == 0 || MODE == 2) ? qf[x] : (MODE == 1 ? (TIP1 ? df[x] : An[sl][x]) : Bn[sl][x]));
       tok = zero_after(st.S[ch][k * 4 + 3]);
       if (k == NK - 1) {   // chunk complete
         if (MODE == 2) {
@@ -1055,7 +1079,7 @@ __device__ __forceinline__ void process_pair(const ThArgs& a, const uint64_t pid
 // default kernel's register allocation is untouched: the runtime-flag version cost 40 more spills)
 // TDPP: the Newton table broadcast by DPP from registers instead of through LDS (single-wave ZERO0 classes; the LDS
 // form stays reachable by the context option "newton_lds")
-template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL = false, bool TAILH = false, int NG = 1, bool TDPP = false>
+template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL = false, bool TAILH = false, int NG = 1, bool TDPP = false, bool TIPD = false>
 __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const ThArgs a) {
   constexpr int NWV = NW * NG;     // waves of the workgroup: site blocks (NW) or category groups (NG)
   __shared__ __attribute__((aligned(16))) double tab[64 * NWV];  // broadcast table of each wave
@@ -1064,11 +1088,13 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
   __shared__ double e2t[64];
   __shared__ __attribute__((aligned(16))) double qa[(16 * QA_STRIDE) * NWV];  // per wave: (U (e o q_code))_i for 16 codes x 16 (category, state)
   __shared__ double xch[NG > 1 ? 2 * NG * Comb<NW, NG>::XCH_MAX * 64 : 1];
+  __shared__ __attribute__((aligned(16))) double dts[TIPD ? 64 : 2];   // TIPD: U^-1 image of the 16 state sets of a tip
   const int lane = threadIdx.x & 63;
   Comb<NW, NG> cb{red, (int)(threadIdx.x >> 6), 0, xch, 0};
   if (threadIdx.x < 64) {
     qts[lane] = a.qt[lane];
     e2t[lane] = exp2((double)lane * 0.015625);
+    if constexpr (TIPD) dts[lane] = a.tipd[lane];
   }
   LaneConst lc;
   lc.e2t = e2t;
@@ -1099,7 +1125,8 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
   if constexpr (NW == 1 && NG == 1) {
     if (a.spec) {   // queued launch: count and validity come from the selection's read-back block
       const uint32_t n = a.spec[0];
-      if (n > a.spec_max || a.spec[9 + a.spec_cls] != n || a.spec[32] || a.spec[33]) return;
+      // (the selection may have counted the class's tip-distal pairs apart: this launch takes both halves)
+      if (n > a.spec_max || a.spec[9 + a.spec_cls] + a.spec[9 + epa_tip_class((int)a.spec_cls)] != n || a.spec[32] || a.spec[33]) return;
       n_pairs = n;
     }
   }
@@ -1109,7 +1136,7 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
   if constexpr (NW == 1 && NG == 1) {
     lo = (n_pairs * a.xcum[x]) >> 20;
     hi = (n_pairs * a.xcum[x + 1]) >> 20;
-    if (a.xstamp && blockIdx.x == 0 && threadIdx.x == 0) a.stats[7] = __builtin_amdgcn_s_memrealtime() & EPA_XSTAMP_MASK;
+    if (a.xstamp == 1 && blockIdx.x == 0 && threadIdx.x == 0) a.stats[7] = __builtin_amdgcn_s_memrealtime() & EPA_XSTAMP_MASK;
   }
   // clock-true roofline: workgroup 0's first wave lives as long as the launch (resident waves); its s_memtime
   // (shader cycles) over s_memrealtime (100 MHz) is the shader clock the launch really ran at
@@ -1142,7 +1169,7 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
       const uint32_t cur = nxt;
       uint32_t f = 0;
       if (lane == 0) f = atomicAdd(ctr, 1u);
-      process_pair<NCH, ZERO0, INV, NW, LOCAL, TAILH, NG, TDPP>(a, lo + cur, lane, tab + cb.wv * 64, qts, qa + cb.wv * (16 * QA_STRIDE), lc, cb, wstat);
+      process_pair<NCH, ZERO0, INV, NW, LOCAL, TAILH, NG, TDPP, TIPD>(a, lo + cur, lane, tab + cb.wv * 64, qts, qa + cb.wv * (16 * QA_STRIDE), lc, cb, wstat, dts);
       nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)f);
 #ifdef TH_TIMING
       ++npr;
@@ -1166,7 +1193,7 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
       if (a.xstamp) atomicMax(&a.stats[8 + x], ((unsigned long long)(__builtin_amdgcn_s_memrealtime() & EPA_XSTAMP_MASK) << 21) |
                                                    (unsigned long long)(a.xcum[x + 1] - a.xcum[x]));
     }
-    if (a.xstamp && blockIdx.x == 0) {
+    if (a.xstamp == 1 && blockIdx.x == 0) {
       a.stats[5] = __builtin_amdgcn_s_memtime() - clk0;
       a.stats[6] = __builtin_amdgcn_s_memrealtime() - rt0;
     }
@@ -1177,6 +1204,37 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
 template __global__ void k_thorough_dna<3, true, false, 1, false, true, 1>(const ThArgs a);
 template __global__ void k_thorough_dna<3, true, false, 1, false, true, 1, true>(const ThArgs a);
 }  // namespace
+#elif defined(TH_TIPD_UNIT)
+}  // namespace
+// The TIPD instantiations are a translation unit of their own (thorough_dna_tipd.hip includes this file with
+// TH_TIPD_UNIT defined): generated beside the other instantiations, this compiler's register allocator crashes on
+// k_thorough_dna<2, .., TAILH, .., TDPP, TIPD> under the iterative-ilp scheduler.  That one instantiation is a third
+// unit (thorough_dna_tipd2h.hip, TH_TIPD_UNIT == 2) built with the default scheduler: 174 VGPRs, no scratch; the others
+// build under iterative-ilp at two waves per SIMD (NCH 1: three) without scratch.  args: the launching unit's ThArgs
+// (the same definition).
+#if TH_TIPD_UNIT == 2
+void launch_dna_tipd2h(hipStream_t stream, uint32_t nwg, const void* args) {
+  const ThArgs& a = *static_cast<const ThArgs*>(args);
+  hipLaunchKernelGGL((k_thorough_dna<2, true, false, 1, false, true, 1, true, true>), dim3(nwg), dim3(64), 0, stream, a);
+}
+#else
+void launch_dna_tipd2h(hipStream_t stream, uint32_t nwg, const void* args);
+void launch_dna_tipd(hipStream_t stream, int nch, bool tailh, bool newton_lds, uint32_t nwg, const void* args) {
+  const ThArgs& a = *static_cast<const ThArgs*>(args);
+  if (nch == 2 && tailh && !newton_lds) { launch_dna_tipd2h(stream, nwg, args); return; }
+#define TIPD_L(N, TH)                                                                                                        \
+  do {                                                                                                                      \
+    if (newton_lds) hipLaunchKernelGGL((k_thorough_dna<N, true, false, 1, false, TH, 1, false, true>), dim3(nwg), dim3(64), 0, stream, a); \
+    else hipLaunchKernelGGL((k_thorough_dna<N, true, false, 1, false, TH, 1, true, true>), dim3(nwg), dim3(64), 0, stream, a);           \
+  } while (0)
+  if (nch == 1) TIPD_L(1, false);
+  else if (nch == 2 && tailh) hipLaunchKernelGGL((k_thorough_dna<2, true, false, 1, false, true, 1, false, true>), dim3(nwg), dim3(64), 0, stream, a);
+  else if (nch == 2) TIPD_L(2, false);
+  else if (tailh) TIPD_L(3, true);
+  else TIPD_L(3, false);
+#undef TIPD_L
+}
+#endif
 #else
 // ---------------------------------------------------------------------------------------------
 // Long windows (more than 24 x 64 sites): same algorithm, the sumtable lives in an HBM slab
@@ -1403,19 +1461,27 @@ __global__ void __launch_bounds__(64, 2) k_thorough_dna_long(const ThArgs a) {
 
 }  // namespace
 
+// thorough_dna_tipd.hip: the TIPD instantiations (NCH 1 .. 3, both Newton forms); args = this unit's ThArgs
+void launch_dna_tipd(hipStream_t stream, int nch, bool tailh, bool newton_lds, uint32_t nwg, const void* args);
+
 namespace {
 
 __global__ void __launch_bounds__(256) k_pair_class(const epa_pair* __restrict__ pairs, uint64_t n,
                                                    const uint32_t* __restrict__ win_span, int states,
+                                                   const uint32_t* __restrict__ tip_row,
                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ idx,
                                                    uint32_t* __restrict__ hist) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const int cls = i < n ? epa_span_class(states, win_span[pairs[i].seq_id]) : -1;
+  int cls = -1;
   if (i < n) {
+    const epa_pair pr = pairs[i];
+    cls = epa_span_class(states, win_span[pr.seq_id]);
+    // tip_row (null: no tip-distal keys in this call): the branch ends in a tip -> the class's TIPD half
+    if (tip_row && epa_tip_class_ok(cls) && tip_row[pr.branch_id] != 0xffffffffu) cls = epa_tip_class(cls);
     if (keys) { keys[i] = (uint32_t)cls; idx[i] = (uint32_t)i; }
   }
   if (hist) {
-    for (int c = 0; c < EPA_N_CLS; ++c) {
+    for (int c = 0; c < EPA_N_CLSX; ++c) {
       const unsigned long long bal = __ballot(cls == c);
       if (bal && (threadIdx.x & 63) == 0) atomicAdd(&hist[c], (uint32_t)__popcll(bal));
     }
@@ -1426,8 +1492,15 @@ __global__ void __launch_bounds__(256) k_pair_class(const epa_pair* __restrict__
 // Newton table by DPP unless the context option "newton_lds" asks for the LDS form (same results).  (--raxml-blo,
 // LOCAL, stays on the LDS form: this compiler's register allocator crashes on its DPP instantiations under the
 // iterative-ilp scheduler.)
+// tipd: the launch's pairs all have a tip on the distal side -> the TIPD instantiations (NCH <= 3, no +I)
 template <int NCH, bool ZERO0, bool INV, int NW, bool LOCAL = false, bool TAILH = false>
-void launch_dna(const epa_ctx* ctx, uint32_t nwg, const ThArgs& a) {
+void launch_dna(const epa_ctx* ctx, uint32_t nwg, const ThArgs& a, bool tipd = false) {
+  if constexpr (ZERO0 && !INV && NW == 1 && !LOCAL && NCH <= 3 && TH_WAVES < 3) {
+    if (tipd) {
+      launch_dna_tipd(ctx->stream, NCH, TAILH, ctx->opt.newton_lds != 0, nwg, &a);
+      return;
+    }
+  }
   if constexpr (ZERO0 && NW == 1 && !LOCAL && TH_WAVES < 3) {
     if (!ctx->opt.newton_lds) {
       hipLaunchKernelGGL((k_thorough_dna<NCH, ZERO0, INV, NW, LOCAL, TAILH, 1, true>), dim3(nwg), dim3(64), 0, ctx->stream, a);
@@ -1441,8 +1514,13 @@ void launch_dna(const epa_ctx* ctx, uint32_t nwg, const ThArgs& a) {
 
 // One launch per span class present (see epa_span_class).  `order` = this class's pair indices
 // in their original (branch-major) order, null when the launch covers all pairs.
-static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t max_span) {
+// tipd: the TIPD half of a single-wave class, on the bank's side stream (the caller has made it ctx->stream): the
+// second eight work counters, cleared here unless the caller says they still are
+static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t max_span, bool tipd = false,
+                                     bool dual = false, bool side_ctr_clean = false) {
   const uint64_t n_pairs = a.n_pairs;
+  if (tipd && !(epa_tip_class_ok(cls) && ctx->dna.ng == 1 && ctx->dna_zero0 && ctx->blo.sliding && !a.cinv))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "thorough: tip-distal launch outside the classes the TIPD kernels serve");
   // Grid: 2048 wavefronts are resident (8 per CU, 2 per SIMD at this kernel's VGPR budget), i.e.
   // 2048 / NW workgroups.  Oversubscribing the resident set lets the hardware dispatcher do the
   // load balancing (pairs differ 10x in cost): a finished workgroup's slot is refilled at once.
@@ -1468,8 +1546,13 @@ static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t m
     a.qctr = nullptr;                                                                              \
     if ((NW_) == 1) {                                                                              \
       TH_TIMING_ALLOC                                                                              \
-      { const int zr_ = epa_th_ctr_reset(ctx); if (zr_) return zr_; }                                  \
-      a.qctr = epa_th_ctr(ctx);                                                                        \
+      if (tipd) {                                                                                  \
+        if (!side_ctr_clean) { const int zr_ = epa_zero_async(ctx, epa_th_ctr(ctx) + 8, 32); if (zr_) return zr_; }  \
+        a.qctr = epa_th_ctr(ctx) + 8;                                                              \
+      } else {                                                                                     \
+        { const int zr_ = epa_th_ctr_reset(ctx, dual ? 32 : 64); if (zr_) return zr_; }            \
+        a.qctr = epa_th_ctr(ctx);                                                                  \
+      }                                                                                            \
       want = th_grid_waves ? th_grid_waves : 1024 * TH_WAVES;                                                   \
     }                                                                                              \
     if (want > n_pairs) want = n_pairs;                                                            \
@@ -1482,11 +1565,11 @@ static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t m
     else if (tailh && TH_ && ctx->dna_zero0 && ctx->blo.sliding && a.cinv)                                        \
       launch_dna<N, true, true, 1, false, TH_>(ctx, nwg, a);                                                       \
     else if (tailh && TH_ && ctx->dna_zero0 && ctx->blo.sliding)                                                   \
-      launch_dna<N, true, false, 1, false, TH_>(ctx, nwg, a);                                                      \
+      launch_dna<N, true, false, 1, false, TH_>(ctx, nwg, a, tipd);                                                \
     else if (!ctx->blo.sliding && a.cinv) launch_dna<N, true, true, NW_, true>(ctx, nwg, a);                       \
     else if (!ctx->blo.sliding) launch_dna<N, true, false, NW_, true>(ctx, nwg, a);                                \
     else if (a.cinv) launch_dna<N, true, true, NW_>(ctx, nwg, a);                                                  \
-    else if (ctx->dna_zero0) launch_dna<N, true, false, NW_>(ctx, nwg, a);                                         \
+    else if (ctx->dna_zero0) launch_dna<N, true, false, NW_>(ctx, nwg, a, tipd);                                   \
     else launch_dna<N, false, false, NW_>(ctx, nwg, a);                                                            \
   } while (0)
   // half-chunk tail (TAILH), classes 10 / 11: every window of the class ends within 32 sites of its
@@ -1612,6 +1695,9 @@ static ThArgs dna_args(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* or
   a.spec_max = 0;
   for (int i = 0; i < 9; ++i) a.xcum[i] = ctx->xcd_cum[i];
   a.xstamp = 0;
+  a.tip_row = ctx->tip_row;
+  a.tipmask = ctx->tipmask;
+  a.tipd = ctx->tipd;
   return a;
 }
 
@@ -1655,22 +1741,26 @@ int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, con
     return launch_thorough_generic(ctx, d_pairs, n_pairs, d_codes, d_begin, d_span, max_span, d_out, d_stats);
   }
   // ---- span classes present in this call
-  uint32_t hist[EPA_N_CLS] = {};
+  uint32_t hist[EPA_N_CLSX] = {};
   const int cmax = epa_span_class(ctx->s, max_span);
+  // tip-distal keys (epa_tipd_active): pairs whose branch ends in a tip are a launch of their own per class
+  const bool tipd = epa_tipd_active(ctx) && TH_WAVES < 3;
+  const uint32_t* tip_row = tipd ? ctx->tip_row : nullptr;
   // cls_hist: the caller's histogram of exactly these pairs (the fused chunk body read it back with the candidate
   // count: no round trip here); trusted only if it adds up to n_pairs
   uint64_t given = 0;
-  if (cls_hist) for (int c = 0; c < EPA_N_CLS; ++c) given += cls_hist[c];
+  if (cls_hist) for (int c = 0; c < EPA_N_CLSX; ++c) given += cls_hist[c];
   const bool cached = cls_hist && given == n_pairs && n_pairs != 0;
   if (cached) {
-    for (int c = 0; c < EPA_N_CLS; ++c) hist[c] = cls_hist[c];
-  } else if (cmax == 0) {
+    for (int c = 0; c < EPA_N_CLSX; ++c) hist[c] = cls_hist[c];
+  } else if (cmax == 0 && !tipd) {
     hist[0] = (uint32_t)n_pairs;  // every window is in the smallest class
   }
   // scratch 8: [hist 64 B | keys n | idx n | keys_out n | order n | rocprim temp]
   size_t temp_bytes = 0;
   (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n_pairs, 0, 4, ctx->stream);
+                                  (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n_pairs, 0, 5, ctx->stream);
+  auto sp_tips = [](const uint32_t* h) { for (int c = EPA_N_CLS; c < EPA_N_CLSX; ++c) if (h[c]) return true; return false; };
   const size_t nb = (sizeof(uint32_t) * n_pairs + 255) & ~(size_t)255;
   uint32_t* d_hist = nullptr;
   uint32_t *d_keys = nullptr, *d_idx = nullptr, *d_keys2 = nullptr, *d_order = nullptr;
@@ -1684,41 +1774,67 @@ int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, con
   };
   const dim3 cgrid((uint32_t)((n_pairs + 255) / 256));
   bool have_keys = false;
-  if (!cached && cmax != 0) {  // pairs from the caller: histogram (and keys) in one pass, one round trip
+  if (!cached && (cmax != 0 || tipd)) {  // pairs from the caller: histogram (and keys) in one pass, one round trip
     int rc = carve();
     if (rc) return rc;
-    EPA_HIP(ctx, hipMemsetAsync(d_hist, 0, 64, ctx->stream));
-    hipLaunchKernelGGL(k_pair_class, cgrid, dim3(256), 0, ctx->stream, d_pairs, n_pairs, d_span, ctx->s, d_keys,
+    EPA_HIP(ctx, hipMemsetAsync(d_hist, 0, 128, ctx->stream));
+    hipLaunchKernelGGL(k_pair_class, cgrid, dim3(256), 0, ctx->stream, d_pairs, n_pairs, d_span, ctx->s, tip_row, d_keys,
                        d_idx, d_hist);
     EPA_HIP(ctx, hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, ctx->stream));
     EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     have_keys = true;
   }
-  int present = 0;
-  for (int c = 0; c < EPA_N_CLS; ++c) present += hist[c] != 0;
+  int present = 0, spans = 0;   // launches; span classes among them (a class and its tip-distal half count once)
+  for (int c = 0; c < EPA_N_CLSX; ++c) present += hist[c] != 0;
+  for (int c = 0; c < EPA_N_CLS; ++c) spans += (hist[c] != 0 || (epa_tip_class_ok(c) && hist[epa_tip_class(c)] != 0));
   const uint32_t* order = nullptr;
   if (present > 1) {  // stable partition by class: branch-major order survives inside a class
     if (!have_keys) {
       int rc = carve();
       if (rc) return rc;
+      // (a cached histogram with tip-distal classes comes from a selection of this context: the same tip_row)
       hipLaunchKernelGGL(k_pair_class, cgrid, dim3(256), 0, ctx->stream, d_pairs, n_pairs, d_span, ctx->s,
-                         d_keys, d_idx, (uint32_t*)nullptr);
+                         sp_tips(hist) ? ctx->tip_row : tip_row, d_keys, d_idx, (uint32_t*)nullptr);
     }
     void* temp = (char*)d_order + nb;
-    EPA_HIP(ctx, rocprim::radix_sort_pairs<epa_radix_cfg>(temp, temp_bytes, d_keys, d_keys2, d_idx, d_order, (size_t)n_pairs, 0, 4,
+    EPA_HIP(ctx, rocprim::radix_sort_pairs<epa_radix_cfg>(temp, temp_bytes, d_keys, d_keys2, d_idx, d_order, (size_t)n_pairs, 0, 5,
                                            ctx->stream));
     order = d_order;
   }
   epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_THOROUGH));
   int rc = EPA_OK;
   uint64_t off = 0;
-  ctx->xstamp_ok = present == 1;
+  // the XCD stamps mean something when the call is one span class: one launch, or a class and its tip-distal half,
+  // which run side by side with the same shares and stamp the same words (start: either; last exit of an XCD: the
+  // later of the two, atomicMax) -- the feedback then sees how fast each XCD went through its share of both lists
+  ctx->xstamp_ok = spans == 1;
+  // tip-distal launches go to the bank's side stream, ordered behind everything queued so far and not behind the
+  // row-form launch of their class: each of the two fills the other's draining tail, as the launches of consecutive
+  // chunks do.  The caller's stream waits for the side stream before anything that follows.
+  const bool dual = sp_tips(hist) && ctx->s == 4;
+  hipStream_t const main_stream = ctx->stream;
+  hipStream_t side = nullptr;
+  bool side_clean = false;
+  if (dual) {
+    const int bk = ctx->bank;
+    if (!ctx->side_stream[bk]) {
+      EPA_HIP(ctx, hipStreamCreateWithFlags(&ctx->side_stream[bk], hipStreamNonBlocking));
+      EPA_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork[bk], hipEventDisableTiming));
+      EPA_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join[bk], hipEventDisableTiming));
+    }
+    side = ctx->side_stream[bk];
+    side_clean = ctx->clean_ctr[bk];   // chunk_body_begin cleared all sixteen counters behind the selection
+    EPA_HIP(ctx, hipEventRecord(ctx->ev_fork[bk], main_stream));
+    EPA_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_fork[bk], 0));
+  }
   // window bound of a class (slab sizing of the 20-state LDS kernel, the long-window kernel)
   static const uint32_t dna_bound[EPA_N_CLS] = {64, 128, 192, 256, 384, 512, 768, 1024, 1536, 0xffffffffu, 96, 160};
-  for (int c = 0; c < EPA_N_CLS && rc == EPA_OK; ++c) {
-    if (!hist[c]) continue;
+  for (int key = 0; key < EPA_N_CLSX && rc == EPA_OK; ++key) {
+    if (!hist[key]) continue;
+    const int c = epa_base_class(key);
+    const bool tip = key >= EPA_N_CLS;
     const uint32_t* ord = order ? order + off : nullptr;
-    off += hist[c];
+    off += hist[key];
     if (ctx->s == 20) {
       // matrix-core kernel (sumtable in registers): windows up to 384 sites with 4 rate categories, up to 256
       // with 8 (+G8, +R5 ..); longer ones, or all of them with EPA_AA_VALU=1 (A/B switch, 4 categories), the
@@ -1729,18 +1845,26 @@ int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, con
       const uint32_t mfma_max = ctx->c == 4 ? 384u : 256u;
       // (the VALU kernel has no --raxml-blo instantiation: the A/B switch applies to the sliding rule only)
       if (bound <= mfma_max && (!aa_valu || !ctx->blo.sliding || ctx->c != 4))
-        rc = launch_thorough_aa_mfma(ctx, d_pairs, ord, hist[c], d_codes, d_begin, d_span, bound, d_out, d_stats);
+        rc = launch_thorough_aa_mfma(ctx, d_pairs, ord, hist[key], d_codes, d_begin, d_span, bound, d_out, d_stats);
       else if (ctx->c == 4 && ctx->blo.sliding)
-        rc = launch_thorough_aa(ctx, d_pairs, ord, hist[c], d_codes, d_begin, d_span, bound,
+        rc = launch_thorough_aa(ctx, d_pairs, ord, hist[key], d_codes, d_begin, d_span, bound,
                                 bound <= EPA_AA_LDS_MAX_SPAN, d_out, d_stats);
       else
-        rc = launch_thorough_generic(ctx, d_pairs, hist[c], d_codes, d_begin, d_span, bound, d_out, d_stats, ord, true);
+        rc = launch_thorough_generic(ctx, d_pairs, hist[key], d_codes, d_begin, d_span, bound, d_out, d_stats, ord, true);
       continue;
     }
     ThArgs a = dna_args(ctx, d_pairs, ord, d_codes, d_begin, d_span, d_out, d_stats);
-    a.n_pairs = hist[c];
-    a.xstamp = (present == 1 && ctx->dna.ng == 1 && (c <= 2 || c == 10 || c == 11)) ? 1u : 0u;
-    rc = launch_thorough_dna_class(ctx, a, c, std::min(max_span, dna_bound[c]));
+    a.n_pairs = hist[key];
+    a.xstamp = (spans == 1 && ctx->dna.ng == 1 && (c <= 2 || c == 10 || c == 11)) ? ((tip && hist[c]) ? 2u : 1u) : 0u;
+    if (tip) ctx->stream = side;
+    rc = launch_thorough_dna_class(ctx, a, c, std::min(max_span, dna_bound[c]), tip, dual, side_clean);
+    if (tip) { ctx->stream = main_stream; side_clean = false; }
+  }
+  if (dual) {
+    const int bk = ctx->bank;
+    EPA_HIP(ctx, hipEventRecord(ctx->ev_join[bk], side));
+    EPA_HIP(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[bk], 0));
+    ctx->clean_ctr[bk] = false;   // the second eight counters are used now
   }
   epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_THOROUGH));
   if (rc) return rc;

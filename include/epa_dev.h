@@ -237,6 +237,10 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
  *   "newton_lds"        1: the single-wave 4-state Newton kernels (windows up to 256 sites, exact zero eigenvalue,
  *                          sliding BLO) read their per-evaluation table through LDS instead of broadcasting it from registers
  *                          by DPP (default 0: DPP; bit-identical results)
+ *   "tip_distal"        0: every pair on the row form of the single-wave 4-state Newton kernels (default 1: pairs whose
+ *                          branch ends in a tip -- contexts created from the tree -- are launched apart on kernels that
+ *                          read the tip's 4-bit state set per site instead of 16 rows of its eigen image; bit-identical
+ *                          results)
  * Unknown key: EPA_ERR_INVALID_ARG.
  */
 int epa_dev_set_option(epa_ctx* ctx, const char* key, int value);

@@ -12,14 +12,16 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin/"
-obj = os.path.join(ROOT, "epa_ng_amd", "build", "thorough_dna.o")
-with tempfile.TemporaryDirectory() as d:
-    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
-    subprocess.check_call([LLVM + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, obj])
-    subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    asm = subprocess.check_output([LLVM + "llvm-objdump", "-d", co], text=True)
-
+# the Newton kernels' objects: the main unit and the two units of the TIPD instantiations
+asm = ""
+for name in ("thorough_dna.o", "thorough_dna_tipd.o", "thorough_dna_tipd2h.o"):
+    obj = os.path.join(ROOT, "epa_ng_amd", "build", name)
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
+        subprocess.check_call([LLVM + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, obj])
+        subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        asm += subprocess.check_output([LLVM + "llvm-objdump", "-d", co], text=True) + "\n"
 
 def vregs(op):
     m = re.match(r"v\[(\d+):(\d+)\]", op.strip())
