@@ -119,6 +119,7 @@ def dev_lib():
         L.epa_dev_rell_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                            C.c_uint64, C.c_void_p]
+        L.epa_dev_rell_tests.argtypes = L.epa_dev_rell_support.argtypes + [C.c_void_p, C.c_void_p]
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -539,6 +540,30 @@ class Evaluator:
         self._check(self.L.epa_dev_rell_support(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                                 _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
                                                 int(replicates), int(seed), _ptr(out)))
+        return out
+
+    def rell_tests(self, pairs, pendant, distal, codes, win_begin, win_span, replicates, seed=1, stream_id=None,
+                   proximal=None, want=("support", "elw", "p_sh"), Q=None):
+        """RELL support, expected likelihood weight and SH test p-value from the same replicates (epa_dev_rell_tests)
+        -> dict of float64 [n] arrays, one per name in `want`.  "support" has the bits of rell_support(); "elw" is the
+        likelihood weight ratio averaged over the replicates; "p_sh" the fraction of replicates in which the entry's
+        centred score lies as far below the best as observed, or further (include/epa_dev.h has the exact definitions)."""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs)
+        want = tuple(want)
+        unknown = [w for w in want if w not in ("support", "elw", "p_sh")]
+        if unknown:
+            raise ValueError("rell_tests: unknown output %r" % (unknown[0],))
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
+        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        if isinstance(stream_id, (np.ndarray, list, tuple)):
+            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
+        out = {w: np.empty(n, np.float64) for w in want}
+        self._layout(codes)
+        self._check(self.L.epa_dev_rell_tests(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                              _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
+                                              int(replicates), int(seed), _ptr(out.get("support")), _ptr(out.get("elw")),
+                                              _ptr(out.get("p_sh"))))
         return out
 
     def set_heuristic(self, mode="dynamic", param=0.0):

@@ -1887,6 +1887,42 @@ extern "C" int epa_dev_rell_support(epa_ctx* ctx, const epa_pair* pairs, const d
   return EPA_OK;
 }
 
+extern "C" int epa_dev_rell_tests(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                  const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
+                                  const uint32_t* win_span, uint32_t Q, const uint64_t* stream_id, uint32_t replicates,
+                                  uint64_t seed, double* support, double* elw, double* p_sh) {
+  if (!ctx || (n && (!pairs || !pendant || !distal || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (!support && !elw && !p_sh) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: support, elw and p_sh are all null");
+  if (replicates == 0 || replicates > (1u << 20))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: replicates must be 1 .. 2^20");
+  if (n == 0) return EPA_OK;
+  if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: more than 2^32 - 1 entries in one call");
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  EntryStage st;
+  int rc = stage_entries(ctx, "rell_tests", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
+  if (rc) return rc;
+  const uint64_t* d_sid = stream_id ? (const uint64_t*)epa_to_device(ctx, 17, stream_id, sizeof(uint64_t) * Q) : nullptr;
+  if (stream_id && !d_sid) return epa_fail(ctx, EPA_ERR_HIP, "rell_tests input upload failed");
+  // outputs in host memory are staged in scratch 3, one [n] block each
+  double* out[3] = {support, elw, p_sh};
+  double* d_out[3] = {nullptr, nullptr, nullptr};
+  size_t staged = 0;
+  for (int i = 0; i < 3; ++i) staged += out[i] && !epa_is_device_ptr(out[i]);
+  double* d_stage = staged ? (double*)epa_scratch(ctx, 3, sizeof(double) * n * staged) : nullptr;
+  if (staged && !d_stage) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_tests out)");
+  for (int i = 0, k = 0; i < 3; ++i)
+    if (out[i]) d_out[i] = epa_is_device_ptr(out[i]) ? out[i] : d_stage + (size_t)n * k++;
+  rc = launch_rell_tests(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, st.hs, Q, d_sid,
+                         replicates, seed, d_out[0], d_out[1], d_out[2]);
+  if (rc) return rc;
+  for (int i = 0; i < 3; ++i)
+    if (out[i] && d_out[i] != out[i])
+      EPA_HIP(ctx, hipMemcpyAsync(out[i], d_out[i], sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return EPA_OK;
+}
+
 extern "C" int epa_dev_select_candidates(epa_ctx* ctx, const double* lnl, uint32_t Q,
                                          double threshold, epa_pair* pairs, uint64_t max_pairs,
                                          uint64_t* n_pairs) {
@@ -2872,6 +2908,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "site_lnl")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SITES]][epa_ctx::T_SITES];
   else if (!strcmp(which, "rell")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL]][epa_ctx::T_RELL];
   else if (!strcmp(which, "marginal")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_MARGINAL]][epa_ctx::T_MARGINAL];
+  else if (!strcmp(which, "rell_tests")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_TESTS]][epa_ctx::T_RELL_TESTS];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

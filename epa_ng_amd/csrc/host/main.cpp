@@ -36,10 +36,14 @@ static void usage() {
       "                        from N (1 .. 1048576) resamplings of the per-site log-likelihoods; written as a sixth\n"
       "                        field \"rell_support\".  Two steps: place first, then --rescore out.jplace --rell N\n"
       "  --rell-seed S         seed of the resampling (default 1); the result depends on N, S and the input file alone\n"
+      "  --rell-tests          with --rescore --rell N: two more fields from the same N replicates, directly after\n"
+      "                        \"rell_support\": \"elw\", the expected likelihood weight (the like_weight_ratio averaged over\n"
+      "                        the replicates; its cumulative sum gives a confidence set), and \"p_sh\", the p-value of the\n"
+      "                        Shimodaira-Hasegawa test of the row against the best row of its placement object\n"
       "  --posterior           with --rescore: marginal likelihood of every row's edge, integrated over the attachment point\n"
       "                        (uniform on the edge) and the pendant length (exponential prior), and its normalisation over\n"
       "                        the rows of the placement object; written as the fields \"marginal_like\" and \"post_prob\"\n"
-      "                        (after \"rell_support\" when --rell is given).  Only edge_num of a row enters them\n"
+      "                        (after \"rell_support\", \"elw\", \"p_sh\" when --rell, --rell-tests are given).  Only edge_num of a row enters them\n"
       "  --prior-mean M        mean of the pendant prior (default: the mean branch length of the reference tree)\n"
       "  --posterior-nodes KX,KP  Gauss-Legendre nodes along the edge x Gauss-Laguerre pendant nodes, 1 .. 64 each (default 8,16)\n"
       "  --precision N         output digits (default 10)\n"
@@ -114,6 +118,7 @@ int main(int argc, char** argv) {
     else if (a == "--rescore") rescore_file = need(i);
     else if (a == "--rell") { opt.rell_replicates = (unsigned)std::stoul(need(i)); rell_given = true; }
     else if (a == "--rell-seed") { opt.rell_seed = std::stoull(need(i)); rell_given = true; }
+    else if (a == "--rell-tests") opt.rell_tests = true;
     else if (a == "--posterior") opt.posterior = true;
     else if (a == "--prior-mean") {
       const std::string v = need(i);
@@ -199,6 +204,11 @@ int main(int argc, char** argv) {
   }
   if (rell_given && (opt.rell_replicates == 0 || opt.rell_replicates > (1u << 20))) {
     std::cerr << "--rell: the number of replicates must be 1 .. 1048576 (--rell-seed needs --rell N)\n";
+    return 1;
+  }
+  if (opt.rell_tests && (rescore_file.empty() || opt.rell_replicates == 0)) {
+    std::cerr << "--rell-tests adds elw and p_sh from the replicates of --rell and needs them: --rescore out.jplace --rell N "
+                 "--rell-tests\n";
     return 1;
   }
   if ((prior_given || nodes_given) && !opt.posterior) {

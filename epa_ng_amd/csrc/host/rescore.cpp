@@ -3,7 +3,8 @@
 // false, src/tree/Tiny_Tree.cpp:186-204); the chunk loop around it reads the query file like simple_mpi (place.cpp)
 // does -- same reader, same premasking -- and picks the sequences the jplace names.  With --rell N the same rows also
 // get their RELL bootstrap support (epa_dev_rell_support) among the rows of their placement object; the object's index
-// in the input file is its random stream, so the result does not depend on --chunk-size.  With --posterior the rows get
+// in the input file is its random stream, so the result does not depend on --chunk-size.  --rell-tests makes that one
+// call epa_dev_rell_tests: expected likelihood weight and SH p-value from the same replicates.  With --posterior the rows get
 // their marginal likelihood (epa_dev_marginal_like: only edge_num comes from the row; Gauss-Legendre x Gauss-Laguerre
 // rule, exponential pendant prior) and post_prob, its normalisation over the rows of the placement object.
 #include <chrono>
@@ -140,13 +141,19 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
                                     lnl.data());
     if (rc != EPA_OK)
       throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
-    std::vector<double> support;
+    std::vector<double> support, elw, p_sh;
     if (options.rell_replicates) {
       std::vector<uint64_t> stream_id(target.begin(), target.end());
       support.resize(pairs.size());
-      const int rrc = epa_dev_rell_support(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
-                                           enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
-                                           stream_id.data(), options.rell_replicates, options.rell_seed, support.data());
+      if (options.rell_tests) { elw.resize(pairs.size()); p_sh.resize(pairs.size()); }
+      const int rrc = options.rell_tests
+          ? epa_dev_rell_tests(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
+                               enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
+                               stream_id.data(), options.rell_replicates, options.rell_seed, support.data(), elw.data(),
+                               p_sh.data())
+          : epa_dev_rell_support(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
+                                 enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
+                                 stream_id.data(), options.rell_replicates, options.rell_seed, support.data());
       if (rrc != EPA_OK)
         throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rrc) + ")"};
     }
@@ -167,6 +174,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
       for (const Jplace_Row& r : input[target[q]].rows) {
         pq.emplace_back(r.edge_num, lnl[k], r.pendant_length, r.distal_length);
         if (!support.empty()) pq[pq.size() - 1].rell_support(support[k]);
+        if (!elw.empty()) { pq[pq.size() - 1].elw(elw[k]); pq[pq.size() - 1].p_sh(p_sh[k]); }
         if (!marginal.empty()) pq[pq.size() - 1].marginal_like(marginal[k]);
         ++k;
       }
@@ -199,7 +207,8 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
   std::ofstream os(out_path);
   if (!os) throw std::runtime_error{"cannot open " + out_path};
   write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision, nullptr,
-               (options.rell_replicates ? kJplaceRell : 0u) | (options.posterior ? kJplacePosterior : 0u));
+               (options.rell_replicates ? kJplaceRell : 0u) | (options.rell_tests ? kJplaceRellTests : 0u) |
+                   (options.posterior ? kJplacePosterior : 0u));
   os.flush();
   if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }
   st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();

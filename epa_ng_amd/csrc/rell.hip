@@ -22,7 +22,17 @@
 // and carries its running best (score, branch, position) across the tiles.  A window longer than LDS_SITES does not
 // fit the LDS tile; its draws gather from the rows in HBM / L2 instead.  Wins are counted with LDS atomics for up to
 // WINS_LDS entries per query, beyond that with global atomics.
+//
+// k_rell_tests (epa_dev_rell_tests): the same replicates also give the expected likelihood weight and the SH p-value of
+// every entry.  Same shape as k_rell; the new part is that a replicate needs all of its query's scores twice.  A query
+// of up to RES_TILES tiles (eight entries) keeps its scores in registers; a longer one sweeps its tiles twice and
+// regenerates the draws: sweep 1 carries the running winner, the running maximum m with the sum Z = sum exp(s - m) rescaled whenever m
+// moves, and max c; sweep 2 forms the weights exp(s - m) / Z and the comparisons t >= T.  The weights of the 256
+// replicate lanes are added by epa_wave::wave_sum and the four wave partials in wave order, the rounds in round order,
+// all by one thread per entry: a fixed order, no floating-point atomics.  The observed sums L and the thresholds T come
+// from two small kernels in front (k_rell_observed, k_rell_threshold), once per entry.
 #include "epa_dev_internal.hpp"
+#include "wave_util.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -39,6 +49,8 @@ constexpr int RELL_THREADS = 256;
 constexpr int TE = 4;                    // entries per tile
 constexpr uint32_t LDS_SITES = 1536;     // 1536 sites x 4 entries x 8 B = 48 KiB
 constexpr uint32_t WINS_LDS = 1024;      // entries per query whose wins are counted in LDS
+constexpr int RES_TILES = 2;             // k_rell_tests: tiles of a query whose scores stay in registers between the sweeps
+constexpr uint32_t ACC_LDS = 256;       // k_rell_tests: entries per query whose three accumulators live in LDS
 constexpr size_t ROWS_BUDGET = (size_t)128 << 20;   // bytes of site rows per batch
 
 struct RellGroup {
@@ -56,6 +68,14 @@ struct RellArgs {
   uint32_t pos0, pitch;
   uint32_t R, k0, k1;
   uint32_t* wins;             // [n] by sorted position
+};
+
+struct RellTestsArgs {
+  RellArgs r;
+  const double* L;            // [n] by sorted position: observed lnL (k_rell_observed)
+  const double* T;            // [n]: the query's largest L minus the entry's (k_rell_threshold)
+  double* elw;                // [n]: sum of the weights over the replicates
+  uint32_t* sh;               // [n]: replicates with t >= T
 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
@@ -99,6 +119,61 @@ __global__ void __launch_bounds__(256) k_rell_support(const uint32_t* __restrict
   if (i < n) support[order[i]] = (double)wins[i] / R;
 }
 
+// ---- what k_rell and k_rell_tests share: one tile of entries staged, scored in a replicate, and entered for the winner
+
+// the tile's [site][TE] matrix (entries from te on: 0.0); the caller puts a barrier in front and behind
+__device__ __forceinline__ void rell_stage_tile(double* mat, const double* __restrict__ rows, uint32_t pitch, uint32_t e0,
+                                                uint32_t te, uint32_t nq, uint32_t tid) {
+  for (uint32_t i = tid; i < nq * TE; i += RELL_THREADS) {
+    const uint32_t k = i / nq, j = i - k * nq;   // consecutive threads read consecutive sites of one row
+    mat[j * TE + k] = k < te ? rows[(size_t)(e0 + k) * pitch + j] : 0.0;
+  }
+}
+
+// sc[k]: the score of entry e0 + k in replicate r of stream (tlo, thi) under key (k0, k1)
+__device__ __forceinline__ void rell_tile_scores(const double* mat, const double* __restrict__ rows, uint32_t pitch,
+                                                 uint32_t e0, uint32_t te, uint32_t nq, bool in_lds, uint32_t r,
+                                                 uint32_t tlo, uint32_t thi, uint32_t k0, uint32_t k1, double sc[TE]) {
+#pragma unroll
+  for (int k = 0; k < TE; ++k) sc[k] = 0.0;
+  for (uint32_t d = 0; d < nq; d += 4) {
+    uint32_t w[4];
+    philox4x32_10(d >> 2, r, tlo, thi, k0, k1, w);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (d + u < nq) {
+        const uint32_t j = __umulhi(w[u], nq);
+        if (in_lds) {
+#pragma unroll
+          for (int k = 0; k < TE; ++k) sc[k] += mat[j * TE + k];   // padded entries add 0.0 to unused scores
+        } else {
+#pragma unroll
+          for (int k = 0; k < TE; ++k)
+            if ((uint32_t)k < te) sc[k] += rows[(size_t)(e0 + k) * pitch + j];
+        }
+      }
+    }
+  }
+}
+
+// the running winner: the largest score, ties to the smaller branch id, then to the smaller entry index
+__device__ __forceinline__ void rell_tile_winner(const double sc[TE], bool first_tile, uint32_t e0, uint32_t te,
+                                                 const epa_pair* __restrict__ pairs, const uint32_t* __restrict__ ord,
+                                                 double& best_sc, uint32_t& best_br, uint32_t& best_k) {
+#pragma unroll
+  for (int k = 0; k < TE; ++k) {
+    if ((uint32_t)k < te) {
+      const uint32_t br = pairs[ord[e0 + k]].branch_id;
+      // positions of a group ascend with the entry index (stable sort): an equal branch keeps the earlier entry
+      if ((first_tile && k == 0) || sc[k] > best_sc || (sc[k] == best_sc && br < best_br)) {
+        best_sc = sc[k];
+        best_br = br;
+        best_k = e0 + k;
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(RELL_THREADS) k_rell(const RellArgs a) {
   __shared__ __attribute__((aligned(16))) double mat[LDS_SITES * TE];   // [site][TE]
   __shared__ uint32_t wins_l[WINS_LDS];
@@ -126,46 +201,13 @@ __global__ void __launch_bounds__(RELL_THREADS) k_rell(const RellArgs a) {
         // a query of one tile keeps it for all rounds of replicates; more tiles are staged again every round
         if (in_lds && (ntiles > 1 || rbase == 0)) {
           __syncthreads();
-          for (uint32_t i = tid; i < nq * TE; i += RELL_THREADS) {
-            const uint32_t k = i / nq, j = i - k * nq;   // consecutive threads read consecutive sites of one row
-            mat[j * TE + k] = k < te ? rows[(size_t)(e0 + k) * a.pitch + j] : 0.0;
-          }
+          rell_stage_tile(mat, rows, a.pitch, e0, te, nq, tid);
           __syncthreads();
         }
         if (!active) continue;
         double sc[TE];
-#pragma unroll
-        for (int k = 0; k < TE; ++k) sc[k] = 0.0;
-        for (uint32_t d = 0; d < nq; d += 4) {
-          uint32_t w[4];
-          philox4x32_10(d >> 2, r, tlo, thi, a.k0, a.k1, w);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (d + u < nq) {
-              const uint32_t j = __umulhi(w[u], nq);
-              if (in_lds) {
-#pragma unroll
-                for (int k = 0; k < TE; ++k) sc[k] += mat[j * TE + k];   // padded entries add 0.0 to unused scores
-              } else {
-#pragma unroll
-                for (int k = 0; k < TE; ++k)
-                  if ((uint32_t)k < te) sc[k] += rows[(size_t)(e0 + k) * a.pitch + j];
-              }
-            }
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < TE; ++k) {
-          if ((uint32_t)k < te) {
-            const uint32_t br = a.pairs[ord[e0 + k]].branch_id;
-            // positions of a group ascend with the entry index (stable sort): an equal branch keeps the earlier entry
-            if ((tile == 0 && k == 0) || sc[k] > best_sc || (sc[k] == best_sc && br < best_br)) {
-              best_sc = sc[k];
-              best_br = br;
-              best_k = e0 + k;
-            }
-          }
-        }
+        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+        rell_tile_winner(sc, tile == 0, e0, te, a.pairs, ord, best_sc, best_br, best_k);
       }
       if (active) {
         if (wins_lds) atomicAdd(&wins_l[best_k], 1u);
@@ -178,15 +220,199 @@ __global__ void __launch_bounds__(RELL_THREADS) k_rell(const RellArgs a) {
   }
 }
 
-}  // namespace
+// L[pos]: the site row of sorted position pos summed from site 0 on, one thread per row of the batch
+__global__ void __launch_bounds__(256) k_rell_observed(const double* __restrict__ rows, uint32_t pitch, uint32_t pos0,
+                                                       uint32_t npos, const uint32_t* __restrict__ order,
+                                                       const epa_pair* __restrict__ pairs, const uint32_t* __restrict__ span,
+                                                       double* __restrict__ L) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= npos) return;
+  const uint32_t nq = span[pairs[order[pos0 + i]].seq_id];
+  const double* __restrict__ row = rows + (size_t)i * pitch;
+  double s = 0.0;
+  for (uint32_t j = 0; j < nq; ++j) s += row[j];
+  L[pos0 + i] = s;
+}
 
-int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
-                const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                uint32_t replicates, uint64_t seed, double* d_support) {
-  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32
+// T[pos] = (the largest L of the query) - L[pos], one thread per query of the batch
+__global__ void __launch_bounds__(256) k_rell_threshold(const RellGroup* __restrict__ groups, uint32_t n_groups,
+                                                        const double* __restrict__ L, double* __restrict__ T) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n_groups) return;
+  const RellGroup grp = groups[g];
+  double mx = L[grp.start];
+  for (uint32_t k = 1; k < grp.count; ++k) mx = fmax(mx, L[grp.start + k]);
+  for (uint32_t k = 0; k < grp.count; ++k) T[grp.start + k] = mx - L[grp.start + k];
+}
+
+__global__ void __launch_bounds__(RELL_THREADS) k_rell_tests(const RellTestsArgs ta) {
+  __shared__ __attribute__((aligned(16))) double mat[LDS_SITES * TE];   // [site][TE]
+  __shared__ double part[2][RELL_THREADS / 64][TE];                      // [tile parity][wave][entry]: the waves' weight sums
+  __shared__ double elw_l[ACC_LDS];
+  __shared__ uint32_t wins_l[ACC_LDS], sh_l[ACC_LDS];
+  const RellArgs& a = ta.r;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint32_t flip = 0;
+  for (uint32_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+    const RellGroup grp = a.groups[g];
+    const uint32_t E = grp.count, nq = a.span[grp.q];
+    const uint64_t t = a.stream_id ? a.stream_id[grp.q] : (uint64_t)grp.q;
+    const uint32_t tlo = (uint32_t)t, thi = (uint32_t)(t >> 32);
+    const double* __restrict__ rows = a.rows + (size_t)(grp.start - a.pos0) * a.pitch;
+    const uint32_t* __restrict__ ord = a.order + grp.start;
+    const double* __restrict__ L = ta.L + grp.start;
+    const double* __restrict__ T = ta.T + grp.start;
+    const bool in_lds = nq <= LDS_SITES, acc_lds = E <= ACC_LDS;   // workgroup-uniform
+    const uint32_t ntiles = (E + TE - 1) / TE;
+    const bool resident = ntiles <= (uint32_t)RES_TILES;   // the query's scores stay in registers: no second sweep of draws
+    __syncthreads();   // the previous query's tile and accumulators are no longer read
+    if (acc_lds)
+      for (uint32_t i = tid; i < E; i += RELL_THREADS) { wins_l[i] = 0; sh_l[i] = 0; elw_l[i] = 0.0; }
+    __syncthreads();
+    for (uint32_t rbase = 0; rbase < a.R; rbase += RELL_THREADS) {
+      const uint32_t r = rbase + tid;
+      const bool active = r < a.R;
+      double sc[TE] = {0.0, 0.0, 0.0, 0.0};
+      double keep[RES_TILES][TE] = {};   // indexed by unrolled loops only: registers
+      // ---- sweep 1: the winner, m = max s with Z = sum exp(s - m), max c
+      double best_sc = 0.0, m = -INFINITY, Z = 0.0, cmax = -INFINITY;
+      uint32_t best_br = 0, best_k = 0;
+      for (uint32_t tile = 0; tile < ntiles; ++tile) {
+        const uint32_t e0 = tile * TE, te = min((uint32_t)TE, E - e0);
+        if (in_lds && (ntiles > 1 || rbase == 0)) {   // as k_rell: a query of one tile keeps it for all rounds
+          __syncthreads();
+          rell_stage_tile(mat, rows, a.pitch, e0, te, nq, tid);
+          __syncthreads();
+        }
+        if (!active) continue;
+        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+        if (resident) {
+#pragma unroll
+          for (int u = 0; u < RES_TILES; ++u)
+            if (tile == (uint32_t)u) {
+#pragma unroll
+              for (int k = 0; k < TE; ++k) keep[u][k] = sc[k];
+            }
+        }
+        rell_tile_winner(sc, tile == 0, e0, te, a.pairs, ord, best_sc, best_br, best_k);
+        double tm = sc[0];
+#pragma unroll
+        for (int k = 1; k < TE; ++k)
+          if ((uint32_t)k < te) tm = fmax(tm, sc[k]);
+        if (tm > m) {   // the sum so far refers to the old maximum (first tile: Z = 0 stays 0)
+          Z *= exp(m - tm);
+          m = tm;
+        }
+#pragma unroll
+        for (int k = 0; k < TE; ++k) {
+          if ((uint32_t)k < te) {
+            Z += exp(sc[k] - m);
+            const double c = sc[k] - L[e0 + k];
+            cmax = c > cmax ? c : cmax;
+          }
+        }
+      }
+      if (active) {
+        if (acc_lds) atomicAdd(&wins_l[best_k], 1u);
+        else atomicAdd(&a.wins[grp.start + best_k], 1u);
+      }
+      // ---- sweep 2: weights and comparisons, every lane of every wave takes part in the sums
+      for (uint32_t tile = 0; tile < ntiles; ++tile) {
+        const uint32_t e0 = tile * TE, te = min((uint32_t)TE, E - e0);
+        if (!resident) {
+          if (in_lds) {
+            __syncthreads();
+            rell_stage_tile(mat, rows, a.pitch, e0, te, nq, tid);
+            __syncthreads();
+          }
+          if (active) rell_tile_scores(mat, rows, a.pitch, e0, te, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+        } else {
+#pragma unroll
+          for (int u = 0; u < RES_TILES; ++u)
+            if (tile == (uint32_t)u) {
+#pragma unroll
+              for (int k = 0; k < TE; ++k) sc[k] = keep[u][k];
+            }
+        }
+        double w[TE];
+        uint32_t hits[TE];
+#pragma unroll
+        for (int k = 0; k < TE; ++k) {
+          const bool on = active && (uint32_t)k < te;
+          bool hit = false;
+          w[k] = 0.0;
+          if (on) {
+            w[k] = exp(sc[k] - m) / Z;
+            const double c = sc[k] - L[e0 + k];
+            const double tk = cmax - c;
+            hit = tk >= T[e0 + k];
+          }
+          hits[k] = (uint32_t)__popcll(__ballot(hit));
+        }
+        epa_wave::wave_sum2(w[0], w[1], w[0], w[1]);
+        epa_wave::wave_sum2(w[2], w[3], w[2], w[3]);
+        if (lane == 0) {
+#pragma unroll
+          for (int k = 0; k < TE; ++k) {
+            part[flip][wave][k] = w[k];
+            if (hits[k]) {
+              if (acc_lds) atomicAdd(&sh_l[e0 + k], hits[k]);
+              else atomicAdd(&ta.sh[grp.start + e0 + k], hits[k]);
+            }
+          }
+        }
+        __syncthreads();
+        if (tid < te) {   // one thread per entry: the waves in order, then onto the rounds before
+          const double s = ((part[flip][0][tid] + part[flip][1][tid]) + part[flip][2][tid]) + part[flip][3][tid];
+          if (acc_lds) elw_l[e0 + tid] += s;
+          else ta.elw[grp.start + e0 + tid] += s;
+        }
+        flip ^= 1u;   // the next tile's partials go to the other half: one barrier per tile is enough
+      }
+    }
+    __syncthreads();
+    if (acc_lds)
+      for (uint32_t i = tid; i < E; i += RELL_THREADS) {
+        a.wins[grp.start + i] = wins_l[i];
+        ta.sh[grp.start + i] = sh_l[i];
+        ta.elw[grp.start + i] = elw_l[i];
+      }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_rell_tests_out(const uint32_t* __restrict__ wins, const uint32_t* __restrict__ sh,
+                                                        const double* __restrict__ elw_sum, const uint32_t* __restrict__ order,
+                                                        uint32_t n, double R, double* __restrict__ support,
+                                                        double* __restrict__ elw, double* __restrict__ p_sh) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t e = order[i];
+  if (support) support[e] = (double)wins[i] / R;
+  if (elw) elw[e] = elw_sum[i] / R;
+  if (p_sh) p_sh[e] = (double)sh[i] / R;
+}
+
+// What launch_rell and launch_rell_tests share: the entries grouped by query, the groups dealt into batches of whole
+// queries, the site rows' scratch, the win counters cleared.  `who` names the entry point in error texts
+struct RellBatch {
+  size_t g0, g1;      // groups [g0, g1)
+  uint64_t rows;      // sorted positions of the batch
+  uint32_t pitch;     // its longest window
+};
+
+struct RellPlan {
+  std::vector<RellGroup> groups;
+  std::vector<RellBatch> batches;
+  RellGroup* d_groups = nullptr;
+  uint32_t *d_order = nullptr, *d_wins = nullptr;
+  double* d_rows = nullptr;
+};
+
+int rell_plan(epa_ctx* ctx, const char* who, const epa_pair* d_pairs, uint32_t n, const uint32_t* h_span, uint32_t Q,
+              RellPlan& plan) {
   const dim3 ngrid((n + 255) / 256);
-  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL));
+  std::vector<RellGroup>& groups = plan.groups;
+  std::vector<RellBatch>& batches = plan.batches;
   // ---- group by query: stable sort of the entry indices by seq_id
   int bits = 1;
   while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)Q) ++bits;
@@ -210,33 +436,21 @@ int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, 
   std::vector<uint32_t> bounds(2 * (size_t)Q);
   EPA_HIP(ctx, hipMemcpyAsync(bounds.data(), d_bounds, sizeof(uint32_t) * 2 * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
   EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<RellGroup> groups;
   uint64_t covered = 0;
   for (uint32_t q = 0; q < Q; ++q)
     if (bounds[Q + q] > bounds[q]) {
       groups.push_back(RellGroup{q, bounds[q], bounds[Q + q] - bounds[q]});
       covered += groups.back().count;
     }
-  if (covered != n) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_support: a sequence id is out of range");
+  if (covered != n) return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": a sequence id is out of range");
   RellGroup* d_groups = (RellGroup*)epa_scratch(ctx, 15, sizeof(RellGroup) * groups.size());
   if (!d_groups) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell groups)");
   EPA_HIP(ctx, hipMemcpyAsync(d_groups, groups.data(), sizeof(RellGroup) * groups.size(), hipMemcpyHostToDevice, ctx->stream));
 
   // ---- batches of whole queries: rows [positions][pitch], pitch = the batch's longest window
-  RellArgs a;
-  a.order = d_order;
-  a.pairs = d_pairs;
-  a.span = d_span;
-  a.stream_id = d_stream_id;
-  a.R = replicates;
-  a.k0 = (uint32_t)seed;
-  a.k1 = (uint32_t)(seed >> 32);
-  a.wins = d_wins;
-  struct Batch { size_t g0, g1; uint64_t rows; uint32_t pitch; };
-  std::vector<Batch> batches;
   size_t rows_bytes = 0;
   for (size_t g0 = 0; g0 < groups.size();) {
-    Batch b{g0, g0, 0, 1};
+    RellBatch b{g0, g0, 0, 1};
     while (b.g1 < groups.size()) {
       const uint32_t p = std::max(b.pitch, h_span[groups[b.g1].q]);
       if (b.g1 > g0 && (b.rows + groups[b.g1].count) * (uint64_t)p * sizeof(double) > ROWS_BUDGET) break;
@@ -248,24 +462,108 @@ int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, 
     batches.push_back(b);
     g0 = b.g1;
   }
-  double* d_rows = (double*)epa_scratch(ctx, 16, rows_bytes);
-  if (!d_rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell site rows)");
-  for (const Batch& b : batches) {
-    const uint32_t pos0 = groups[b.g0].start;
-    int rc = launch_site_lnl(ctx, d_pairs, d_pendant, d_distal, d_proximal, d_order + pos0, b.rows, d_codes, d_begin, d_span,
-                             b.pitch, false, d_rows, false);
+  plan.d_rows = (double*)epa_scratch(ctx, 16, rows_bytes);
+  if (!plan.d_rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell site rows)");
+  plan.d_groups = d_groups;
+  plan.d_order = d_order;
+  plan.d_wins = d_wins;
+  return EPA_OK;
+}
+
+// what does not change from batch to batch
+RellArgs rell_args(const RellPlan& plan, const epa_pair* d_pairs, const uint32_t* d_span, const uint64_t* d_stream_id,
+                   uint32_t replicates, uint64_t seed) {
+  RellArgs a{};
+  a.order = plan.d_order;
+  a.pairs = d_pairs;
+  a.span = d_span;
+  a.stream_id = d_stream_id;
+  a.rows = plan.d_rows;
+  a.R = replicates;
+  a.k0 = (uint32_t)seed;
+  a.k1 = (uint32_t)(seed >> 32);
+  a.wins = plan.d_wins;
+  return a;
+}
+
+// the batch's site rows computed and its part of the arguments set
+int rell_batch_rows(epa_ctx* ctx, const RellPlan& plan, const RellBatch& b, const epa_pair* d_pairs, const double* d_pendant,
+                    const double* d_distal, const double* d_proximal, const uint8_t* d_codes, const uint32_t* d_begin,
+                    const uint32_t* d_span, RellArgs& a) {
+  const uint32_t pos0 = plan.groups[b.g0].start;
+  int rc = launch_site_lnl(ctx, d_pairs, d_pendant, d_distal, d_proximal, plan.d_order + pos0, b.rows, d_codes, d_begin,
+                           d_span, b.pitch, false, plan.d_rows, false);
+  if (rc) return rc;
+  a.groups = plan.d_groups + b.g0;
+  a.n_groups = (uint32_t)(b.g1 - b.g0);
+  a.pos0 = pos0;
+  a.pitch = b.pitch;
+  return EPA_OK;
+}
+
+}  // namespace
+
+int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
+                const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
+                uint32_t replicates, uint64_t seed, double* d_support) {
+  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32
+  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL));
+  RellPlan plan;
+  int rc = rell_plan(ctx, "rell_support", d_pairs, n, h_span, Q, plan);
+  if (rc) return rc;
+  RellArgs a = rell_args(plan, d_pairs, d_span, d_stream_id, replicates, seed);
+  for (const RellBatch& b : plan.batches) {
+    rc = rell_batch_rows(ctx, plan, b, d_pairs, d_pendant, d_distal, d_proximal, d_codes, d_begin, d_span, a);
     if (rc) return rc;
-    a.groups = d_groups + b.g0;
-    a.n_groups = (uint32_t)(b.g1 - b.g0);
-    a.rows = d_rows;
-    a.pos0 = pos0;
-    a.pitch = b.pitch;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(a.n_groups, (uint64_t)ctx->n_cu * 8);
     hipLaunchKernelGGL(k_rell, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, a);
     EPA_HIP(ctx, hipGetLastError());
   }
-  hipLaunchKernelGGL(k_rell_support, ngrid, dim3(256), 0, ctx->stream, d_wins, d_order, n, (double)replicates, d_support);
+  hipLaunchKernelGGL(k_rell_support, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, plan.d_wins, plan.d_order, n,
+                     (double)replicates, d_support);
   epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL));
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}
+
+int launch_rell_tests(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                      const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
+                      const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
+                      uint32_t replicates, uint64_t seed, double* d_support, double* d_elw, double* d_p_sh) {
+  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32
+  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL_TESTS));
+  RellPlan plan;
+  int rc = rell_plan(ctx, "rell_tests", d_pairs, n, h_span, Q, plan);
+  if (rc) return rc;
+  // scratch 18: [L n | T n | weight sums n | SH counts n]; the two accumulators are cleared per call, L and T written in full
+  const size_t db = (sizeof(double) * (size_t)n + 255) & ~(size_t)255;
+  char* base = (char*)epa_scratch(ctx, 18, 3 * db + sizeof(uint32_t) * (size_t)n);
+  if (!base) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_tests accumulators)");
+  double *d_L = (double*)base, *d_T = (double*)(base + db), *d_sum = (double*)(base + 2 * db);
+  uint32_t* d_sh = (uint32_t*)(base + 3 * db);
+  EPA_HIP(ctx, hipMemsetAsync(d_sum, 0, db + sizeof(uint32_t) * (size_t)n, ctx->stream));
+  RellTestsArgs ta{};
+  ta.r = rell_args(plan, d_pairs, d_span, d_stream_id, replicates, seed);
+  ta.L = d_L;
+  ta.T = d_T;
+  ta.elw = d_sum;
+  ta.sh = d_sh;
+  for (const RellBatch& b : plan.batches) {
+    rc = rell_batch_rows(ctx, plan, b, d_pairs, d_pendant, d_distal, d_proximal, d_codes, d_begin, d_span, ta.r);
+    if (rc) return rc;
+    const uint32_t npos = (uint32_t)b.rows;
+    hipLaunchKernelGGL(k_rell_observed, dim3((npos + 255) / 256), dim3(256), 0, ctx->stream, plan.d_rows, b.pitch, ta.r.pos0,
+                       npos, plan.d_order, d_pairs, d_span, d_L);
+    hipLaunchKernelGGL(k_rell_threshold, dim3((ta.r.n_groups + 255) / 256), dim3(256), 0, ctx->stream, ta.r.groups,
+                       ta.r.n_groups, d_L, d_T);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ta.r.n_groups, (uint64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(k_rell_tests, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, ta);
+    EPA_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_rell_tests_out, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, plan.d_wins, d_sh, d_sum,
+                     plan.d_order, n, (double)replicates, d_support, d_elw, d_p_sh);
+  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL_TESTS));
   EPA_HIP(ctx, hipGetLastError());
   return EPA_OK;
 }

@@ -487,6 +487,44 @@ int epa_dev_rell_support(epa_ctx* ctx, const epa_pair* pairs, const double* pend
                          uint32_t replicates, uint64_t seed, double* support /* [n] */);
 
 /*
+ * Three statistics from one set of RELL replicates: the bootstrap support above, the expected likelihood weight (ELW,
+ * Strimmer & Rambaut 2002: the likelihood weight ratio averaged over the replicates; its cumulative sum gives a
+ * confidence set of placements) and the p-value of the Shimodaira-Hasegawa (SH) test of every entry against the best
+ * entry of its query.  Generator, draws and score are those of epa_dev_rell_support (above) and nothing else; the same
+ * (seed, stream_id, replicates) give the same replicates in both calls.  For a query with span n_q and entries k (in the
+ * caller's order), replicate r:
+ *   score     s_k^(r): epa_dev_rell_support's score -- 0.0 plus the drawn site values in draw order, plain fp64 adds
+ *   observed  L_k: 0.0 plus the entry's site values (epa_dev_site_lnl) at j = 0 .. n_q - 1 in this order, plain fp64
+ *             adds: the site row summed sequentially; epa_dev_score_at's lnL up to the rounding of the sum
+ *   support   epa_dev_rell_support's winner and tie rule; support[k] has the bits that call returns for the same arguments
+ *   elw       m = max_k s_k^(r);  w_k^(r) = exp(s_k^(r) - m) / sum_k' exp(s_k'^(r) - m);  elw[k] = (sum_r w_k^(r)) / replicates.
+ *             The order of the floating-point sums is not specified; a restatement agrees to 1e-12 absolute (the scores
+ *             are bit-exact, exp and the sums differ by a few ulp each).  The same call returns the same bits every
+ *             time: the sums run in a fixed order, no floating-point atomics.  Duplicated entries share the weight: no
+ *             tie rule.  The elw of a query add up to 1
+ *   p_sh      c_k^(r) = s_k^(r) - L_k;  t_k^(r) = (max_k' c_k'^(r)) - c_k^(r);  T_k = (max_k' L_k') - L_k;
+ *             p_sh[k] = #{ r : t_k^(r) >= T_k } / replicates.  Every step is ONE fp64 subtraction, nothing fused or
+ *             reassociated: the counts are a function of the site values alone and a restatement reaches them as
+ *             integers.  The entry with the largest L has T = 0 and t >= 0: its p_sh is 1.0 exactly
+ *   centring  the resampled scores are centred at L_k, the exact mean of the resampling distribution of s_k.  The
+ *             classic SH recipe centres at the Monte-Carlo mean of the replicates instead; the two agree as
+ *             `replicates` grows.  The exact centre needs no second pass over the replicates and makes the count
+ *             reproducible from the site values
+ *   span 0    every score and every L is 0.0: elw = 1 / (entries of the query), p_sh = 1, support by the tie rule
+ *   one entry support = elw = p_sh = 1
+ * Arguments, checks, error texts, the host-or-device pointer rule and query staging are epa_dev_rell_support's
+ * (errors name "rell_tests").  support, elw, p_sh: [n] each (host or device), any of them NULL to leave it out; all three
+ * NULL is EPA_ERR_INVALID_ARG.  replicates: 1 .. 2^20; n < 2^32; n == 0 returns EPA_OK.
+ * Timer: "rell_tests" (grouping, site rows, observed sums and resampling together).
+ */
+int epa_dev_rell_tests(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                       const double* proximal /* may be NULL */, uint64_t n,
+                       const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                       const uint64_t* stream_id /* [Q] or NULL = seq_id */,
+                       uint32_t replicates, uint64_t seed,
+                       double* support /* [n] or NULL */, double* elw /* [n] or NULL */, double* p_sh /* [n] or NULL */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -723,7 +761,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
