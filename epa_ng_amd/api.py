@@ -120,6 +120,8 @@ def dev_lib():
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                            C.c_uint64, C.c_void_p]
         L.epa_dev_rell_tests.argtypes = L.epa_dev_rell_support.argtypes + [C.c_void_p, C.c_void_p]
+        L.epa_dev_rell_au.argtypes = L.epa_dev_rell_support.argtypes[:-1] + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                                             C.c_void_p]
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -564,6 +566,37 @@ class Evaluator:
                                               _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
                                               int(replicates), int(seed), _ptr(out.get("support")), _ptr(out.get("elw")),
                                               _ptr(out.get("p_sh"))))
+        return out
+
+    def rell_au(self, pairs, pendant, distal, codes, win_begin, win_span, replicates, seed=1, stream_id=None,
+                proximal=None, scales=None, want=("p_au", "counts", "fit"), Q=None):
+        """p-value of the approximately unbiased test from multiscale RELL replicates (epa_dev_rell_au) -> dict, one
+        item per name in `want`: "p_au" float64 [n]; "counts" uint32 [n_scales][n], the replicates every entry wins at
+        every scale; "fit" float64 [n][2], the fitted signed distance and curvature (d, c), NaN where p_au is the plain
+        proportion of the scale nearest 1000.  `replicates` is per scale; `scales`: replicate lengths per mille of the
+        span (1 .. 16 values in 100 .. 4000), None: 500, 600, ..., 1400 (include/epa_dev.h has the exact definitions)."""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs)
+        want = tuple(want)
+        unknown = [w for w in want if w not in ("p_au", "counts", "fit")]
+        if unknown:
+            raise ValueError("rell_au: unknown output %r" % (unknown[0],))
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
+        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        if isinstance(stream_id, (np.ndarray, list, tuple)):
+            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
+        if scales is not None:
+            scales = np.ascontiguousarray(scales, dtype=np.uint32)
+            if scales.ndim != 1 or len(scales) == 0:
+                raise ValueError("rell_au: scales must be a non-empty 1-d array (None: the default scales)")
+        S = 10 if scales is None else len(scales)
+        shape = {"p_au": ((n,), np.float64), "counts": ((S, n), np.uint32), "fit": ((n, 2), np.float64)}
+        out = {w: np.empty(*shape[w]) for w in want}
+        self._layout(codes)
+        self._check(self.L.epa_dev_rell_au(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                           _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
+                                           int(replicates), int(seed), _ptr(scales), 0 if scales is None else S,
+                                           _ptr(out.get("p_au")), _ptr(out.get("counts")), _ptr(out.get("fit"))))
         return out
 
     def set_heuristic(self, mode="dynamic", param=0.0):

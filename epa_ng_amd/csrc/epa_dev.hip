@@ -1923,6 +1923,58 @@ extern "C" int epa_dev_rell_tests(epa_ctx* ctx, const epa_pair* pairs, const dou
   return EPA_OK;
 }
 
+extern "C" int epa_dev_rell_au(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                               const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
+                               const uint32_t* win_span, uint32_t Q, const uint64_t* stream_id, uint32_t replicates,
+                               uint64_t seed, const uint32_t* scale_pm, uint32_t n_scales, double* p_au, uint32_t* counts,
+                               double* fit) {
+  static const uint32_t default_pm[10] = {500, 600, 700, 800, 900, 1000, 1100, 1200, 1300, 1400};
+  if (!ctx || (n && (!pairs || !pendant || !distal || !q_codes || !win_begin || !win_span)))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  if (!p_au && !counts && !fit) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: p_au, counts and fit are all null");
+  if (replicates == 0 || replicates > (1u << 20))
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: replicates must be 1 .. 2^20");
+  if (!scale_pm) {
+    if (n_scales) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: n_scales must be 0 when scale_pm is null (the default scales)");
+    scale_pm = default_pm;
+    n_scales = 10;
+  } else if (n_scales < 1 || n_scales > 16) {
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: n_scales " + std::to_string(n_scales) + " is outside 1 .. 16");
+  }
+  for (uint32_t s = 0; s < n_scales; ++s)
+    if (scale_pm[s] < 100 || scale_pm[s] > 4000)
+      return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: scale " + std::to_string(s) + " is " + std::to_string(scale_pm[s]) +
+                                                    " per mille, outside 100 .. 4000");
+  if (n == 0) return EPA_OK;
+  if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: more than 2^32 - 1 entries in one call");
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  EntryStage st;
+  int rc = stage_entries(ctx, "rell_au", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
+  if (rc) return rc;
+  const uint64_t* d_sid = stream_id ? (const uint64_t*)epa_to_device(ctx, 17, stream_id, sizeof(uint64_t) * Q) : nullptr;
+  if (stream_id && !d_sid) return epa_fail(ctx, EPA_ERR_HIP, "rell_au input upload failed");
+  // outputs in host memory are staged in scratch 3: [p_au n | fit 2 n | counts n_scales x n]
+  void* out[3] = {p_au, fit, counts};
+  const size_t bytes[3] = {sizeof(double) * n, sizeof(double) * 2 * n, sizeof(uint32_t) * (size_t)n_scales * n};
+  void* d_out[3] = {nullptr, nullptr, nullptr};
+  size_t staged = 0;
+  for (int i = 0; i < 3; ++i) staged += out[i] && !epa_is_device_ptr(out[i]) ? bytes[i] : 0;
+  char* d_stage = staged ? (char*)epa_scratch(ctx, 3, staged) : nullptr;
+  if (staged && !d_stage) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_au out)");
+  for (int i = 0; i < 3; ++i)
+    if (out[i]) {
+      if (epa_is_device_ptr(out[i])) d_out[i] = out[i];
+      else { d_out[i] = d_stage; d_stage += bytes[i]; }
+    }
+  rc = launch_rell_au(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, st.hs, Q, d_sid,
+                      replicates, seed, scale_pm, n_scales, (double*)d_out[0], (uint32_t*)d_out[2], (double*)d_out[1]);
+  if (rc) return rc;
+  for (int i = 0; i < 3; ++i)
+    if (out[i] && d_out[i] != out[i]) EPA_HIP(ctx, hipMemcpyAsync(out[i], d_out[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return EPA_OK;
+}
+
 extern "C" int epa_dev_select_candidates(epa_ctx* ctx, const double* lnl, uint32_t Q,
                                          double threshold, epa_pair* pairs, uint64_t max_pairs,
                                          uint64_t* n_pairs) {
@@ -2909,6 +2961,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "rell")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL]][epa_ctx::T_RELL];
   else if (!strcmp(which, "marginal")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_MARGINAL]][epa_ctx::T_MARGINAL];
   else if (!strcmp(which, "rell_tests")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_TESTS]][epa_ctx::T_RELL_TESTS];
+  else if (!strcmp(which, "rell_au")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_AU]][epa_ctx::T_RELL_AU];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

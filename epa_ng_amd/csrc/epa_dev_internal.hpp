@@ -218,7 +218,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 19;   // 13 .. 17: epa_dev_rell_support / _tests, 18: epa_dev_rell_tests (rell.hip, epa_dev.hip)
+  static constexpr int N_SCRATCH = 20;   // 13 .. 17: epa_dev_rell_support / _tests / _au, 18: epa_dev_rell_tests, 19: epa_dev_rell_au (rell.hip, epa_dev.hip)
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -248,7 +248,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, N_TIMERS = 8 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, N_TIMERS = 9 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -399,6 +399,13 @@ int launch_rell_tests(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pen
                       const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
                       const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
                       uint32_t replicates, uint64_t seed, double* d_support, double* d_elw, double* d_p_sh);
+// AU p-values from multiscale RELL replicates (rell.hip): h_scale_pm [n_scales <= 16] per mille (host); d_p_au [n],
+// d_counts [n_scales][n], d_fit [n][2], each or null
+int launch_rell_au(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                   const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
+                   const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
+                   uint32_t replicates, uint64_t seed, const uint32_t* h_scale_pm, uint32_t n_scales, double* d_p_au,
+                   uint32_t* d_counts, double* d_fit);
 // marginal likelihood of n entries over a (distal x pendant) tensor rule (marginal.hip); d_rule: x_frac [Kx] | x_logw
 // [Kx] | p_len [Kp] | p_logw [Kp]; d_grid: [n][Kx][Kp] or null.  Uses scratch slot 9 for the waves' grid values
 int launch_marginal(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n, const double* d_rule, uint32_t Kx, uint32_t Kp,

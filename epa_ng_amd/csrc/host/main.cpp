@@ -40,10 +40,15 @@ static void usage() {
       "                        \"rell_support\": \"elw\", the expected likelihood weight (the like_weight_ratio averaged over\n"
       "                        the replicates; its cumulative sum gives a confidence set), and \"p_sh\", the p-value of the\n"
       "                        Shimodaira-Hasegawa test of the row against the best row of its placement object\n"
+      "  --au                  with --rescore --rell N: one more field, \"p_au\", directly after \"rell_support\" (after \"p_sh\" with\n"
+      "                        --rell-tests): the p-value of the approximately unbiased test (Shimodaira 2002) of the row, from\n"
+      "                        N replicates at each of ten replicate lengths (0.5 .. 1.4 of the sites).  Unlike p_sh it does\n"
+      "                        not grow more conservative with the number of rows.  AU wants N of the order of 10000 per\n"
+      "                        scale (CONSEL's default)\n"
       "  --posterior           with --rescore: marginal likelihood of every row's edge, integrated over the attachment point\n"
       "                        (uniform on the edge) and the pendant length (exponential prior), and its normalisation over\n"
       "                        the rows of the placement object; written as the fields \"marginal_like\" and \"post_prob\"\n"
-      "                        (after \"rell_support\", \"elw\", \"p_sh\" when --rell, --rell-tests are given).  Only edge_num of a row enters them\n"
+      "                        (after \"rell_support\", \"elw\", \"p_sh\", \"p_au\" when --rell, --rell-tests, --au are given).  Only edge_num of a row enters them\n"
       "  --prior-mean M        mean of the pendant prior (default: the mean branch length of the reference tree)\n"
       "  --posterior-nodes KX,KP  Gauss-Legendre nodes along the edge x Gauss-Laguerre pendant nodes, 1 .. 64 each (default 8,16)\n"
       "  --precision N         output digits (default 10)\n"
@@ -119,6 +124,7 @@ int main(int argc, char** argv) {
     else if (a == "--rell") { opt.rell_replicates = (unsigned)std::stoul(need(i)); rell_given = true; }
     else if (a == "--rell-seed") { opt.rell_seed = std::stoull(need(i)); rell_given = true; }
     else if (a == "--rell-tests") opt.rell_tests = true;
+    else if (a == "--au") opt.au = true;
     else if (a == "--posterior") opt.posterior = true;
     else if (a == "--prior-mean") {
       const std::string v = need(i);
@@ -197,6 +203,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (opt.filter_min > opt.filter_max) { std::cerr << "filter-min must not exceed filter-max!\n"; return 1; }
+  if (opt.au && (rescore_file.empty() || opt.rell_replicates == 0)) {
+    std::cerr << "--au adds p_au from multiscale replicates, N of --rell per scale, to an existing result: place first, then "
+                 "--rescore out.jplace --rell N --au\n";
+    return 1;
+  }
   if (rell_given && rescore_file.empty()) {
     std::cerr << "--rell / --rell-seed work on an existing result: place first, then run again with "
                  "--rescore out.jplace --rell N\n";

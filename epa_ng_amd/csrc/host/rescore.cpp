@@ -4,7 +4,8 @@
 // does -- same reader, same premasking -- and picks the sequences the jplace names.  With --rell N the same rows also
 // get their RELL bootstrap support (epa_dev_rell_support) among the rows of their placement object; the object's index
 // in the input file is its random stream, so the result does not depend on --chunk-size.  --rell-tests makes that one
-// call epa_dev_rell_tests: expected likelihood weight and SH p-value from the same replicates.  With --posterior the rows get
+// call epa_dev_rell_tests: expected likelihood weight and SH p-value from the same replicates; --au adds the AU test's
+// p-value from multiscale replicates of the same streams (epa_dev_rell_au, the default scales).  With --posterior the rows get
 // their marginal likelihood (epa_dev_marginal_like: only edge_num comes from the row; Gauss-Legendre x Gauss-Laguerre
 // rule, exponential pendant prior) and post_prob, its normalisation over the rows of the placement object.
 #include <chrono>
@@ -141,7 +142,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
                                     lnl.data());
     if (rc != EPA_OK)
       throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
-    std::vector<double> support, elw, p_sh;
+    std::vector<double> support, elw, p_sh, p_au;
     if (options.rell_replicates) {
       std::vector<uint64_t> stream_id(target.begin(), target.end());
       support.resize(pairs.size());
@@ -156,6 +157,15 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
                                  stream_id.data(), options.rell_replicates, options.rell_seed, support.data());
       if (rrc != EPA_OK)
         throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rrc) + ")"};
+      if (options.au) {
+        p_au.resize(pairs.size());
+        const int arc = epa_dev_rell_au(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
+                                        enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
+                                        stream_id.data(), options.rell_replicates, options.rell_seed, nullptr, 0, p_au.data(),
+                                        nullptr, nullptr);
+        if (arc != EPA_OK)
+          throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(arc) + ")"};
+      }
     }
     std::vector<double> marginal;
     if (options.posterior) {
@@ -175,6 +185,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
         pq.emplace_back(r.edge_num, lnl[k], r.pendant_length, r.distal_length);
         if (!support.empty()) pq[pq.size() - 1].rell_support(support[k]);
         if (!elw.empty()) { pq[pq.size() - 1].elw(elw[k]); pq[pq.size() - 1].p_sh(p_sh[k]); }
+        if (!p_au.empty()) pq[pq.size() - 1].p_au(p_au[k]);
         if (!marginal.empty()) pq[pq.size() - 1].marginal_like(marginal[k]);
         ++k;
       }
@@ -208,6 +219,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
   if (!os) throw std::runtime_error{"cannot open " + out_path};
   write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision, nullptr,
                (options.rell_replicates ? kJplaceRell : 0u) | (options.rell_tests ? kJplaceRellTests : 0u) |
+                   (options.au ? kJplaceAu : 0u) |
                    (options.posterior ? kJplacePosterior : 0u));
   os.flush();
   if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }

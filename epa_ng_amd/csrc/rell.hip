@@ -31,6 +31,14 @@
 // replicate lanes are added by epa_wave::wave_sum and the four wave partials in wave order, the rounds in round order,
 // all by one thread per entry: a fixed order, no floating-point atomics.  The observed sums L and the thresholds T come
 // from two small kernels in front (k_rell_observed, k_rell_threshold), once per entry.
+//
+// k_rell_ms / k_rell_au_fit (epa_dev_rell_au): the AU test's p-value from multiscale replicates.  k_rell_ms is k_rell with
+// a loop over the scales around the rounds: scale s draws n'_s = round(n_q * scale_s) times from the same n_q sites, with
+// (s + 1) << 20 above the replicate in the counter's second word, so every scale is a stream of its own.  A query of one
+// tile is staged once for all scales and rounds.  The counters are [scale][entry]: in LDS while n_scales * E fit
+// MS_WINS_LDS (the 4 KiB k_rell spends on its counters: the same three workgroups per CU), else global integer atomics.
+// k_rell_au_fit: one thread per entry fits the signed distance d and the curvature c to its ten proportions and writes
+// p_au = normcdf(c - d), or the plain proportion where fewer than three scales are usable.
 #include "epa_dev_internal.hpp"
 #include "wave_util.hpp"
 
@@ -49,6 +57,8 @@ constexpr int RELL_THREADS = 256;
 constexpr int TE = 4;                    // entries per tile
 constexpr uint32_t LDS_SITES = 1536;     // 1536 sites x 4 entries x 8 B = 48 KiB
 constexpr uint32_t WINS_LDS = 1024;      // entries per query whose wins are counted in LDS
+constexpr uint32_t MS_SCALES = 16;       // k_rell_ms: the most scales of a call
+constexpr uint32_t MS_WINS_LDS = 1024;   // k_rell_ms: scales x entries per query counted in LDS: 48 + 4 KiB as k_rell, three workgroups per CU
 constexpr int RES_TILES = 2;             // k_rell_tests: tiles of a query whose scores stay in registers between the sweeps
 constexpr uint32_t ACC_LDS = 256;       // k_rell_tests: entries per query whose three accumulators live in LDS
 constexpr size_t ROWS_BUDGET = (size_t)128 << 20;   // bytes of site rows per batch
@@ -76,6 +86,17 @@ struct RellTestsArgs {
   const double* T;            // [n]: the query's largest L minus the entry's (k_rell_threshold)
   double* elw;                // [n]: sum of the weights over the replicates
   uint32_t* sh;               // [n]: replicates with t >= T
+};
+
+struct RellMsScales {
+  uint32_t n;                 // scales in use
+  uint32_t pm[MS_SCALES];     // replicate length per mille of the span
+};
+
+struct RellMsArgs {
+  RellArgs r;                 // r.wins: [scale][n] by sorted position
+  RellMsScales sc;
+  uint32_t n;                 // entries of the call: the pitch of the counters
 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
@@ -130,18 +151,19 @@ __device__ __forceinline__ void rell_stage_tile(double* mat, const double* __res
   }
 }
 
-// sc[k]: the score of entry e0 + k in replicate r of stream (tlo, thi) under key (k0, k1)
+// sc[k]: the score of entry e0 + k over nd draws from the nq sites, counter word 1 = c1 (the replicate r; k_rell_ms puts
+// the scale above it), stream (tlo, thi), key (k0, k1).  k_rell and k_rell_tests draw nd = nq times
 __device__ __forceinline__ void rell_tile_scores(const double* mat, const double* __restrict__ rows, uint32_t pitch,
-                                                 uint32_t e0, uint32_t te, uint32_t nq, bool in_lds, uint32_t r,
+                                                 uint32_t e0, uint32_t te, uint32_t nq, uint32_t nd, bool in_lds, uint32_t c1,
                                                  uint32_t tlo, uint32_t thi, uint32_t k0, uint32_t k1, double sc[TE]) {
 #pragma unroll
   for (int k = 0; k < TE; ++k) sc[k] = 0.0;
-  for (uint32_t d = 0; d < nq; d += 4) {
+  for (uint32_t d = 0; d < nd; d += 4) {
     uint32_t w[4];
-    philox4x32_10(d >> 2, r, tlo, thi, k0, k1, w);
+    philox4x32_10(d >> 2, c1, tlo, thi, k0, k1, w);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (d + u < nq) {
+      if (d + u < nd) {
         const uint32_t j = __umulhi(w[u], nq);
         if (in_lds) {
 #pragma unroll
@@ -206,7 +228,7 @@ __global__ void __launch_bounds__(RELL_THREADS) k_rell(const RellArgs a) {
         }
         if (!active) continue;
         double sc[TE];
-        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
         rell_tile_winner(sc, tile == 0, e0, te, a.pairs, ord, best_sc, best_br, best_k);
       }
       if (active) {
@@ -218,6 +240,118 @@ __global__ void __launch_bounds__(RELL_THREADS) k_rell(const RellArgs a) {
     if (wins_lds)
       for (uint32_t i = tid; i < E; i += RELL_THREADS) a.wins[grp.start + i] = wins_l[i];
   }
+}
+
+// draws per replicate at scale pm (per mille) of a query of nq sites: round(nq * pm / 1000), at least 1; 0 for no sites
+__device__ __forceinline__ uint32_t rell_ms_draws(uint32_t nq, uint32_t pm) {
+  if (nq == 0) return 0;
+  const uint64_t nd = ((uint64_t)nq * pm + 500u) / 1000u;
+  return nd ? (uint32_t)nd : 1u;
+}
+
+// The multiscale replicates of epa_dev_rell_au: k_rell once per scale s with nd = rell_ms_draws(nq, pm[s]) draws from the
+// same nq sites and (s + 1) << 20 above the replicate in the counter's second word.  A query of one tile is staged once for
+// all scales and rounds; the counters are [scale][entry], in LDS while a query's n_scales * E fit MS_WINS_LDS
+__global__ void __launch_bounds__(RELL_THREADS) k_rell_ms(const RellMsArgs ma) {
+  __shared__ __attribute__((aligned(16))) double mat[LDS_SITES * TE];   // [site][TE]
+  __shared__ uint32_t wins_l[MS_WINS_LDS];                              // [scale][E]
+  const RellArgs& a = ma.r;
+  const uint32_t tid = threadIdx.x, S = ma.sc.n;
+  for (uint32_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+    const RellGroup grp = a.groups[g];
+    const uint32_t E = grp.count, nq = a.span[grp.q];
+    const uint64_t t = a.stream_id ? a.stream_id[grp.q] : (uint64_t)grp.q;
+    const uint32_t tlo = (uint32_t)t, thi = (uint32_t)(t >> 32);
+    const double* __restrict__ rows = a.rows + (size_t)(grp.start - a.pos0) * a.pitch;
+    const uint32_t* __restrict__ ord = a.order + grp.start;
+    const bool in_lds = nq <= LDS_SITES, wins_lds = (uint64_t)S * E <= MS_WINS_LDS;   // workgroup-uniform
+    const uint32_t ntiles = (E + TE - 1) / TE;
+    __syncthreads();   // the previous query's tile and counters are no longer read
+    if (wins_lds)
+      for (uint32_t i = tid; i < S * E; i += RELL_THREADS) wins_l[i] = 0;
+    if (in_lds && ntiles == 1) rell_stage_tile(mat, rows, a.pitch, 0, E, nq, tid);
+    __syncthreads();
+    for (uint32_t s = 0; s < S; ++s) {
+      const uint32_t nd = rell_ms_draws(nq, ma.sc.pm[s]), c1 = (s + 1) << 20;
+      for (uint32_t rbase = 0; rbase < a.R; rbase += RELL_THREADS) {
+        const uint32_t r = rbase + tid;
+        const bool active = r < a.R;
+        double best_sc = 0.0;
+        uint32_t best_br = 0, best_k = 0;
+        for (uint32_t tile = 0; tile < ntiles; ++tile) {
+          const uint32_t e0 = tile * TE, te = min((uint32_t)TE, E - e0);
+          if (in_lds && ntiles > 1) {   // as k_rell: more tiles are staged again for every round of replicates
+            __syncthreads();
+            rell_stage_tile(mat, rows, a.pitch, e0, te, nq, tid);
+            __syncthreads();
+          }
+          if (!active) continue;
+          double sc[TE];
+          rell_tile_scores(mat, rows, a.pitch, e0, te, nq, nd, in_lds, c1 | r, tlo, thi, a.k0, a.k1, sc);
+          rell_tile_winner(sc, tile == 0, e0, te, a.pairs, ord, best_sc, best_br, best_k);
+        }
+        if (active) {
+          if (wins_lds) atomicAdd(&wins_l[s * E + best_k], 1u);
+          else atomicAdd(&a.wins[(size_t)s * ma.n + grp.start + best_k], 1u);
+        }
+      }
+    }
+    __syncthreads();
+    if (wins_lds)
+      for (uint32_t i = tid; i < S * E; i += RELL_THREADS) {
+        const uint32_t s = i / E;
+        a.wins[(size_t)s * ma.n + grp.start + (i - s * E)] = wins_l[i];
+      }
+  }
+}
+
+// The AU p-value of every entry from its win counts (include/epa_dev.h, epa_dev_rell_au): one thread per sorted position.
+// Weighted least squares of z_s = -normcdfinv(p_s) on (sqrt(r_s), 1 / sqrt(r_s)) over the usable scales, the five sums in
+// scale order; fewer than three usable scales, or one draw count among them: the count of the scale nearest 1000
+__global__ void __launch_bounds__(256) k_rell_au_fit(const uint32_t* __restrict__ wins, const uint32_t* __restrict__ order,
+                                                     const epa_pair* __restrict__ pairs, const uint32_t* __restrict__ span,
+                                                     const RellMsScales sc, uint32_t n, uint32_t R, double* __restrict__ p_au,
+                                                     uint32_t* __restrict__ counts, double* __restrict__ fit) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t e = order[i], nq = span[pairs[e].seq_id], S = sc.n;
+  const double Rd = (double)R;
+  uint32_t usable = 0, nd0 = 0, s_star = 0, off_star = 0xffffffffu;
+  bool distinct = false;
+  for (uint32_t s = 0; s < S; ++s) {
+    const uint32_t c = wins[(size_t)s * n + i], pm = sc.pm[s], off = pm > 1000u ? pm - 1000u : 1000u - pm;
+    if (counts) counts[(size_t)s * n + e] = c;
+    if (off < off_star) { off_star = off; s_star = s; }
+    if (c > 0 && c < R) {
+      const uint32_t nd = rell_ms_draws(nq, pm);
+      if (usable == 0) nd0 = nd;
+      else if (nd != nd0) distinct = true;
+      ++usable;
+    }
+  }
+  double p = (double)wins[(size_t)s_star * n + i] / Rd, d = NAN, c = NAN;
+  if (usable >= 3 && distinct) {
+    double Saa = 0.0, Sab = 0.0, Sbb = 0.0, Saz = 0.0, Sbz = 0.0;
+    for (uint32_t s = 0; s < S; ++s) {
+      const uint32_t cs = wins[(size_t)s * n + i];
+      if (cs == 0 || cs >= R) continue;
+      const double ps = (double)cs / Rd, rs = (double)rell_ms_draws(nq, sc.pm[s]) / (double)nq;
+      const double z = -normcdfinv(ps), as = sqrt(rs), bs = 1.0 / as;
+      const double phi = 0.3989422804014327 * exp(-0.5 * z * z);   // 1 / sqrt(2 pi)
+      const double w = phi * phi / (ps * (1.0 - ps));
+      Saa += w * as * as;
+      Sab += w * as * bs;
+      Sbb += w * bs * bs;
+      Saz += w * as * z;
+      Sbz += w * bs * z;
+    }
+    const double det = Saa * Sbb - Sab * Sab;
+    d = (Saz * Sbb - Sbz * Sab) / det;
+    c = (Sbz * Saa - Saz * Sab) / det;
+    p = normcdf(c - d);
+  }
+  if (p_au) p_au[e] = p;
+  if (fit) { fit[2 * (size_t)e] = d; fit[2 * (size_t)e + 1] = c; }
 }
 
 // L[pos]: the site row of sorted position pos summed from site 0 on, one thread per row of the batch
@@ -285,7 +419,7 @@ __global__ void __launch_bounds__(RELL_THREADS) k_rell_tests(const RellTestsArgs
           __syncthreads();
         }
         if (!active) continue;
-        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
         if (resident) {
 #pragma unroll
           for (int u = 0; u < RES_TILES; ++u)
@@ -325,7 +459,7 @@ __global__ void __launch_bounds__(RELL_THREADS) k_rell_tests(const RellTestsArgs
             rell_stage_tile(mat, rows, a.pitch, e0, te, nq, tid);
             __syncthreads();
           }
-          if (active) rell_tile_scores(mat, rows, a.pitch, e0, te, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+          if (active) rell_tile_scores(mat, rows, a.pitch, e0, te, nq, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
         } else {
 #pragma unroll
           for (int u = 0; u < RES_TILES; ++u)
@@ -564,6 +698,41 @@ int launch_rell_tests(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pen
   hipLaunchKernelGGL(k_rell_tests_out, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, plan.d_wins, d_sh, d_sum,
                      plan.d_order, n, (double)replicates, d_support, d_elw, d_p_sh);
   epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL_TESTS));
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}
+
+int launch_rell_au(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
+                   const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
+                   const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
+                   uint32_t replicates, uint64_t seed, const uint32_t* h_scale_pm, uint32_t n_scales, double* d_p_au,
+                   uint32_t* d_counts, double* d_fit) {
+  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32 and n_scales <= MS_SCALES
+  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL_AU));
+  RellPlan plan;
+  int rc = rell_plan(ctx, "rell_au", d_pairs, n, h_span, Q, plan);
+  if (rc) return rc;
+  // scratch 19: the win counters [scale][n] by sorted position, cleared per call
+  const size_t cbytes = sizeof(uint32_t) * (size_t)n_scales * n;
+  uint32_t* d_ms = (uint32_t*)epa_scratch(ctx, 19, cbytes);
+  if (!d_ms) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_au counters)");
+  EPA_HIP(ctx, hipMemsetAsync(d_ms, 0, cbytes, ctx->stream));
+  RellMsArgs ma{};
+  ma.r = rell_args(plan, d_pairs, d_span, d_stream_id, replicates, seed);
+  ma.r.wins = d_ms;
+  ma.sc.n = n_scales;
+  for (uint32_t s = 0; s < n_scales; ++s) ma.sc.pm[s] = h_scale_pm[s];
+  ma.n = n;
+  for (const RellBatch& b : plan.batches) {
+    rc = rell_batch_rows(ctx, plan, b, d_pairs, d_pendant, d_distal, d_proximal, d_codes, d_begin, d_span, ma.r);
+    if (rc) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ma.r.n_groups, (uint64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(k_rell_ms, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, ma);
+    EPA_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_rell_au_fit, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_ms, plan.d_order, d_pairs, d_span,
+                     ma.sc, n, replicates, d_p_au, d_counts, d_fit);
+  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL_AU));
   EPA_HIP(ctx, hipGetLastError());
   return EPA_OK;
 }

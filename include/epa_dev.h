@@ -525,6 +525,57 @@ int epa_dev_rell_tests(epa_ctx* ctx, const epa_pair* pairs, const double* pendan
                        double* support /* [n] or NULL */, double* elw /* [n] or NULL */, double* p_sh /* [n] or NULL */);
 
 /*
+ * The p-value of the approximately unbiased (AU) test (Shimodaira 2002) of every entry, from multiscale RELL replicates:
+ * the resampling above repeated at several replicate lengths n' != n_q, and the change of an entry's bootstrap
+ * proportion with n' / n_q used to correct the proportion for the curvature of the boundary of the region in which the
+ * entry wins.  Where the SH p-value above grows more conservative with every competing entry, this one does not.
+ * Generator, draws, scales, fit and fallback are specified exactly; a restatement anywhere reaches the same counts from
+ * the same site values, and the same p-values up to the rounding of the fit:
+ *   scales     scale_pm: [n_scales] HOST array, replicate lengths per mille of the span, each 100 .. 4000, n_scales 1 .. 16;
+ *              NULL with n_scales == 0: the default ten, 500, 600, ..., 1400
+ *   draw count scale s of a query with span n_q makes n'_s = max(1, (n_q * scale_pm[s] + 500) / 1000) draws per replicate
+ *              (64-bit integers, truncating division); n'_s = 0 when n_q = 0.  n'_s may exceed n_q: the sites are still
+ *              drawn from the n_q sites
+ *   draws      generator and key of the bootstrap support above.  Replicate r of scale s uses output word d % 4 of
+ *              counter (d / 4, ((s + 1) << 20) | r, t low word, t high word) for d = 0 .. n'_s - 1; the drawn site is
+ *              j = (word * n_q) >> 32.  r < 2^20: the second counter word never meets another scale's, nor that of the
+ *              plain RELL calls, where it is r alone.  The scales are independent streams; no replicate is a prefix of
+ *              another scale's
+ *   score      0.0 plus the entry's site values at the drawn j in draw order, plain fp64 adds, as above; no rescaling by
+ *              n_q / n'_s, on which the winner does not depend
+ *   winner     the largest score; ties go to the smaller branch_id, then to the smaller entry index
+ *   counts     counts[s][i]: the replicates of scale s that entry i wins, an integer; the counts of a query add up to
+ *              `replicates` at every scale
+ *   fit        per entry.  Scale s is usable if 0 < counts[s][i] < R (R = replicates).  With at least 3 usable scales that
+ *              have at least 2 distinct n'_s among them, for each usable scale
+ *                p_s = counts[s][i] / R,  r_s = n'_s / n_q,  z_s = -Phi^-1(p_s),  a_s = sqrt(r_s),  b_s = 1 / a_s,
+ *                w_s = phi(z_s)^2 / (p_s (1 - p_s))
+ *              and (d, c) minimise sum_s w_s (z_s - d a_s - c b_s)^2: the 2 x 2 normal equations, the five sums Saa, Sab,
+ *              Sbb, Saz, Sbz accumulated in scale order, det = Saa Sbb - Sab^2.  p_au = Phi(c - d); fit = (d, c), the
+ *              signed distance and the curvature
+ *   fallback   otherwise -- an entry that wins always or never, span 0, span 1 (every n'_s is 1), a single entry --
+ *              p_au = counts[s*][i] / R for the scale s* with the smallest |scale_pm[s] - 1000|, ties to the smaller s,
+ *              and fit = (NaN, NaN).  A single entry gets p_au = 1
+ *   rounding   the order of the floating-point operations inside Phi^-1, Phi and the solve is not specified beyond the
+ *              above; a float64 restatement with other library functions agrees to 3.2e-12 in p_au, d and c (100 x its own error
+ *              against the same fit at 50 digits; measured 5e-14).  The same call returns
+ *              the same bits every time: integer atomics for the counts, one thread per entry for the fit, no
+ *              floating-point atomics
+ * Arguments, checks, error texts, the host-or-device pointer rule and query staging are those of the bootstrap support
+ * above (errors name "rell_au").  p_au: [n], counts: [n_scales][n] (ten rows with the default scales), fit: [n][2], host or
+ * device, any of them NULL to leave it out; all three NULL is EPA_ERR_INVALID_ARG.  replicates: 1 .. 2^20 per scale;
+ * n < 2^32; n == 0 returns EPA_OK.  Timer: "rell_au" (grouping, site rows, resampling at every scale and fit together).
+ */
+int epa_dev_rell_au(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                    const double* proximal /* may be NULL */, uint64_t n,
+                    const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                    const uint64_t* stream_id /* [Q] or NULL = seq_id */,
+                    uint32_t replicates, uint64_t seed,
+                    const uint32_t* scale_pm /* [n_scales] per mille, or NULL = the default ten */, uint32_t n_scales,
+                    double* p_au /* [n] or NULL */, uint32_t* counts /* [n_scales][n] or NULL */,
+                    double* fit /* [n][2] = (d, c) or NULL */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -761,7 +812,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
