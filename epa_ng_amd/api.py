@@ -472,16 +472,34 @@ class Evaluator:
                            "newton_evals": st.newton_evals, "reverts": st.reverts}
         return out
 
+    def _entries(self, pairs, pendant, distal, proximal, codes, win_begin, Q, stream_id=None):
+        """what the calls on (pair, pendant, distal[, proximal]) entries begin with -> (n, Q, pendant, distal, proximal,
+        stream_id): host lengths converted to float64 and host stream ids to uint64 (device buffers pass as is), the
+        context told the layout of `codes`"""
+        n, Q = len(pairs), (len(win_begin) if Q is None else Q)
+        host = (np.ndarray, list, tuple)
+        pendant, distal, proximal = (np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, host) else a
+                                     for a in (pendant, distal, proximal))
+        if isinstance(stream_id, host):
+            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
+        self._layout(codes)
+        return n, Q, pendant, distal, proximal, stream_id
+
+    @staticmethod
+    def _want(who, want, table):
+        """table: output name -> (shape, dtype) -> dict of new arrays, one per name in `want`"""
+        want = tuple(want)
+        unknown = [w for w in want if w not in table]
+        if unknown:
+            raise ValueError("%s: unknown output %r" % (who, unknown[0]))
+        return {w: np.empty(*table[w]) for w in want}
+
     def score_at(self, pairs, pendant, distal, codes, win_begin, win_span, proximal=None, Q=None, out=None):
         """lnL of the placements `pairs` (PAIR_DTYPE) at the GIVEN lengths, no optimiser (epa_dev_score_at) -> float64
         [n].  proximal None: branch length - distal.  Host arrays are converted to float64; device buffers pass as is."""
-        Q = len(win_begin) if Q is None else Q
-        n = len(pairs)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
-        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        n, Q, pendant, distal, proximal, _ = self._entries(pairs, pendant, distal, proximal, codes, win_begin, Q)
         if out is None:
             out = np.empty(n, np.float64)
-        self._layout(codes)
         self._check(self.L.epa_dev_score_at(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                             _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(out)))
         return out
@@ -491,15 +509,11 @@ class Evaluator:
         [n][pitch]: row i, column j < win_span[seq_id] is the log of the site likelihood at window position j (scaler
         counts and the +I term included: the row's sum is score_at's lnL), the columns beyond the span are 0.0.
         pitch None: the longest window (host win_span)."""
-        Q = len(win_begin) if Q is None else Q
-        n = len(pairs)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
-        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
+        n, Q, pendant, distal, proximal, _ = self._entries(pairs, pendant, distal, proximal, codes, win_begin, Q)
         if pitch is None:
             pitch = int(np.max(np.asarray(win_span)[:Q])) if Q else 0
         if out is None:
             out = np.empty((n, int(pitch)), np.float64)
-        self._layout(codes)
         self._check(self.L.epa_dev_site_lnl(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                             _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, int(pitch), _ptr(out)))
         return out
@@ -509,8 +523,7 @@ class Evaluator:
         posterior_rule() makes the default one) -> M float64 [n], or (M, g) with grid=True: g [n][Kx][Kp] is the lnL
         (score_at's) at distal x_frac[i] * branch length and pendant p_len[j].  The four rule arrays are host arrays;
         `out` may be a device buffer for M."""
-        Q = len(win_begin) if Q is None else Q
-        n = len(pairs)
+        n, Q = self._entries(pairs, None, None, None, codes, win_begin, Q)[:2]      # no lengths
         x_frac, x_logw, p_len, p_logw = (np.ascontiguousarray(a, dtype=np.float64) for a in (x_frac, x_logw, p_len, p_logw))
         if x_frac.shape != x_logw.shape or p_len.shape != p_logw.shape or x_frac.ndim != 1 or p_len.ndim != 1:
             raise ValueError("marginal_like: nodes and log weights must be 1-d arrays of equal length")
@@ -518,7 +531,6 @@ class Evaluator:
         if out is None:
             out = np.empty(n, np.float64)
         g = np.empty((n, Kx, Kp), np.float64) if grid else None
-        self._layout(codes)
         self._check(self.L.epa_dev_marginal_like(self.h, _ptr(pairs), n, _ptr(x_frac), _ptr(x_logw), Kx, _ptr(p_len),
                                                  _ptr(p_logw), Kp, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q,
                                                  _ptr(out), _ptr(g)))
@@ -530,15 +542,10 @@ class Evaluator:
         is the fraction of the `replicates` resamplings of the query's sites that entry i wins.  The resampling is
         specified exactly in include/epa_dev.h (Philox4x32-10, key = seed, stream_id[q] selects the query's stream;
         None: the query's index)."""
-        Q = len(win_begin) if Q is None else Q
-        n = len(pairs)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
-        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
-        if isinstance(stream_id, (np.ndarray, list, tuple)):
-            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
+        n, Q, pendant, distal, proximal, stream_id = self._entries(pairs, pendant, distal, proximal, codes, win_begin, Q,
+                                                                   stream_id)
         if out is None:
             out = np.empty(n, np.float64)
-        self._layout(codes)
         self._check(self.L.epa_dev_rell_support(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                                 _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
                                                 int(replicates), int(seed), _ptr(out)))
@@ -550,18 +557,9 @@ class Evaluator:
         -> dict of float64 [n] arrays, one per name in `want`.  "support" has the bits of rell_support(); "elw" is the
         likelihood weight ratio averaged over the replicates; "p_sh" the fraction of replicates in which the entry's
         centred score lies as far below the best as observed, or further (include/epa_dev.h has the exact definitions)."""
-        Q = len(win_begin) if Q is None else Q
-        n = len(pairs)
-        want = tuple(want)
-        unknown = [w for w in want if w not in ("support", "elw", "p_sh")]
-        if unknown:
-            raise ValueError("rell_tests: unknown output %r" % (unknown[0],))
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
-        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
-        if isinstance(stream_id, (np.ndarray, list, tuple)):
-            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
-        out = {w: np.empty(n, np.float64) for w in want}
-        self._layout(codes)
+        out = self._want("rell_tests", want, {w: ((len(pairs),), np.float64) for w in ("support", "elw", "p_sh")})
+        n, Q, pendant, distal, proximal, stream_id = self._entries(pairs, pendant, distal, proximal, codes, win_begin, Q,
+                                                                   stream_id)
         self._check(self.L.epa_dev_rell_tests(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                               _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
                                               int(replicates), int(seed), _ptr(out.get("support")), _ptr(out.get("elw")),
@@ -575,24 +573,14 @@ class Evaluator:
         every scale; "fit" float64 [n][2], the fitted signed distance and curvature (d, c), NaN where p_au is the plain
         proportion of the scale nearest 1000.  `replicates` is per scale; `scales`: replicate lengths per mille of the
         span (1 .. 16 values in 100 .. 4000), None: 500, 600, ..., 1400 (include/epa_dev.h has the exact definitions)."""
-        Q = len(win_begin) if Q is None else Q
-        n = len(pairs)
-        want = tuple(want)
-        unknown = [w for w in want if w not in ("p_au", "counts", "fit")]
-        if unknown:
-            raise ValueError("rell_au: unknown output %r" % (unknown[0],))
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a  # noqa: E731
-        pendant, distal, proximal = f64(pendant), f64(distal), (None if proximal is None else f64(proximal))
-        if isinstance(stream_id, (np.ndarray, list, tuple)):
-            stream_id = np.ascontiguousarray(stream_id, dtype=np.uint64)
+        n, S = len(pairs), (10 if scales is None else np.size(scales))
+        out = self._want("rell_au", want, {"p_au": ((n,), np.float64), "counts": ((S, n), np.uint32), "fit": ((n, 2), np.float64)})
         if scales is not None:
             scales = np.ascontiguousarray(scales, dtype=np.uint32)
             if scales.ndim != 1 or len(scales) == 0:
                 raise ValueError("rell_au: scales must be a non-empty 1-d array (None: the default scales)")
-        S = 10 if scales is None else len(scales)
-        shape = {"p_au": ((n,), np.float64), "counts": ((S, n), np.uint32), "fit": ((n, 2), np.float64)}
-        out = {w: np.empty(*shape[w]) for w in want}
-        self._layout(codes)
+        n, Q, pendant, distal, proximal, stream_id = self._entries(pairs, pendant, distal, proximal, codes, win_begin, Q,
+                                                                   stream_id)
         self._check(self.L.epa_dev_rell_au(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
                                            _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
                                            int(replicates), int(seed), _ptr(scales), 0 if scales is None else S,

@@ -1714,213 +1714,217 @@ extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_
   return EPA_OK;
 }
 
-// What epa_dev_score_at, epa_dev_site_lnl and epa_dev_rell_support share: the entries' arguments checked (host arrays;
-// the first offending entry is named after `who`) and staged on the device.  hs: the host's view of win_span.
-// pendant == distal == NULL (epa_dev_marginal_like): the pairs alone, no per-entry lengths are checked or staged.
-struct EntryStage {
-  std::vector<uint32_t> hb_buf, hs_buf;
-  const uint32_t* hs = nullptr;
-  uint32_t max_span = 0;
-  const uint8_t* d_codes = nullptr;
-  const uint32_t *d_begin = nullptr, *d_span = nullptr;
-  const epa_pair* d_pairs = nullptr;
-  const double *d_pen = nullptr, *d_dis = nullptr, *d_prx = nullptr;
+// ---- the post-placement entry points: epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au
+
+namespace {
+
+// the arguments all six take (epa_dev_marginal_like: no lengths)
+struct EntryArgs {
+  const epa_pair* pairs;
+  const double *pendant, *distal, *proximal;
+  uint64_t n;
+  const uint8_t* q_codes;
+  const uint32_t *win_begin, *win_span;
+  uint32_t Q;
 };
 
-static int stage_entries(epa_ctx* ctx, const char* who, const epa_pair* pairs, const double* pendant, const double* distal,
-                         const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
-                         const uint32_t* win_span, uint32_t Q, EntryStage& st) {
-  const uint32_t* hb = host_view(win_begin, Q, st.hb_buf, ctx->stream);
-  st.hs = host_view(win_span, Q, st.hs_buf, ctx->stream);
-  if (!hb || !st.hs) return epa_fail(ctx, EPA_ERR_HIP, "cannot read window arrays");
-  int rc = check_windows(ctx, hb, st.hs, Q, &st.max_span, true);   // an empty window is the empty sum: lnL 0
-  if (rc) return rc;
-  // host arrays are validated (device arrays are the caller's responsibility): the first offending entry is named
-  const bool hp = !epa_is_device_ptr(pairs), hpe = pendant && !epa_is_device_ptr(pendant), hd = distal && !epa_is_device_ptr(distal);
-  const bool hx = proximal && !epa_is_device_ptr(proximal);
-  auto bad = [&](uint64_t i, const char* what) {
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": entry " + std::to_string(i) + ": " + what);
-  };
-  for (uint64_t i = 0; i < n; ++i) {
-    if (hp && pairs[i].branch_id >= ctx->B) return bad(i, "branch id out of range");
-    if (hp && pairs[i].seq_id >= Q) return bad(i, "sequence id out of range");
-    if (hpe && !(std::isfinite(pendant[i]) && pendant[i] >= 0.0)) return bad(i, "pendant length is negative or not finite");
-    if (hd && !(std::isfinite(distal[i]) && distal[i] >= 0.0)) return bad(i, "distal length is negative or not finite");
-    if (hx && !(std::isfinite(proximal[i]) && proximal[i] >= 0.0)) return bad(i, "proximal length is negative or not finite");
-    if (!proximal && hp && hd && distal[i] > ctx->h_blen[pairs[i].branch_id])
-      return bad(i, "distal length beyond the branch's length");
+// One call of the six: begin(), output() for every output, run()
+struct EntryCall {
+  epa_ctx* ctx;
+  const char* who;   // the entry point in error texts
+  EntryArgs a;
+  EntryStage st;
+  std::vector<uint32_t> hb_buf, hs_buf;   // own the host's views of the windows
+  const uint64_t* d_sid = nullptr;        // a RELL call's stream ids
+  bool empty = false;                     // n == 0: the call is done
+  struct Out { void *user, *dev; size_t bytes; } out[3] = {};
+  int n_out = 0;
+
+  // The entries' arguments checked (host arrays; the first offending entry is named) and staged on the device.
+  // pendant == distal == NULL (epa_dev_marginal_like): the pairs alone, no per-entry lengths are checked or staged.
+  int stage() {
+    const uint32_t* hb = host_view(a.win_begin, a.Q, hb_buf, ctx->stream);
+    st.h_span = host_view(a.win_span, a.Q, hs_buf, ctx->stream);
+    if (!hb || !st.h_span) return epa_fail(ctx, EPA_ERR_HIP, "cannot read window arrays");
+    int rc = check_windows(ctx, hb, st.h_span, a.Q, &st.max_span, true);   // an empty window is the empty sum: lnL 0
+    if (rc) return rc;
+    // host arrays are validated (device arrays are the caller's responsibility)
+    const bool hp = !epa_is_device_ptr(a.pairs), hpe = a.pendant && !epa_is_device_ptr(a.pendant);
+    const bool hd = a.distal && !epa_is_device_ptr(a.distal), hx = a.proximal && !epa_is_device_ptr(a.proximal);
+    auto bad = [&](uint64_t i, const char* what) {
+      return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": entry " + std::to_string(i) + ": " + what);
+    };
+    auto length_ok = [](double t) { return std::isfinite(t) && t >= 0.0; };
+    for (uint64_t i = 0; i < a.n; ++i) {
+      if (hp && a.pairs[i].branch_id >= ctx->B) return bad(i, "branch id out of range");
+      if (hp && a.pairs[i].seq_id >= a.Q) return bad(i, "sequence id out of range");
+      if (hpe && !length_ok(a.pendant[i])) return bad(i, "pendant length is negative or not finite");
+      if (hd && !length_ok(a.distal[i])) return bad(i, "distal length is negative or not finite");
+      if (hx && !length_ok(a.proximal[i])) return bad(i, "proximal length is negative or not finite");
+      if (!a.proximal && hp && hd && a.distal[i] > ctx->h_blen[a.pairs[i].branch_id])
+        return bad(i, "distal length beyond the branch's length");
+    }
+    auto lengths = [&](int slot, const double* t) { return t ? (const double*)epa_to_device(ctx, slot, t, sizeof(double) * a.n) : nullptr; };
+    st.n = a.n;
+    st.Q = a.Q;
+    st.d_codes = epa_codes_to_device(ctx, a.q_codes, a.Q);
+    st.d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, a.win_begin, sizeof(uint32_t) * a.Q);
+    st.d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, a.win_span, sizeof(uint32_t) * a.Q);
+    st.d_pairs = (const epa_pair*)epa_to_device(ctx, SLOT_PAIRS, a.pairs, sizeof(epa_pair) * a.n);
+    st.d_pen = lengths(SLOT_PENDANT, a.pendant);
+    st.d_dis = lengths(SLOT_DISTAL, a.distal);
+    st.d_prx = lengths(SLOT_PROXIMAL, a.proximal);
+    if (!st.d_codes || !st.d_begin || !st.d_span || !st.d_pairs || (a.pendant && !st.d_pen) || (a.distal && !st.d_dis) ||
+        (a.proximal && !st.d_prx))
+      return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
+    return EPA_OK;
   }
-  st.d_codes = epa_codes_to_device(ctx, q_codes, Q);
-  st.d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
-  st.d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
-  st.d_pairs = (const epa_pair*)epa_to_device(ctx, 4, pairs, sizeof(epa_pair) * n);
-  st.d_pen = pendant ? (const double*)epa_to_device(ctx, 7, pendant, sizeof(double) * n) : nullptr;
-  st.d_dis = distal ? (const double*)epa_to_device(ctx, 8, distal, sizeof(double) * n) : nullptr;
-  st.d_prx = proximal ? (const double*)epa_to_device(ctx, 9, proximal, sizeof(double) * n) : nullptr;
-  if (!st.d_codes || !st.d_begin || !st.d_span || !st.d_pairs || (pendant && !st.d_pen) || (distal && !st.d_dis) ||
-      (proximal && !st.d_prx))
-    return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
-  return EPA_OK;
-}
+
+  // How every call begins, in this order: the null check (`need`: the pointers needed, beside pairs, codes and windows,
+  // when n > 0); own_checks() of the call's other arguments; done (empty) when n == 0; the device selected and the
+  // entries staged.  A RELL call (stream_id != NULL; *stream_id may be null) also takes at most 2^32 - 1 entries and has
+  // its stream ids uploaded.
+  template <class Checks>
+  int begin(std::initializer_list<const void*> need, const uint64_t* const* stream_id, Checks own_checks) {
+    bool null_arg = !ctx || (a.n && (!a.pairs || !a.q_codes || !a.win_begin || !a.win_span));
+    for (const void* p : need) null_arg |= a.n && !p;
+    if (null_arg) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+    int rc = own_checks();
+    if (rc) return rc;
+    empty = a.n == 0;
+    if (empty) return EPA_OK;
+    if (stream_id && a.n > 0xffffffffull)
+      return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": more than 2^32 - 1 entries in one call");
+    EPA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = stage();
+    if (rc) return rc;
+    if (stream_id && *stream_id) {
+      d_sid = (const uint64_t*)epa_to_device(ctx, SLOT_RELL_STREAMS, *stream_id, sizeof(uint64_t) * a.Q);
+      if (!d_sid) return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
+    }
+    return EPA_OK;
+  }
+  int check_replicates(uint32_t replicates) {
+    if (replicates == 0 || replicates > (1u << 20))
+      return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": replicates must be 1 .. 2^20");
+    return EPA_OK;
+  }
+
+  // An output: null (not asked for), a device pointer (written in place) or a host pointer (staged by run())
+  void output(void* p, size_t bytes) { out[n_out++] = Out{p, p && epa_is_device_ptr(p) ? p : nullptr, bytes}; }
+  template <class T> T* dev(int i) const { return (T*)out[i].dev; }
+  // The host outputs get their place in SLOT_OUT, one after the other in the order of output(); launch() -> status; the
+  // host outputs copied out.  Host inputs were staged from pageable memory and must not change before the copies ran,
+  // hence the wait in every case
+  template <class Launch>
+  int run(Launch launch) {
+    size_t staged = 0;
+    for (int i = 0; i < n_out; ++i) staged += out[i].user && !out[i].dev ? out[i].bytes : 0;
+    char* d_stage = staged ? (char*)epa_scratch(ctx, SLOT_OUT, staged) : nullptr;
+    if (staged && !d_stage) return epa_fail(ctx, EPA_ERR_HIP, std::string("hipMalloc(") + who + " out)");
+    for (int i = 0; i < n_out; ++i)
+      if (out[i].user && !out[i].dev) { out[i].dev = d_stage; d_stage += out[i].bytes; }
+    int rc = launch();
+    if (rc) return rc;
+    for (int i = 0; i < n_out; ++i)
+      if (out[i].dev != out[i].user)
+        EPA_HIP(ctx, hipMemcpyAsync(out[i].user, out[i].dev, out[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return EPA_OK;
+  }
+};
+
+}  // namespace
 
 extern "C" int epa_dev_score_at(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
                                 const double* proximal, uint64_t n, const uint8_t* q_codes,
                                 const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, double* lnl) {
-  if (!ctx || (n && (!pairs || !pendant || !distal || !lnl || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (n == 0) return EPA_OK;
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
-  EntryStage st;
-  int rc = stage_entries(ctx, "score_at", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
-  if (rc) return rc;
-  const bool out_dev = epa_is_device_ptr(lnl);
-  double* d_lnl = out_dev ? lnl : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
-  if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(score_at out)");
-  rc = launch_score_at(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, d_lnl);
-  if (rc) return rc;
-  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(lnl, d_lnl, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  // host inputs were staged from pageable memory: they must not change before the copies ran
-  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EPA_OK;
+  EntryCall c{ctx, "score_at", {pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({pendant, distal, lnl}, nullptr, [] { return EPA_OK; });
+  if (rc || c.empty) return rc;
+  c.output(lnl, sizeof(double) * n);
+  return c.run([&] { return launch_score_at(ctx, c.st, c.dev<double>(0)); });
 }
 
 extern "C" int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
                                 const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
                                 const uint32_t* win_span, uint32_t Q, uint32_t pitch, double* site_lnl) {
-  if (!ctx || (n && (!pairs || !pendant || !distal || !site_lnl || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (n == 0) return EPA_OK;
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
-  EntryStage st;
-  int rc = stage_entries(ctx, "site_lnl", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
-  if (rc) return rc;
+  EntryCall c{ctx, "site_lnl", {pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({pendant, distal, site_lnl}, nullptr, [] { return EPA_OK; });
+  if (rc || c.empty) return rc;
   // the pitch must hold the longest window among the entries' queries (of all queries when the pairs live on the device)
   uint32_t need = 0;
-  if (!epa_is_device_ptr(pairs)) for (uint64_t i = 0; i < n; ++i) need = std::max(need, st.hs[pairs[i].seq_id]);
-  else need = st.max_span;
+  if (!epa_is_device_ptr(pairs)) for (uint64_t i = 0; i < n; ++i) need = std::max(need, c.st.h_span[pairs[i].seq_id]);
+  else need = c.st.max_span;
   if (pitch < need)
     return epa_fail(ctx, EPA_ERR_INVALID_ARG, "site_lnl: pitch " + std::to_string(pitch) + " is smaller than the longest window (" +
                                                   std::to_string(need) + ")");
   if (pitch == 0) return EPA_OK;   // every window is empty: there is nothing to write
-  const bool out_dev = epa_is_device_ptr(site_lnl);
-  const size_t bytes = sizeof(double) * (size_t)n * pitch;
-  double* d_rows = out_dev ? site_lnl : (double*)epa_scratch(ctx, 3, bytes);
-  if (!d_rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(site_lnl out)");
-  rc = launch_site_lnl(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, nullptr, n, st.d_codes, st.d_begin, st.d_span, pitch,
-                       true, d_rows, true);
-  if (rc) return rc;
-  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(site_lnl, d_rows, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EPA_OK;
+  c.output(site_lnl, sizeof(double) * (size_t)n * pitch);
+  return c.run([&] { return launch_site_lnl(ctx, c.st, nullptr, n, pitch, c.dev<double>(0), SITES_PAD | SITES_TIMED); });
 }
 
 extern "C" int epa_dev_marginal_like(epa_ctx* ctx, const epa_pair* pairs, uint64_t n, const double* x_frac,
                                      const double* x_logw, uint32_t Kx, const double* p_len, const double* p_logw,
                                      uint32_t Kp, const uint8_t* q_codes, const uint32_t* win_begin,
                                      const uint32_t* win_span, uint32_t Q, double* marginal, double* grid_lnl) {
-  if (!ctx || !x_frac || !x_logw || !p_len || !p_logw || (n && (!pairs || !marginal || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (Kx < 1 || Kx > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "marginal_like: Kx " + std::to_string(Kx) + " is outside 1 .. 64");
-  if (Kp < 1 || Kp > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "marginal_like: Kp " + std::to_string(Kp) + " is outside 1 .. 64");
-  auto bad = [&](const char* what, uint32_t i, const char* why) {
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string("marginal_like: ") + what + " node " + std::to_string(i) + ": " + why);
-  };
-  for (uint32_t i = 0; i < Kx; ++i) {
-    if (!(std::isfinite(x_frac[i]) && x_frac[i] >= 0.0 && x_frac[i] <= 1.0)) return bad("distal", i, "x_frac is outside [0, 1] or not finite");
-    if (!std::isfinite(x_logw[i])) return bad("distal", i, "the log weight is not finite");
-  }
-  for (uint32_t j = 0; j < Kp; ++j) {
-    if (!(std::isfinite(p_len[j]) && p_len[j] >= 0.0)) return bad("pendant", j, "p_len is negative or not finite");
-    if (!std::isfinite(p_logw[j])) return bad("pendant", j, "the log weight is not finite");
-  }
-  if (n == 0) return EPA_OK;
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
-  EntryStage st;
-  int rc = stage_entries(ctx, "marginal_like", pairs, nullptr, nullptr, nullptr, n, q_codes, win_begin, win_span, Q, st);
-  if (rc) return rc;
-  std::vector<double> rule;
+  EntryCall c{ctx, "marginal_like", {pairs, nullptr, nullptr, nullptr, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({marginal}, nullptr, [&] {
+    if (!x_frac || !x_logw || !p_len || !p_logw) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");   // whatever n is
+    if (Kx < 1 || Kx > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "marginal_like: Kx " + std::to_string(Kx) + " is outside 1 .. 64");
+    if (Kp < 1 || Kp > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "marginal_like: Kp " + std::to_string(Kp) + " is outside 1 .. 64");
+    auto bad = [&](const char* what, uint32_t i, const char* why) {
+      return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string("marginal_like: ") + what + " node " + std::to_string(i) + ": " + why);
+    };
+    for (uint32_t i = 0; i < Kx; ++i) {
+      if (!(std::isfinite(x_frac[i]) && x_frac[i] >= 0.0 && x_frac[i] <= 1.0)) return bad("distal", i, "x_frac is outside [0, 1] or not finite");
+      if (!std::isfinite(x_logw[i])) return bad("distal", i, "the log weight is not finite");
+    }
+    for (uint32_t j = 0; j < Kp; ++j) {
+      if (!(std::isfinite(p_len[j]) && p_len[j] >= 0.0)) return bad("pendant", j, "p_len is negative or not finite");
+      if (!std::isfinite(p_logw[j])) return bad("pendant", j, "the log weight is not finite");
+    }
+    return (int)EPA_OK;
+  });
+  if (rc || c.empty) return rc;
+  std::vector<double> rule;   // staged from pageable memory like the entries: run()'s wait covers it
   rule.reserve(2 * (size_t)(Kx + Kp));
   rule.insert(rule.end(), x_frac, x_frac + Kx);
   rule.insert(rule.end(), x_logw, x_logw + Kx);
   rule.insert(rule.end(), p_len, p_len + Kp);
   rule.insert(rule.end(), p_logw, p_logw + Kp);
-  const double* d_rule = (const double*)epa_to_device(ctx, 7, rule.data(), sizeof(double) * rule.size());
+  const double* d_rule = (const double*)epa_to_device(ctx, SLOT_MG_RULE, rule.data(), sizeof(double) * rule.size());
   if (!d_rule) return epa_fail(ctx, EPA_ERR_HIP, "marginal_like input upload failed");
-  const bool out_dev = epa_is_device_ptr(marginal), grid_dev = grid_lnl && epa_is_device_ptr(grid_lnl);
-  const size_t gbytes = sizeof(double) * (size_t)n * Kx * Kp;
-  double* d_m = out_dev ? marginal : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
-  double* d_g = !grid_lnl ? nullptr : grid_dev ? grid_lnl : (double*)epa_scratch(ctx, 8, gbytes);
-  if (!d_m || (grid_lnl && !d_g)) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(marginal_like out)");
-  rc = launch_marginal(ctx, st.d_pairs, n, d_rule, Kx, Kp, st.d_codes, st.d_begin, st.d_span, d_m, d_g);
-  if (rc) return rc;
-  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(marginal, d_m, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (grid_lnl && !grid_dev) EPA_HIP(ctx, hipMemcpyAsync(grid_lnl, d_g, gbytes, hipMemcpyDeviceToHost, ctx->stream));
-  // the rule and host inputs were staged from pageable memory: they must not change before the copies ran
-  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EPA_OK;
+  c.output(marginal, sizeof(double) * n);
+  c.output(grid_lnl, sizeof(double) * (size_t)n * Kx * Kp);
+  return c.run([&] { return launch_marginal(ctx, c.st, d_rule, Kx, Kp, c.dev<double>(0), c.dev<double>(1)); });
 }
 
 extern "C" int epa_dev_rell_support(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
                                     const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
                                     const uint32_t* win_span, uint32_t Q, const uint64_t* stream_id, uint32_t replicates,
                                     uint64_t seed, double* support) {
-  if (!ctx || (n && (!pairs || !pendant || !distal || !support || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (replicates == 0 || replicates > (1u << 20))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_support: replicates must be 1 .. 2^20");
-  if (n == 0) return EPA_OK;
-  if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_support: more than 2^32 - 1 entries in one call");
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
-  EntryStage st;
-  int rc = stage_entries(ctx, "rell_support", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
-  if (rc) return rc;
-  const uint64_t* d_sid = stream_id ? (const uint64_t*)epa_to_device(ctx, 17, stream_id, sizeof(uint64_t) * Q) : nullptr;
-  if (stream_id && !d_sid) return epa_fail(ctx, EPA_ERR_HIP, "rell_support input upload failed");
-  const bool out_dev = epa_is_device_ptr(support);
-  double* d_sup = out_dev ? support : (double*)epa_scratch(ctx, 3, sizeof(double) * n);
-  if (!d_sup) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_support out)");
-  rc = launch_rell(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, st.hs, Q, d_sid,
-                   replicates, seed, d_sup);
-  if (rc) return rc;
-  if (!out_dev) EPA_HIP(ctx, hipMemcpyAsync(support, d_sup, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EPA_OK;
+  EntryCall c{ctx, "rell_support", {pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({pendant, distal, support}, &stream_id, [&] { return c.check_replicates(replicates); });
+  if (rc || c.empty) return rc;
+  c.output(support, sizeof(double) * n);
+  return c.run([&] { return launch_rell(ctx, c.st, RellDraws{c.d_sid, replicates, seed}, c.dev<double>(0)); });
 }
 
 extern "C" int epa_dev_rell_tests(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
                                   const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
                                   const uint32_t* win_span, uint32_t Q, const uint64_t* stream_id, uint32_t replicates,
                                   uint64_t seed, double* support, double* elw, double* p_sh) {
-  if (!ctx || (n && (!pairs || !pendant || !distal || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (!support && !elw && !p_sh) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: support, elw and p_sh are all null");
-  if (replicates == 0 || replicates > (1u << 20))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: replicates must be 1 .. 2^20");
-  if (n == 0) return EPA_OK;
-  if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: more than 2^32 - 1 entries in one call");
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
-  EntryStage st;
-  int rc = stage_entries(ctx, "rell_tests", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
-  if (rc) return rc;
-  const uint64_t* d_sid = stream_id ? (const uint64_t*)epa_to_device(ctx, 17, stream_id, sizeof(uint64_t) * Q) : nullptr;
-  if (stream_id && !d_sid) return epa_fail(ctx, EPA_ERR_HIP, "rell_tests input upload failed");
-  // outputs in host memory are staged in scratch 3, one [n] block each
-  double* out[3] = {support, elw, p_sh};
-  double* d_out[3] = {nullptr, nullptr, nullptr};
-  size_t staged = 0;
-  for (int i = 0; i < 3; ++i) staged += out[i] && !epa_is_device_ptr(out[i]);
-  double* d_stage = staged ? (double*)epa_scratch(ctx, 3, sizeof(double) * n * staged) : nullptr;
-  if (staged && !d_stage) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_tests out)");
-  for (int i = 0, k = 0; i < 3; ++i)
-    if (out[i]) d_out[i] = epa_is_device_ptr(out[i]) ? out[i] : d_stage + (size_t)n * k++;
-  rc = launch_rell_tests(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, st.hs, Q, d_sid,
-                         replicates, seed, d_out[0], d_out[1], d_out[2]);
-  if (rc) return rc;
-  for (int i = 0; i < 3; ++i)
-    if (out[i] && d_out[i] != out[i])
-      EPA_HIP(ctx, hipMemcpyAsync(out[i], d_out[i], sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EPA_OK;
+  EntryCall c{ctx, "rell_tests", {pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({pendant, distal}, &stream_id, [&] {
+    if (!support && !elw && !p_sh) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_tests: support, elw and p_sh are all null");
+    return c.check_replicates(replicates);
+  });
+  if (rc || c.empty) return rc;
+  for (double* p : {support, elw, p_sh}) c.output(p, sizeof(double) * n);
+  return c.run([&] {
+    return launch_rell_tests(ctx, c.st, RellDraws{c.d_sid, replicates, seed}, c.dev<double>(0), c.dev<double>(1), c.dev<double>(2));
+  });
 }
 
 extern "C" int epa_dev_rell_au(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
@@ -1929,50 +1933,31 @@ extern "C" int epa_dev_rell_au(epa_ctx* ctx, const epa_pair* pairs, const double
                                uint64_t seed, const uint32_t* scale_pm, uint32_t n_scales, double* p_au, uint32_t* counts,
                                double* fit) {
   static const uint32_t default_pm[10] = {500, 600, 700, 800, 900, 1000, 1100, 1200, 1300, 1400};
-  if (!ctx || (n && (!pairs || !pendant || !distal || !q_codes || !win_begin || !win_span)))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
-  if (!p_au && !counts && !fit) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: p_au, counts and fit are all null");
-  if (replicates == 0 || replicates > (1u << 20))
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: replicates must be 1 .. 2^20");
-  if (!scale_pm) {
-    if (n_scales) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: n_scales must be 0 when scale_pm is null (the default scales)");
-    scale_pm = default_pm;
-    n_scales = 10;
-  } else if (n_scales < 1 || n_scales > 16) {
-    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: n_scales " + std::to_string(n_scales) + " is outside 1 .. 16");
-  }
-  for (uint32_t s = 0; s < n_scales; ++s)
-    if (scale_pm[s] < 100 || scale_pm[s] > 4000)
-      return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: scale " + std::to_string(s) + " is " + std::to_string(scale_pm[s]) +
-                                                    " per mille, outside 100 .. 4000");
-  if (n == 0) return EPA_OK;
-  if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: more than 2^32 - 1 entries in one call");
-  EPA_HIP(ctx, hipSetDevice(ctx->device));
-  EntryStage st;
-  int rc = stage_entries(ctx, "rell_au", pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q, st);
-  if (rc) return rc;
-  const uint64_t* d_sid = stream_id ? (const uint64_t*)epa_to_device(ctx, 17, stream_id, sizeof(uint64_t) * Q) : nullptr;
-  if (stream_id && !d_sid) return epa_fail(ctx, EPA_ERR_HIP, "rell_au input upload failed");
-  // outputs in host memory are staged in scratch 3: [p_au n | fit 2 n | counts n_scales x n]
-  void* out[3] = {p_au, fit, counts};
-  const size_t bytes[3] = {sizeof(double) * n, sizeof(double) * 2 * n, sizeof(uint32_t) * (size_t)n_scales * n};
-  void* d_out[3] = {nullptr, nullptr, nullptr};
-  size_t staged = 0;
-  for (int i = 0; i < 3; ++i) staged += out[i] && !epa_is_device_ptr(out[i]) ? bytes[i] : 0;
-  char* d_stage = staged ? (char*)epa_scratch(ctx, 3, staged) : nullptr;
-  if (staged && !d_stage) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_au out)");
-  for (int i = 0; i < 3; ++i)
-    if (out[i]) {
-      if (epa_is_device_ptr(out[i])) d_out[i] = out[i];
-      else { d_out[i] = d_stage; d_stage += bytes[i]; }
+  EntryCall c{ctx, "rell_au", {pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({pendant, distal}, &stream_id, [&] {
+    if (!p_au && !counts && !fit) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: p_au, counts and fit are all null");
+    if (int bad = c.check_replicates(replicates)) return bad;
+    if (!scale_pm) {
+      if (n_scales) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: n_scales must be 0 when scale_pm is null (the default scales)");
+      scale_pm = default_pm;
+      n_scales = 10;
+    } else if (n_scales < 1 || n_scales > 16) {
+      return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: n_scales " + std::to_string(n_scales) + " is outside 1 .. 16");
     }
-  rc = launch_rell_au(ctx, st.d_pairs, st.d_pen, st.d_dis, st.d_prx, n, st.d_codes, st.d_begin, st.d_span, st.hs, Q, d_sid,
-                      replicates, seed, scale_pm, n_scales, (double*)d_out[0], (uint32_t*)d_out[2], (double*)d_out[1]);
-  if (rc) return rc;
-  for (int i = 0; i < 3; ++i)
-    if (out[i] && d_out[i] != out[i]) EPA_HIP(ctx, hipMemcpyAsync(out[i], d_out[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EPA_OK;
+    for (uint32_t s = 0; s < n_scales; ++s)
+      if (scale_pm[s] < 100 || scale_pm[s] > 4000)
+        return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_au: scale " + std::to_string(s) + " is " + std::to_string(scale_pm[s]) +
+                                                      " per mille, outside 100 .. 4000");
+    return (int)EPA_OK;
+  });
+  if (rc || c.empty) return rc;
+  c.output(p_au, sizeof(double) * n);   // staged as [p_au n | fit 2 n | counts n_scales x n]
+  c.output(fit, sizeof(double) * 2 * n);
+  c.output(counts, sizeof(uint32_t) * (size_t)n_scales * n);
+  return c.run([&] {
+    return launch_rell_au(ctx, c.st, RellDraws{c.d_sid, replicates, seed}, scale_pm, n_scales, c.dev<double>(0), c.dev<uint32_t>(2),
+                          c.dev<double>(1));
+  });
 }
 
 extern "C" int epa_dev_select_candidates(epa_ctx* ctx, const double* lnl, uint32_t Q,

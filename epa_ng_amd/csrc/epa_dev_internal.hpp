@@ -218,7 +218,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 20;   // 13 .. 17: epa_dev_rell_support / _tests / _au, 18: epa_dev_rell_tests, 19: epa_dev_rell_au (rell.hip, epa_dev.hip)
+  static constexpr int N_SCRATCH = 20;   // the post-placement calls name theirs: EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -295,8 +295,6 @@ bool epa_is_device_ptr(const void* p);
 const void* epa_to_device(epa_ctx* ctx, int slot, const void* p, size_t bytes);
 // query code rows -> device in the one-byte layout the kernels read (unpacks the 4-bit wire format)
 const uint8_t* epa_codes_to_device(epa_ctx* ctx, const uint8_t* q_codes, uint32_t Q);
-// query code rows -> device in the one-byte layout the kernels read (unpacks the 4-bit wire format)
-const uint8_t* epa_codes_to_device(epa_ctx* ctx, const uint8_t* q_codes, uint32_t Q);
 // hst: the 16 statistics words of a thorough launch ([7] start, [8 + x] last exit of XCD x: ThArgs::xstamp)
 void epa_xcd_feedback(epa_ctx* ctx, uint64_t n_pairs, const unsigned long long* hst);
 // in-kernel s_memrealtime stamps are kept to 43 bits (24 h at 100 MHz) so that the XCD's share fits below them
@@ -315,6 +313,46 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
     if (e__ != hipSuccess)                                                                \
       return epa_fail(ctx, EPA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
+
+// ---- scratch slots of the post-placement entry points (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support,
+// _rell_tests, _rell_au: epa_dev.hip) and of their launchers (score_at.hip, marginal.hip, rell.hip).  The placement
+// path writes its slots as numbers: 0 .. 4 mean the same there, 5 .. 12 are its own (7 .. 9 too, within its own calls).
+// Among these six, 7 and 9 have two meanings.  A call with per-entry lengths stages them in 7 .. 9 (EntryCall::stage); marginal_like has no
+// lengths -- it hands the staging null for all three, so nothing of its own call sits there -- and keeps its rule and
+// its waves' grid values in 7 and 9 instead.  Every call stages what it reads before it launches, so what the other
+// meaning left behind in an earlier call is never read.
+enum EpaSlot : int {
+  SLOT_CODES = 0,         // query codes, one byte per site (epa_codes_to_device)
+  SLOT_BEGIN = 1,         // win_begin [Q]
+  SLOT_SPAN = 2,          // win_span [Q]
+  SLOT_OUT = 3,           // the outputs the caller wants in host memory, one after the other (EntryCall::run)
+  SLOT_PAIRS = 4,         // the entries' pairs [n]
+  SLOT_PENDANT = 7,       // per-entry lengths [n] each
+  SLOT_DISTAL = 8,
+  SLOT_PROXIMAL = 9,
+  SLOT_MG_RULE = 7,       // marginal_like: x_frac [Kx] | x_logw [Kx] | p_len [Kp] | p_logw [Kp]
+  SLOT_MG_WAVES = 9,      // marginal_like: [waves][Kx][Kp] grid values (launch_marginal)
+  SLOT_RELL_SORT = 13,    // [keys n | idx n | sorted keys n | order n | wins n | rocprim temp]
+  SLOT_RELL_BOUNDS = 14,  // [2][Q] first and one-past-last sorted position of every query
+  SLOT_RELL_GROUPS = 15,  // one RellGroup per query that has entries
+  SLOT_RELL_ROWS = 16,    // site rows of one batch [positions][pitch]
+  SLOT_RELL_STREAMS = 17, // stream_id [Q]
+  SLOT_RELL_TESTS = 18,   // rell_tests: [L n | T n | weight sums n | SH counts n]
+  SLOT_RELL_AU = 19,      // rell_au: win counters [scale][n]
+};
+
+// The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,
+// distal, proximal) over Q queries.  d_prx null: branch length - distal; all three lengths null: marginal_like
+struct EntryStage {
+  const epa_pair* d_pairs = nullptr;
+  const double *d_pen = nullptr, *d_dis = nullptr, *d_prx = nullptr;
+  uint64_t n = 0;
+  const uint8_t* d_codes = nullptr;
+  const uint32_t *d_begin = nullptr, *d_span = nullptr;
+  const uint32_t* h_span = nullptr;   // the host's view of win_span
+  uint32_t Q = 0;
+  uint32_t max_span = 0;              // the longest window of the Q queries
+};
 
 // ---- span classes of the thorough kernels: a launch covers pairs whose window needs the same
 // kernel instantiation, so one long window does not drag a whole chunk onto the big-register
@@ -378,38 +416,31 @@ int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pa
 int launch_thorough_aa_mfma(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* d_order, uint64_t n_pairs,
                             const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span,
                             uint32_t max_span, epa_result* d_out, unsigned long long* d_stats);
-// lnL of n entries (pair, pendant, distal, proximal or null = blen - distal) at the given lengths (score_at.hip)
-int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                    const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                    const uint32_t* d_span, double* d_lnl);
+// lnL of the entries at their lengths (score_at.hip)
+int launch_score_at(epa_ctx* ctx, const EntryStage& e, double* d_lnl);
 // per-site log-likelihoods of the same entries (k_score_at<S, true>): row i of d_rows [n_rows][pitch] takes entry
-// d_order[i] (null: entry i), columns [0, span); pad: the columns from the span up to the pitch are written as 0.0.
-// timed: records the "site_lnl" timer (the RELL driver times the whole call as "rell" instead)
-int launch_site_lnl(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                    const double* d_proximal, const uint32_t* d_order, uint64_t n_rows, const uint8_t* d_codes,
-                    const uint32_t* d_begin, const uint32_t* d_span, uint32_t pitch, bool pad, double* d_rows,
-                    bool timed);
-// RELL bootstrap support of n entries competing per query (rell.hip); h_span: the host's view of the spans
-int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                uint32_t replicates, uint64_t seed, double* d_support);
-// RELL support, expected likelihood weights and SH p-values from the same replicates (rell.hip); each output [n] or null
-int launch_rell_tests(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                      const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                      const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                      uint32_t replicates, uint64_t seed, double* d_support, double* d_elw, double* d_p_sh);
-// AU p-values from multiscale RELL replicates (rell.hip): h_scale_pm [n_scales <= 16] per mille (host); d_p_au [n],
-// d_counts [n_scales][n], d_fit [n][2], each or null
-int launch_rell_au(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                   const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                   const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                   uint32_t replicates, uint64_t seed, const uint32_t* h_scale_pm, uint32_t n_scales, double* d_p_au,
-                   uint32_t* d_counts, double* d_fit);
-// marginal likelihood of n entries over a (distal x pendant) tensor rule (marginal.hip); d_rule: x_frac [Kx] | x_logw
-// [Kx] | p_len [Kp] | p_logw [Kp]; d_grid: [n][Kx][Kp] or null.  Uses scratch slot 9 for the waves' grid values
-int launch_marginal(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n, const double* d_rule, uint32_t Kx, uint32_t Kp,
-                    const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, double* d_marginal,
+// d_order[i] (null: entry i), columns [0, span).  SITES_PAD: the columns from the span up to the pitch are written as
+// 0.0; SITES_TIMED: records the "site_lnl" timer (the RELL driver times the whole call under its own instead)
+enum SiteLnlFlags : unsigned { SITES_PLAIN = 0u, SITES_PAD = 1u, SITES_TIMED = 2u };
+int launch_site_lnl(epa_ctx* ctx, const EntryStage& e, const uint32_t* d_order, uint64_t n_rows, uint32_t pitch,
+                    double* d_rows, unsigned flags);
+// The RELL calls (rell.hip): the entries compete per query; e.n < 2^32.  Which replicates are drawn:
+struct RellDraws {
+  const uint64_t* d_stream_id;   // [Q] or null: the query's index
+  uint32_t replicates;
+  uint64_t seed;
+};
+// bootstrap support [n]
+int launch_rell(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support);
+// support, expected likelihood weights and SH p-values from the same replicates; each output [n] or null
+int launch_rell_tests(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support, double* d_elw, double* d_p_sh);
+// AU p-values from multiscale replicates: h_scale_pm [n_scales <= 16] per mille (host); d_p_au [n], d_counts
+// [n_scales][n], d_fit [n][2], each or null
+int launch_rell_au(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, const uint32_t* h_scale_pm, uint32_t n_scales,
+                   double* d_p_au, uint32_t* d_counts, double* d_fit);
+// marginal likelihood of the entries' pairs over a (distal x pendant) tensor rule (marginal.hip); d_rule: x_frac [Kx] |
+// x_logw [Kx] | p_len [Kp] | p_logw [Kp]; d_grid: [n][Kx][Kp] or null
+int launch_marginal(epa_ctx* ctx, const EntryStage& e, const double* d_rule, uint32_t Kx, uint32_t Kp, double* d_marginal,
                     double* d_grid);
 int launch_select(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold,
                   epa_pair* d_pairs, uint64_t max_pairs, uint64_t* n_pairs,

@@ -137,45 +137,36 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
     ts = clk::now();
     epa_dev_set_query_layout(dev.ctx(), enc.stride);
     epa_dev_set_query_packing(dev.ctx(), enc.bits);
-    const int rc = epa_dev_score_at(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
-                                    enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
-                                    lnl.data());
-    if (rc != EPA_OK)
-      throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+    auto check = [&](int rc) {
+      if (rc != EPA_OK)
+        throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+    };
+    // the calls on the rows at their own lengths begin with the same ten arguments; `rest` is what follows them
+    auto rows = [&](auto fn, auto... rest) {
+      check(fn(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(), enc.codes.data(),
+               enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(), rest...));
+    };
+    rows(epa_dev_score_at, lnl.data());
     std::vector<double> support, elw, p_sh, p_au;
     if (options.rell_replicates) {
-      std::vector<uint64_t> stream_id(target.begin(), target.end());
+      const std::vector<uint64_t> stream_id(target.begin(), target.end());
+      const uint32_t R = options.rell_replicates;
+      const uint64_t seed = options.rell_seed;
       support.resize(pairs.size());
       if (options.rell_tests) { elw.resize(pairs.size()); p_sh.resize(pairs.size()); }
-      const int rrc = options.rell_tests
-          ? epa_dev_rell_tests(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
-                               enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
-                               stream_id.data(), options.rell_replicates, options.rell_seed, support.data(), elw.data(),
-                               p_sh.data())
-          : epa_dev_rell_support(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
-                                 enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
-                                 stream_id.data(), options.rell_replicates, options.rell_seed, support.data());
-      if (rrc != EPA_OK)
-        throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rrc) + ")"};
+      if (options.rell_tests) rows(epa_dev_rell_tests, stream_id.data(), R, seed, support.data(), elw.data(), p_sh.data());
+      else rows(epa_dev_rell_support, stream_id.data(), R, seed, support.data());
       if (options.au) {
         p_au.resize(pairs.size());
-        const int arc = epa_dev_rell_au(dev.ctx(), pairs.data(), pendant.data(), distal.data(), nullptr, pairs.size(),
-                                        enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
-                                        stream_id.data(), options.rell_replicates, options.rell_seed, nullptr, 0, p_au.data(),
-                                        nullptr, nullptr);
-        if (arc != EPA_OK)
-          throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(arc) + ")"};
+        rows(epa_dev_rell_au, stream_id.data(), R, seed, nullptr, 0, p_au.data(), nullptr, nullptr);
       }
     }
     std::vector<double> marginal;
     if (options.posterior) {
       marginal.resize(pairs.size());
-      const int mrc = epa_dev_marginal_like(dev.ctx(), pairs.data(), pairs.size(), x_frac.data(), x_logw.data(),
-                                            (uint32_t)x_frac.size(), p_len.data(), p_logw.data(), (uint32_t)p_len.size(),
-                                            enc.codes.data(), enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(),
-                                            marginal.data(), nullptr);
-      if (mrc != EPA_OK)
-        throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(mrc) + ")"};
+      check(epa_dev_marginal_like(dev.ctx(), pairs.data(), pairs.size(), x_frac.data(), x_logw.data(), (uint32_t)x_frac.size(),
+                                  p_len.data(), p_logw.data(), (uint32_t)p_len.size(), enc.codes.data(), enc.win_begin.data(),
+                                  enc.win_span.data(), (uint32_t)named.size(), marginal.data(), nullptr));
     }
     st.seconds_place += std::chrono::duration<double>(clk::now() - ts).count();
     size_t k = 0;

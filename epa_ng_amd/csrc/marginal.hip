@@ -240,8 +240,7 @@ __global__ void __launch_bounds__(64) k_marginal(const MgArgs a) {
 
 }  // namespace
 
-int launch_marginal(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n, const double* d_rule, uint32_t Kx, uint32_t Kp,
-                    const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, double* d_marginal,
+int launch_marginal(epa_ctx* ctx, const EntryStage& e, const double* d_rule, uint32_t Kx, uint32_t Kp, double* d_marginal,
                     double* d_grid) {
   MgArgs a;
   a.m = ctx->dmodel;
@@ -250,25 +249,25 @@ int launch_marginal(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n, const dou
   a.cinv = ctx->cinv;
   a.inv_w0 = ctx->inv_w0;
   a.blen = ctx->blen;
-  a.pairs = d_pairs;
+  a.pairs = e.d_pairs;
   a.x_frac = d_rule;
   a.x_logw = d_rule + Kx;
   a.p_len = d_rule + 2 * (size_t)Kx;
   a.p_logw = d_rule + 2 * (size_t)Kx + Kp;
   a.Kx = Kx;
   a.Kp = Kp;
-  a.codes = d_codes;
+  a.codes = e.d_codes;
   a.crel = ctx->code_stride ? 1u : 0u;
   a.cstride = a.crel ? ctx->code_stride : ctx->W;
-  a.win_begin = d_begin;
-  a.win_span = d_span;
+  a.win_begin = e.d_begin;
+  a.win_span = e.d_span;
   a.marginal = d_marginal;
   a.grid = d_grid;
-  a.n = n;
+  a.n = e.n;
   a.W = ctx->W;
   // persistent grid: neither n nor a branch id reaches a grid dimension
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->n_cu * 8);
-  a.vbuf = (double*)epa_scratch(ctx, 9, sizeof(double) * (size_t)grid * Kx * Kp);
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(e.n, (uint64_t)ctx->n_cu * 8);
+  a.vbuf = (double*)epa_scratch(ctx, SLOT_MG_WAVES, sizeof(double) * (size_t)grid * Kx * Kp);
   if (!a.vbuf) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(marginal_like grid values)");
   const size_t lds = sizeof(double) * (size_t)(2 + TJ) * ctx->hmodel.c * ctx->s;
   epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_MARGINAL));

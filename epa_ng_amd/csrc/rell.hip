@@ -12,7 +12,7 @@
 //              plain fp64 adds, no centring, no reassociation
 //   winner     the largest score; ties go to the smaller branch id, then to the smaller entry index
 //
-// Host side (launch_rell): the entries are grouped by query with a stable radix sort of their indices, so a group
+// Host side (rell_run): the entries are grouped by query with a stable radix sort of their indices, so a group
 // keeps the caller's entry order; the groups are worked off in batches of whole queries whose site rows fit a fixed
 // scratch budget (one query alone may exceed it: its rows are then allocated as they are).
 //
@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(256) k_rell_tests_out(const uint32_t* __restri
   if (p_sh) p_sh[e] = (double)sh[i] / R;
 }
 
-// What launch_rell and launch_rell_tests share: the entries grouped by query, the groups dealt into batches of whole
+// What the RELL calls share (rell_run): the entries grouped by query, the groups dealt into batches of whole
 // queries, the site rows' scratch, the win counters cleared.  `who` names the entry point in error texts
 struct RellBatch {
   size_t g0, g1;      // groups [g0, g1)
@@ -554,9 +554,8 @@ int rell_plan(epa_ctx* ctx, const char* who, const epa_pair* d_pairs, uint32_t n
   (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                                  (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0, bits, ctx->stream);
   const size_t nb = (sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255;
-  // scratch 13: [keys n | idx n | sorted keys n | order n | wins n | rocprim temp]
-  char* base = (char*)epa_scratch(ctx, 13, 5 * nb + temp_bytes);
-  uint32_t* d_bounds = (uint32_t*)epa_scratch(ctx, 14, sizeof(uint32_t) * 2 * (size_t)Q);
+  char* base = (char*)epa_scratch(ctx, SLOT_RELL_SORT, 5 * nb + temp_bytes);
+  uint32_t* d_bounds = (uint32_t*)epa_scratch(ctx, SLOT_RELL_BOUNDS, sizeof(uint32_t) * 2 * (size_t)Q);
   if (!base || !d_bounds) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell grouping)");
   uint32_t *d_keys = (uint32_t*)base, *d_idx = (uint32_t*)(base + nb), *d_sorted = (uint32_t*)(base + 2 * nb);
   uint32_t *d_order = (uint32_t*)(base + 3 * nb), *d_wins = (uint32_t*)(base + 4 * nb);
@@ -577,7 +576,7 @@ int rell_plan(epa_ctx* ctx, const char* who, const epa_pair* d_pairs, uint32_t n
       covered += groups.back().count;
     }
   if (covered != n) return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string(who) + ": a sequence id is out of range");
-  RellGroup* d_groups = (RellGroup*)epa_scratch(ctx, 15, sizeof(RellGroup) * groups.size());
+  RellGroup* d_groups = (RellGroup*)epa_scratch(ctx, SLOT_RELL_GROUPS, sizeof(RellGroup) * groups.size());
   if (!d_groups) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell groups)");
   EPA_HIP(ctx, hipMemcpyAsync(d_groups, groups.data(), sizeof(RellGroup) * groups.size(), hipMemcpyHostToDevice, ctx->stream));
 
@@ -596,7 +595,7 @@ int rell_plan(epa_ctx* ctx, const char* who, const epa_pair* d_pairs, uint32_t n
     batches.push_back(b);
     g0 = b.g1;
   }
-  plan.d_rows = (double*)epa_scratch(ctx, 16, rows_bytes);
+  plan.d_rows = (double*)epa_scratch(ctx, SLOT_RELL_ROWS, rows_bytes);
   if (!plan.d_rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell site rows)");
   plan.d_groups = d_groups;
   plan.d_order = d_order;
@@ -605,28 +604,24 @@ int rell_plan(epa_ctx* ctx, const char* who, const epa_pair* d_pairs, uint32_t n
 }
 
 // what does not change from batch to batch
-RellArgs rell_args(const RellPlan& plan, const epa_pair* d_pairs, const uint32_t* d_span, const uint64_t* d_stream_id,
-                   uint32_t replicates, uint64_t seed) {
+RellArgs rell_args(const RellPlan& plan, const EntryStage& e, const RellDraws& dr) {
   RellArgs a{};
   a.order = plan.d_order;
-  a.pairs = d_pairs;
-  a.span = d_span;
-  a.stream_id = d_stream_id;
+  a.pairs = e.d_pairs;
+  a.span = e.d_span;
+  a.stream_id = dr.d_stream_id;
   a.rows = plan.d_rows;
-  a.R = replicates;
-  a.k0 = (uint32_t)seed;
-  a.k1 = (uint32_t)(seed >> 32);
+  a.R = dr.replicates;
+  a.k0 = (uint32_t)dr.seed;
+  a.k1 = (uint32_t)(dr.seed >> 32);
   a.wins = plan.d_wins;
   return a;
 }
 
 // the batch's site rows computed and its part of the arguments set
-int rell_batch_rows(epa_ctx* ctx, const RellPlan& plan, const RellBatch& b, const epa_pair* d_pairs, const double* d_pendant,
-                    const double* d_distal, const double* d_proximal, const uint8_t* d_codes, const uint32_t* d_begin,
-                    const uint32_t* d_span, RellArgs& a) {
+int rell_batch_rows(epa_ctx* ctx, const RellPlan& plan, const RellBatch& b, const EntryStage& e, RellArgs& a) {
   const uint32_t pos0 = plan.groups[b.g0].start;
-  int rc = launch_site_lnl(ctx, d_pairs, d_pendant, d_distal, d_proximal, plan.d_order + pos0, b.rows, d_codes, d_begin,
-                           d_span, b.pitch, false, plan.d_rows, false);
+  int rc = launch_site_lnl(ctx, e, plan.d_order + pos0, b.rows, b.pitch, plan.d_rows, SITES_PLAIN);
   if (rc) return rc;
   a.groups = plan.d_groups + b.g0;
   a.n_groups = (uint32_t)(b.g1 - b.g0);
@@ -635,104 +630,101 @@ int rell_batch_rows(epa_ctx* ctx, const RellPlan& plan, const RellBatch& b, cons
   return EPA_OK;
 }
 
+// One RELL call, timed as `timer`.  The variant supplies prepare(a) -> status: its own scratch cleared, a.wins redirected if
+// it counts elsewhere; batch(plan, b, a, grid): its kernels on a batch whose site rows are ready, `grid` the workgroups of
+// the kernel that runs one query each; finish(plan, grid): the kernel that writes the outputs, one thread per entry
+template <class Prepare, class Batch, class Finish>
+int rell_run(epa_ctx* ctx, const char* who, int timer, const EntryStage& e, const RellDraws& dr, Prepare prepare, Batch batch,
+             Finish finish) {
+  const uint32_t n = (uint32_t)e.n;   // the caller checked e.n < 2^32
+  epa_timer_start(ctx, epa_t(ctx, timer));
+  RellPlan plan;
+  int rc = rell_plan(ctx, who, e.d_pairs, n, e.h_span, e.Q, plan);
+  if (rc) return rc;
+  RellArgs a = rell_args(plan, e, dr);
+  rc = prepare(a);
+  if (rc) return rc;
+  for (const RellBatch& b : plan.batches) {
+    rc = rell_batch_rows(ctx, plan, b, e, a);
+    if (rc) return rc;
+    batch(plan, b, a, dim3((uint32_t)std::min<uint64_t>(a.n_groups, (uint64_t)ctx->n_cu * 8)));
+    EPA_HIP(ctx, hipGetLastError());
+  }
+  finish(plan, dim3((n + 255) / 256));
+  epa_timer_stop(ctx, epa_t(ctx, timer));
+  EPA_HIP(ctx, hipGetLastError());
+  return EPA_OK;
+}
+
 }  // namespace
 
-int launch_rell(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
-                const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                uint32_t replicates, uint64_t seed, double* d_support) {
-  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32
-  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL));
-  RellPlan plan;
-  int rc = rell_plan(ctx, "rell_support", d_pairs, n, h_span, Q, plan);
-  if (rc) return rc;
-  RellArgs a = rell_args(plan, d_pairs, d_span, d_stream_id, replicates, seed);
-  for (const RellBatch& b : plan.batches) {
-    rc = rell_batch_rows(ctx, plan, b, d_pairs, d_pendant, d_distal, d_proximal, d_codes, d_begin, d_span, a);
-    if (rc) return rc;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(a.n_groups, (uint64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(k_rell, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, a);
-    EPA_HIP(ctx, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_rell_support, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, plan.d_wins, plan.d_order, n,
-                     (double)replicates, d_support);
-  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL));
-  EPA_HIP(ctx, hipGetLastError());
-  return EPA_OK;
+int launch_rell(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support) {
+  return rell_run(
+      ctx, "rell_support", epa_ctx::T_RELL, e, dr, [](RellArgs&) -> int { return EPA_OK; },
+      [&](const RellPlan&, const RellBatch&, const RellArgs& a, dim3 grid) {
+        hipLaunchKernelGGL(k_rell, grid, dim3(RELL_THREADS), 0, ctx->stream, a);
+      },
+      [&](const RellPlan& plan, dim3 grid) {
+        hipLaunchKernelGGL(k_rell_support, grid, dim3(256), 0, ctx->stream, plan.d_wins, plan.d_order, (uint32_t)e.n,
+                           (double)dr.replicates, d_support);
+      });
 }
 
-int launch_rell_tests(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                      const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
-                      const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                      uint32_t replicates, uint64_t seed, double* d_support, double* d_elw, double* d_p_sh) {
-  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32
-  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL_TESTS));
-  RellPlan plan;
-  int rc = rell_plan(ctx, "rell_tests", d_pairs, n, h_span, Q, plan);
-  if (rc) return rc;
-  // scratch 18: [L n | T n | weight sums n | SH counts n]; the two accumulators are cleared per call, L and T written in full
-  const size_t db = (sizeof(double) * (size_t)n + 255) & ~(size_t)255;
-  char* base = (char*)epa_scratch(ctx, 18, 3 * db + sizeof(uint32_t) * (size_t)n);
-  if (!base) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_tests accumulators)");
-  double *d_L = (double*)base, *d_T = (double*)(base + db), *d_sum = (double*)(base + 2 * db);
-  uint32_t* d_sh = (uint32_t*)(base + 3 * db);
-  EPA_HIP(ctx, hipMemsetAsync(d_sum, 0, db + sizeof(uint32_t) * (size_t)n, ctx->stream));
+int launch_rell_tests(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support, double* d_elw, double* d_p_sh) {
+  const uint32_t n = (uint32_t)e.n;
+  double *d_L = nullptr, *d_T = nullptr;
   RellTestsArgs ta{};
-  ta.r = rell_args(plan, d_pairs, d_span, d_stream_id, replicates, seed);
-  ta.L = d_L;
-  ta.T = d_T;
-  ta.elw = d_sum;
-  ta.sh = d_sh;
-  for (const RellBatch& b : plan.batches) {
-    rc = rell_batch_rows(ctx, plan, b, d_pairs, d_pendant, d_distal, d_proximal, d_codes, d_begin, d_span, ta.r);
-    if (rc) return rc;
-    const uint32_t npos = (uint32_t)b.rows;
-    hipLaunchKernelGGL(k_rell_observed, dim3((npos + 255) / 256), dim3(256), 0, ctx->stream, plan.d_rows, b.pitch, ta.r.pos0,
-                       npos, plan.d_order, d_pairs, d_span, d_L);
-    hipLaunchKernelGGL(k_rell_threshold, dim3((ta.r.n_groups + 255) / 256), dim3(256), 0, ctx->stream, ta.r.groups,
-                       ta.r.n_groups, d_L, d_T);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(ta.r.n_groups, (uint64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(k_rell_tests, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, ta);
-    EPA_HIP(ctx, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_rell_tests_out, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, plan.d_wins, d_sh, d_sum,
-                     plan.d_order, n, (double)replicates, d_support, d_elw, d_p_sh);
-  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL_TESTS));
-  EPA_HIP(ctx, hipGetLastError());
-  return EPA_OK;
+  return rell_run(
+      ctx, "rell_tests", epa_ctx::T_RELL_TESTS, e, dr,
+      [&](RellArgs&) -> int {
+        // [L n | T n | weight sums n | SH counts n]; the two accumulators are cleared per call, L and T written in full
+        const size_t db = (sizeof(double) * (size_t)n + 255) & ~(size_t)255;
+        char* base = (char*)epa_scratch(ctx, SLOT_RELL_TESTS, 3 * db + sizeof(uint32_t) * (size_t)n);
+        if (!base) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_tests accumulators)");
+        ta.L = d_L = (double*)base;
+        ta.T = d_T = (double*)(base + db);
+        ta.elw = (double*)(base + 2 * db);
+        ta.sh = (uint32_t*)(base + 3 * db);
+        EPA_HIP(ctx, hipMemsetAsync(ta.elw, 0, db + sizeof(uint32_t) * (size_t)n, ctx->stream));
+        return EPA_OK;
+      },
+      [&](const RellPlan& plan, const RellBatch& b, const RellArgs& a, dim3 grid) {
+        const uint32_t npos = (uint32_t)b.rows;
+        ta.r = a;
+        hipLaunchKernelGGL(k_rell_observed, dim3((npos + 255) / 256), dim3(256), 0, ctx->stream, plan.d_rows, b.pitch, a.pos0,
+                           npos, plan.d_order, e.d_pairs, e.d_span, d_L);
+        hipLaunchKernelGGL(k_rell_threshold, dim3((a.n_groups + 255) / 256), dim3(256), 0, ctx->stream, a.groups, a.n_groups, d_L, d_T);
+        hipLaunchKernelGGL(k_rell_tests, grid, dim3(RELL_THREADS), 0, ctx->stream, ta);
+      },
+      [&](const RellPlan& plan, dim3 grid) {
+        hipLaunchKernelGGL(k_rell_tests_out, grid, dim3(256), 0, ctx->stream, plan.d_wins, ta.sh, ta.elw, plan.d_order, n,
+                           (double)dr.replicates, d_support, d_elw, d_p_sh);
+      });
 }
 
-int launch_rell_au(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                   const double* d_proximal, uint64_t n64, const uint8_t* d_codes, const uint32_t* d_begin,
-                   const uint32_t* d_span, const uint32_t* h_span, uint32_t Q, const uint64_t* d_stream_id,
-                   uint32_t replicates, uint64_t seed, const uint32_t* h_scale_pm, uint32_t n_scales, double* d_p_au,
-                   uint32_t* d_counts, double* d_fit) {
-  const uint32_t n = (uint32_t)n64;   // the caller checked n64 < 2^32 and n_scales <= MS_SCALES
-  epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_RELL_AU));
-  RellPlan plan;
-  int rc = rell_plan(ctx, "rell_au", d_pairs, n, h_span, Q, plan);
-  if (rc) return rc;
-  // scratch 19: the win counters [scale][n] by sorted position, cleared per call
+int launch_rell_au(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, const uint32_t* h_scale_pm, uint32_t n_scales,
+                   double* d_p_au, uint32_t* d_counts, double* d_fit) {
+  const uint32_t n = (uint32_t)e.n;   // the caller checked n_scales <= MS_SCALES
   const size_t cbytes = sizeof(uint32_t) * (size_t)n_scales * n;
-  uint32_t* d_ms = (uint32_t*)epa_scratch(ctx, 19, cbytes);
-  if (!d_ms) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_au counters)");
-  EPA_HIP(ctx, hipMemsetAsync(d_ms, 0, cbytes, ctx->stream));
+  uint32_t* d_ms = nullptr;
   RellMsArgs ma{};
-  ma.r = rell_args(plan, d_pairs, d_span, d_stream_id, replicates, seed);
-  ma.r.wins = d_ms;
   ma.sc.n = n_scales;
   for (uint32_t s = 0; s < n_scales; ++s) ma.sc.pm[s] = h_scale_pm[s];
   ma.n = n;
-  for (const RellBatch& b : plan.batches) {
-    rc = rell_batch_rows(ctx, plan, b, d_pairs, d_pendant, d_distal, d_proximal, d_codes, d_begin, d_span, ma.r);
-    if (rc) return rc;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(ma.r.n_groups, (uint64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(k_rell_ms, dim3(grid), dim3(RELL_THREADS), 0, ctx->stream, ma);
-    EPA_HIP(ctx, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_rell_au_fit, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_ms, plan.d_order, d_pairs, d_span,
-                     ma.sc, n, replicates, d_p_au, d_counts, d_fit);
-  epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_RELL_AU));
-  EPA_HIP(ctx, hipGetLastError());
-  return EPA_OK;
+  return rell_run(
+      ctx, "rell_au", epa_ctx::T_RELL_AU, e, dr,
+      [&](RellArgs& a) -> int {   // the win counters [scale][n] by sorted position, cleared per call
+        a.wins = d_ms = (uint32_t*)epa_scratch(ctx, SLOT_RELL_AU, cbytes);
+        if (!d_ms) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_au counters)");
+        EPA_HIP(ctx, hipMemsetAsync(d_ms, 0, cbytes, ctx->stream));
+        return EPA_OK;
+      },
+      [&](const RellPlan&, const RellBatch&, const RellArgs& a, dim3 grid) {
+        ma.r = a;
+        hipLaunchKernelGGL(k_rell_ms, grid, dim3(RELL_THREADS), 0, ctx->stream, ma);
+      },
+      [&](const RellPlan& plan, dim3 grid) {
+        hipLaunchKernelGGL(k_rell_au_fit, grid, dim3(256), 0, ctx->stream, d_ms, plan.d_order, e.d_pairs, e.d_span, ma.sc, n,
+                           dr.replicates, d_p_au, d_counts, d_fit);
+      });
 }

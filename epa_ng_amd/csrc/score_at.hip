@@ -179,24 +179,22 @@ __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
 
 }  // namespace
 
-static void fill_args(epa_ctx* ctx, ScArgs& a, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                      const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                      const uint32_t* d_span) {
+static void fill_args(epa_ctx* ctx, ScArgs& a, const EntryStage& e, uint64_t n) {
   a.m = ctx->dmodel;
   a.refT = ctx->refT;
   a.scSum = ctx->scSum;
   a.cinv = ctx->cinv;
   a.inv_w0 = ctx->inv_w0;
   a.blen = ctx->blen;
-  a.pairs = d_pairs;
-  a.pendant = d_pendant;
-  a.distal = d_distal;
-  a.proximal = d_proximal;
-  a.codes = d_codes;
+  a.pairs = e.d_pairs;
+  a.pendant = e.d_pen;
+  a.distal = e.d_dis;
+  a.proximal = e.d_prx;
+  a.codes = e.d_codes;
   a.crel = ctx->code_stride ? 1u : 0u;
   a.cstride = a.crel ? ctx->code_stride : ctx->W;
-  a.win_begin = d_begin;
-  a.win_span = d_span;
+  a.win_begin = e.d_begin;
+  a.win_span = e.d_span;
   a.lnl = nullptr;
   a.n = n;
   a.W = ctx->W;
@@ -206,14 +204,12 @@ static void fill_args(epa_ctx* ctx, ScArgs& a, const epa_pair* d_pairs, const do
   a.pad = 0;
 }
 
-int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                    const double* d_proximal, uint64_t n, const uint8_t* d_codes, const uint32_t* d_begin,
-                    const uint32_t* d_span, double* d_lnl) {
+int launch_score_at(epa_ctx* ctx, const EntryStage& e, double* d_lnl) {
   ScArgs a;
-  fill_args(ctx, a, d_pairs, d_pendant, d_distal, d_proximal, n, d_codes, d_begin, d_span);
+  fill_args(ctx, a, e, e.n);
   a.lnl = d_lnl;
   // persistent grid: neither n nor a branch id reaches a grid dimension
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->n_cu * 8);
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(e.n, (uint64_t)ctx->n_cu * 8);
   epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_SCORE));
   if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
   else hipLaunchKernelGGL((k_score_at<20, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
@@ -222,16 +218,15 @@ int launch_score_at(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_penda
   return EPA_OK;
 }
 
-int launch_site_lnl(epa_ctx* ctx, const epa_pair* d_pairs, const double* d_pendant, const double* d_distal,
-                    const double* d_proximal, const uint32_t* d_order, uint64_t n_rows, const uint8_t* d_codes,
-                    const uint32_t* d_begin, const uint32_t* d_span, uint32_t pitch, bool pad, double* d_rows,
-                    bool timed) {
+int launch_site_lnl(epa_ctx* ctx, const EntryStage& e, const uint32_t* d_order, uint64_t n_rows, uint32_t pitch,
+                    double* d_rows, unsigned flags) {
   ScArgs a;
-  fill_args(ctx, a, d_pairs, d_pendant, d_distal, d_proximal, n_rows, d_codes, d_begin, d_span);
+  fill_args(ctx, a, e, n_rows);
   a.order = d_order;
   a.rows = d_rows;
   a.pitch = pitch;
-  a.pad = pad ? 1u : 0u;
+  a.pad = flags & SITES_PAD ? 1u : 0u;
+  const bool timed = flags & SITES_TIMED;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(n_rows, (uint64_t)ctx->n_cu * 8);
   if (timed) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_SITES));
   if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
