@@ -122,6 +122,7 @@ def dev_lib():
         L.epa_dev_rell_tests.argtypes = L.epa_dev_rell_support.argtypes + [C.c_void_p, C.c_void_p]
         L.epa_dev_rell_au.argtypes = L.epa_dev_rell_support.argtypes[:-1] + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                                              C.c_void_p]
+        L.epa_dev_rell_kh.argtypes = L.epa_dev_rell_tests.argtypes
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -585,6 +586,22 @@ class Evaluator:
                                            _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
                                            int(replicates), int(seed), _ptr(scales), 0 if scales is None else S,
                                            _ptr(out.get("p_au")), _ptr(out.get("counts")), _ptr(out.get("fit"))))
+        return out
+
+    def rell_kh(self, pairs, pendant, distal, codes, win_begin, win_span, replicates, seed=1, stream_id=None,
+                proximal=None, want=("p_kh", "p_wkh", "p_wsh"), Q=None):
+        """p-values of the KH, the weighted KH and the weighted SH test from the replicates of rell_support()
+        (epa_dev_rell_kh) -> dict of float64 [n] arrays, one per name in `want`.  "p_kh": the entry against the best
+        entry of its query; "p_wkh": against the opponent that is furthest ahead in standard deviations of the
+        difference; "p_wsh": the largest standardised difference against its resampled distribution.  At most 1024
+        entries per query (include/epa_dev.h has the exact definitions)."""
+        out = self._want("rell_kh", want, {w: ((len(pairs),), np.float64) for w in ("p_kh", "p_wkh", "p_wsh")})
+        n, Q, pendant, distal, proximal, stream_id = self._entries(pairs, pendant, distal, proximal, codes, win_begin, Q,
+                                                                   stream_id)
+        self._check(self.L.epa_dev_rell_kh(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                           _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(stream_id),
+                                           int(replicates), int(seed), _ptr(out.get("p_kh")), _ptr(out.get("p_wkh")),
+                                           _ptr(out.get("p_wsh"))))
         return out
 
     def set_heuristic(self, mode="dynamic", param=0.0):

@@ -1714,11 +1714,12 @@ extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_
   return EPA_OK;
 }
 
-// ---- the post-placement entry points: epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au
+// ---- the post-placement entry points: epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au,
+// _rell_kh
 
 namespace {
 
-// the arguments all six take (epa_dev_marginal_like: no lengths)
+// the arguments all seven take (epa_dev_marginal_like: no lengths)
 struct EntryArgs {
   const epa_pair* pairs;
   const double *pendant, *distal, *proximal;
@@ -1728,7 +1729,7 @@ struct EntryArgs {
   uint32_t Q;
 };
 
-// One call of the six: begin(), output() for every output, run()
+// One call of the seven: begin(), output() for every output, run()
 struct EntryCall {
   epa_ctx* ctx;
   const char* who;   // the entry point in error texts
@@ -1957,6 +1958,22 @@ extern "C" int epa_dev_rell_au(epa_ctx* ctx, const epa_pair* pairs, const double
   return c.run([&] {
     return launch_rell_au(ctx, c.st, RellDraws{c.d_sid, replicates, seed}, scale_pm, n_scales, c.dev<double>(0), c.dev<uint32_t>(2),
                           c.dev<double>(1));
+  });
+}
+
+extern "C" int epa_dev_rell_kh(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                               const double* proximal, uint64_t n, const uint8_t* q_codes, const uint32_t* win_begin,
+                               const uint32_t* win_span, uint32_t Q, const uint64_t* stream_id, uint32_t replicates,
+                               uint64_t seed, double* p_kh, double* p_wkh, double* p_wsh) {
+  EntryCall c{ctx, "rell_kh", {pairs, pendant, distal, proximal, n, q_codes, win_begin, win_span, Q}};
+  int rc = c.begin({pendant, distal}, &stream_id, [&] {
+    if (!p_kh && !p_wkh && !p_wsh) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_kh: p_kh, p_wkh and p_wsh are all null");
+    return c.check_replicates(replicates);
+  });
+  if (rc || c.empty) return rc;
+  for (double* p : {p_kh, p_wkh, p_wsh}) c.output(p, sizeof(double) * n);
+  return c.run([&] {
+    return launch_rell_kh(ctx, c.st, RellDraws{c.d_sid, replicates, seed}, c.dev<double>(0), c.dev<double>(1), c.dev<double>(2));
   });
 }
 
@@ -2947,6 +2964,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "marginal")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_MARGINAL]][epa_ctx::T_MARGINAL];
   else if (!strcmp(which, "rell_tests")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_TESTS]][epa_ctx::T_RELL_TESTS];
   else if (!strcmp(which, "rell_au")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_AU]][epa_ctx::T_RELL_AU];
+  else if (!strcmp(which, "rell_kh")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_KH]][epa_ctx::T_RELL_KH];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

@@ -218,7 +218,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 20;   // the post-placement calls name theirs: EpaSlot below
+  static constexpr int N_SCRATCH = 21;   // the post-placement calls name theirs: EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -248,7 +248,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, N_TIMERS = 9 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, N_TIMERS = 10 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -315,9 +315,9 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
   } while (0)
 
 // ---- scratch slots of the post-placement entry points (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support,
-// _rell_tests, _rell_au: epa_dev.hip) and of their launchers (score_at.hip, marginal.hip, rell.hip).  The placement
+// _rell_tests, _rell_au, _rell_kh: epa_dev.hip) and of their launchers (score_at.hip, marginal.hip, rell.hip).  The placement
 // path writes its slots as numbers: 0 .. 4 mean the same there, 5 .. 12 are its own (7 .. 9 too, within its own calls).
-// Among these six, 7 and 9 have two meanings.  A call with per-entry lengths stages them in 7 .. 9 (EntryCall::stage); marginal_like has no
+// Among these seven, 7 and 9 have two meanings.  A call with per-entry lengths stages them in 7 .. 9 (EntryCall::stage); marginal_like has no
 // lengths -- it hands the staging null for all three, so nothing of its own call sits there -- and keeps its rule and
 // its waves' grid values in 7 and 9 instead.  Every call stages what it reads before it launches, so what the other
 // meaning left behind in an earlier call is never read.
@@ -339,6 +339,7 @@ enum EpaSlot : int {
   SLOT_RELL_STREAMS = 17, // stream_id [Q]
   SLOT_RELL_TESTS = 18,   // rell_tests: [L n | T n | weight sums n | SH counts n]
   SLOT_RELL_AU = 19,      // rell_au: win counters [scale][n]
+  SLOT_RELL_KH = 20,      // rell_kh: [L n | L_b - L n | L_k* - L n | T n | k* n | counters 3 n | matrix offsets | b | scale matrices | spilled scores]
 };
 
 // The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,
@@ -438,6 +439,9 @@ int launch_rell_tests(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, do
 // [n_scales][n], d_fit [n][2], each or null
 int launch_rell_au(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, const uint32_t* h_scale_pm, uint32_t n_scales,
                    double* d_p_au, uint32_t* d_counts, double* d_fit);
+// p-values of the KH, the weighted KH and the weighted SH test from the replicates of launch_rell; each output [n] or null.
+// At most 1024 entries per query.  Not exported: the call adds one symbol to the library, its entry point
+__attribute__((visibility("hidden"))) int launch_rell_kh(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_p_kh, double* d_p_wkh, double* d_p_wsh);
 // marginal likelihood of the entries' pairs over a (distal x pendant) tensor rule (marginal.hip); d_rule: x_frac [Kx] |
 // x_logw [Kx] | p_len [Kp] | p_logw [Kp]; d_grid: [n][Kx][Kp] or null
 int launch_marginal(epa_ctx* ctx, const EntryStage& e, const double* d_rule, uint32_t Kx, uint32_t Kp, double* d_marginal,

@@ -76,6 +76,7 @@ struct Options {  // defaults: src/util/Options.hpp:13-34
   unsigned long long rell_seed = 1;  // --rell-seed
   bool rell_tests = false;           // --rell-tests (with --rescore --rell N): elw and p_sh from the same replicates
   bool au = false;                   // --au (with --rescore --rell N): p_au from multiscale replicates, N per scale
+  bool kh = false;                   // --kh (with --rescore --rell N): p_kh, p_wkh and p_wsh from the same replicates
   bool posterior = false;            // --posterior (with --rescore): marginal_like and post_prob of every row
   double prior_mean = 0.0;           // --prior-mean: mean of the pendant length's exponential prior; 0: the tree's mean branch length
   unsigned int posterior_kx = 8, posterior_kp = 16;   // --posterior-nodes KX,KP: Gauss-Legendre x Gauss-Laguerre nodes
@@ -142,6 +143,12 @@ public:
   void p_sh(double v) { p_sh_ = v; }
   double p_au() const { return p_au_; }   // --rescore --rell --au only
   void p_au(double v) { p_au_ = v; }
+  double p_kh() const { return p_kh_; }   // --rescore --rell --kh only
+  void p_kh(double v) { p_kh_ = v; }
+  double p_wkh() const { return p_wkh_; }
+  void p_wkh(double v) { p_wkh_ = v; }
+  double p_wsh() const { return p_wsh_; }
+  void p_wsh(double v) { p_wsh_ = v; }
   double marginal_like() const { return marginal_like_; }   // --rescore --posterior only
   void marginal_like(double v) { marginal_like_ = v; }
   double post_prob() const { return post_prob_; }
@@ -149,7 +156,7 @@ public:
 private:
   size_t branch_id_ = 0;
   double likelihood_ = 0, lwr_ = 0, pendant_length_ = 0, distal_length_ = 0, rell_support_ = 0;
-  double marginal_like_ = 0, post_prob_ = 0, elw_ = 0, p_sh_ = 0, p_au_ = 0;
+  double marginal_like_ = 0, post_prob_ = 0, elw_ = 0, p_sh_ = 0, p_au_ = 0, p_kh_ = 0, p_wkh_ = 0, p_wsh_ = 0;
 };
 
 class PQuery {  // src/sample/PQuery.hpp:12-92
@@ -386,9 +393,10 @@ private:
 // v in fixed notation with `precision` digits, correctly rounded (= printf %.*f); returns the length written to buf
 size_t format_fixed(char* buf, size_t cap, double v, unsigned int precision);
 // optional row fields behind pendant_length, written in this order and named in "fields": kJplaceRell
-// "rell_support" (Placement::rell_support), kJplaceRellTests "elw", "p_sh", kJplaceAu "p_au", kJplacePosterior
+// "rell_support" (Placement::rell_support), kJplaceRellTests "elw", "p_sh", kJplaceAu "p_au", kJplaceKh "p_kh", "p_wkh",
+// "p_wsh", kJplacePosterior
 // "marginal_like", "post_prob".  0: the five standard fields
-enum Jplace_Fields : unsigned int { kJplaceRell = 1u, kJplacePosterior = 2u, kJplaceRellTests = 4u, kJplaceAu = 8u };
+enum Jplace_Fields : unsigned int { kJplaceRell = 1u, kJplacePosterior = 2u, kJplaceRellTests = 4u, kJplaceAu = 8u, kJplaceKh = 16u };
 void write_jplace(std::ostream& os, const std::vector<Sample>& chunks, const std::string& newick,
                   const std::string& invocation, unsigned int precision,
                   const Rtree_Mapper* mapper = nullptr, unsigned int extra = 0);

@@ -45,10 +45,15 @@ static void usage() {
       "                        N replicates at each of ten replicate lengths (0.5 .. 1.4 of the sites).  Unlike p_sh it does\n"
       "                        not grow more conservative with the number of rows.  AU wants N of the order of 10000 per\n"
       "                        scale (CONSEL's default)\n"
+      "  --kh                  with --rescore --rell N: three more fields from the same N replicates, directly after \"p_au\" (or\n"
+      "                        whatever precedes its place): \"p_kh\", the p-value of the Kishino-Hasegawa test of the row against\n"
+      "                        the best row of its placement object; \"p_wkh\", the same against the row that is furthest ahead in\n"
+      "                        standard deviations of the difference; \"p_wsh\", the weighted Shimodaira-Hasegawa test, which unlike\n"
+      "                        p_sh does not let a row far off set the scale for the others.  At most 1024 rows per object\n"
       "  --posterior           with --rescore: marginal likelihood of every row's edge, integrated over the attachment point\n"
       "                        (uniform on the edge) and the pendant length (exponential prior), and its normalisation over\n"
       "                        the rows of the placement object; written as the fields \"marginal_like\" and \"post_prob\"\n"
-      "                        (after \"rell_support\", \"elw\", \"p_sh\", \"p_au\" when --rell, --rell-tests, --au are given).  Only edge_num of a row enters them\n"
+      "                        (after \"rell_support\", \"elw\", \"p_sh\", \"p_au\", \"p_kh\" .. when --rell, --rell-tests, --au, --kh are given).  Only edge_num of a row enters them\n"
       "  --prior-mean M        mean of the pendant prior (default: the mean branch length of the reference tree)\n"
       "  --posterior-nodes KX,KP  Gauss-Legendre nodes along the edge x Gauss-Laguerre pendant nodes, 1 .. 64 each (default 8,16)\n"
       "  --precision N         output digits (default 10)\n"
@@ -125,6 +130,7 @@ int main(int argc, char** argv) {
     else if (a == "--rell-seed") { opt.rell_seed = std::stoull(need(i)); rell_given = true; }
     else if (a == "--rell-tests") opt.rell_tests = true;
     else if (a == "--au") opt.au = true;
+    else if (a == "--kh") opt.kh = true;
     else if (a == "--posterior") opt.posterior = true;
     else if (a == "--prior-mean") {
       const std::string v = need(i);
@@ -206,6 +212,11 @@ int main(int argc, char** argv) {
   if (opt.au && (rescore_file.empty() || opt.rell_replicates == 0)) {
     std::cerr << "--au adds p_au from multiscale replicates, N of --rell per scale, to an existing result: place first, then "
                  "--rescore out.jplace --rell N --au\n";
+    return 1;
+  }
+  if (opt.kh && (rescore_file.empty() || opt.rell_replicates == 0)) {
+    std::cerr << "--kh adds p_kh, p_wkh and p_wsh from the replicates of --rell to an existing result: place first, then "
+                 "--rescore out.jplace --rell N --kh\n";
     return 1;
   }
   if (rell_given && rescore_file.empty()) {

@@ -5,7 +5,8 @@
 // get their RELL bootstrap support (epa_dev_rell_support) among the rows of their placement object; the object's index
 // in the input file is its random stream, so the result does not depend on --chunk-size.  --rell-tests makes that one
 // call epa_dev_rell_tests: expected likelihood weight and SH p-value from the same replicates; --au adds the AU test's
-// p-value from multiscale replicates of the same streams (epa_dev_rell_au, the default scales).  With --posterior the rows get
+// p-value from multiscale replicates of the same streams (epa_dev_rell_au, the default scales); --kh adds the p-values of
+// the KH, weighted KH and weighted SH tests from the replicates of --rell (epa_dev_rell_kh).  With --posterior the rows get
 // their marginal likelihood (epa_dev_marginal_like: only edge_num comes from the row; Gauss-Legendre x Gauss-Laguerre
 // rule, exponential pendant prior) and post_prob, its normalisation over the rows of the placement object.
 #include <chrono>
@@ -147,7 +148,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
                enc.win_begin.data(), enc.win_span.data(), (uint32_t)named.size(), rest...));
     };
     rows(epa_dev_score_at, lnl.data());
-    std::vector<double> support, elw, p_sh, p_au;
+    std::vector<double> support, elw, p_sh, p_au, p_kh, p_wkh, p_wsh;
     if (options.rell_replicates) {
       const std::vector<uint64_t> stream_id(target.begin(), target.end());
       const uint32_t R = options.rell_replicates;
@@ -159,6 +160,10 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
       if (options.au) {
         p_au.resize(pairs.size());
         rows(epa_dev_rell_au, stream_id.data(), R, seed, nullptr, 0, p_au.data(), nullptr, nullptr);
+      }
+      if (options.kh) {
+        p_kh.resize(pairs.size()); p_wkh.resize(pairs.size()); p_wsh.resize(pairs.size());
+        rows(epa_dev_rell_kh, stream_id.data(), R, seed, p_kh.data(), p_wkh.data(), p_wsh.data());
       }
     }
     std::vector<double> marginal;
@@ -177,6 +182,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
         if (!support.empty()) pq[pq.size() - 1].rell_support(support[k]);
         if (!elw.empty()) { pq[pq.size() - 1].elw(elw[k]); pq[pq.size() - 1].p_sh(p_sh[k]); }
         if (!p_au.empty()) pq[pq.size() - 1].p_au(p_au[k]);
+        if (!p_kh.empty()) { pq[pq.size() - 1].p_kh(p_kh[k]); pq[pq.size() - 1].p_wkh(p_wkh[k]); pq[pq.size() - 1].p_wsh(p_wsh[k]); }
         if (!marginal.empty()) pq[pq.size() - 1].marginal_like(marginal[k]);
         ++k;
       }
@@ -210,7 +216,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
   if (!os) throw std::runtime_error{"cannot open " + out_path};
   write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision, nullptr,
                (options.rell_replicates ? kJplaceRell : 0u) | (options.rell_tests ? kJplaceRellTests : 0u) |
-                   (options.au ? kJplaceAu : 0u) |
+                   (options.au ? kJplaceAu : 0u) | (options.kh ? kJplaceKh : 0u) |
                    (options.posterior ? kJplacePosterior : 0u));
   os.flush();
   if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }

@@ -39,6 +39,13 @@
 // MS_WINS_LDS (the 4 KiB k_rell spends on its counters: the same three workgroups per CU), else global integer atomics.
 // k_rell_au_fit: one thread per entry fits the signed distance d and the curvature c to its ten proportions and writes
 // p_au = normcdf(c - d), or the plain proportion where fewer than three scales are usable.
+//
+// k_rell_pair_scale / k_rell_kh_thresholds / k_rell_kh (epa_dev_rell_kh): the KH, the weighted KH and the weighted SH
+// test from the replicates of k_rell.  The first statistics here that need every PAIR of a query's entries: the scale
+// w_kk' = 1 / sd(s_k' - s_k) comes from the two site rows (one thread per pair, sequential sums), the opponents and
+// thresholds from w and the observed sums, once per entry; k_rell_kh then holds a replicate's centred scores of ALL
+// entries -- in registers up to eight entries, beyond that in a scratch column of its own -- and compares every entry
+// with every other.  Integer atomics only.  A batch is worked off in ranges of queries whose [K][K] matrices fit 64 MiB.
 #include "epa_dev_internal.hpp"
 #include "wave_util.hpp"
 
@@ -61,6 +68,12 @@ constexpr uint32_t MS_SCALES = 16;       // k_rell_ms: the most scales of a call
 constexpr uint32_t MS_WINS_LDS = 1024;   // k_rell_ms: scales x entries per query counted in LDS: 48 + 4 KiB as k_rell, three workgroups per CU
 constexpr int RES_TILES = 2;             // k_rell_tests: tiles of a query whose scores stay in registers between the sweeps
 constexpr uint32_t ACC_LDS = 256;       // k_rell_tests: entries per query whose three accumulators live in LDS
+constexpr int KH_RES = 2 * TE;           // k_rell_kh: entries of a query whose centred scores stay in registers, w in LDS
+constexpr uint32_t KH_MAX_ENTRIES = 1024;   // epa_dev_rell_kh: entries per query; the [K][K] scales of one query: 8 MiB
+constexpr uint32_t KH_CNT_LDS = 256;     // k_rell_kh: entries per query whose three counters live in LDS
+constexpr uint32_t KH_NONE = 0xffffffffu;   // no opponent: every pair of the entry is skipped
+constexpr size_t KH_W_BUDGET = (size_t)64 << 20;       // bytes of scale matrices per launch (a range of whole queries)
+constexpr size_t KH_SPILL_BUDGET = (size_t)256 << 20;  // bytes of spilled scores of all workgroups of a launch
 constexpr size_t ROWS_BUDGET = (size_t)128 << 20;   // bytes of site rows per batch
 
 struct RellGroup {
@@ -97,6 +110,21 @@ struct RellMsArgs {
   RellArgs r;                 // r.wins: [scale][n] by sorted position
   RellMsScales sc;
   uint32_t n;                 // entries of the call: the pitch of the counters
+};
+
+struct RellKhArgs {
+  RellArgs r;                 // r.groups: the queries of this launch (a range of a batch); r.wins is not used
+  uint32_t lo, hi;            // the launch serves the queries of lo .. hi entries
+  const double* L;            // [n] by sorted position: observed lnL (k_rell_observed)
+  double* W;                  // the scale matrices of the launch's queries, [K][K] each (k_rell_pair_scale); < 0: skipped
+  const uint64_t* woff;       // [queries of the launch]: where the query's matrix begins in W
+  uint32_t* best;             // [queries of the launch]: b, the entry with the largest L (k_rell_kh_thresholds)
+  uint32_t* opp;              // [n]: k*, the entry's opponent in the weighted KH test, or KH_NONE
+  double *D, *Dw, *Tw;        // [n]: L_b - L_k; L_k* - L_k; T_k
+  uint32_t* cnt;              // [3][n]: replicates counted by KH, weighted KH, weighted SH
+  uint32_t n;                 // entries of the call: the pitch of the counters
+  double* spill;              // [workgroups][spill_pitch]: the centred scores of a query beyond KH_RES, [entry][thread]
+  uint32_t spill_pitch;
 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
@@ -526,6 +554,265 @@ __global__ void __launch_bounds__(256) k_rell_tests_out(const uint32_t* __restri
   if (p_sh) p_sh[e] = (double)sh[i] / R;
 }
 
+// ---- epa_dev_rell_kh: the KH, the weighted KH and the weighted SH test (include/epa_dev.h)
+
+// The scale w_kk' = 1 / sd(s_k' - s_k) of every ordered pair of entries of the launch's queries of lo .. hi entries: one
+// thread per pair, the two sums over the sites sequential in site order.  blockIdx.y splits the pairs of a large query
+// over several workgroups.  A skipped pair (the diagonal, q == 0, w not finite) is stored as -1.0
+__global__ void __launch_bounds__(64) k_rell_pair_scale(const RellKhArgs ka) {
+#pragma clang fp contract(off)   // q adds the ROUNDED product: every step is one fp64 operation
+  const RellArgs& a = ka.r;
+  for (uint32_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+    const RellGroup grp = a.groups[g];
+    const uint32_t E = grp.count;
+    if (E < ka.lo || E > ka.hi) continue;
+    const uint32_t nq = a.span[grp.q];
+    const double nqd = (double)nq;
+    const double* __restrict__ rows = a.rows + (size_t)(grp.start - a.pos0) * a.pitch;
+    double* __restrict__ W = ka.W + ka.woff[g];
+    for (uint32_t i = blockIdx.y * 64 + threadIdx.x; i < E * E; i += gridDim.y * 64) {   // E <= 1024: E * E fits
+      const uint32_t k = i / E, kp = i - k * E;
+      double w = -1.0;
+      if (k != kp) {
+        const double* __restrict__ xk = rows + (size_t)k * a.pitch;
+        const double* __restrict__ xp = rows + (size_t)kp * a.pitch;
+        double sum = 0.0;
+        for (uint32_t j = 0; j < nq; ++j) sum += xp[j] - xk[j];
+        const double m = sum / nqd;
+        double q = 0.0;
+        for (uint32_t j = 0; j < nq; ++j) {
+          const double dev = (xp[j] - xk[j]) - m;
+          const double sq = dev * dev;
+          q += sq;
+        }
+        const double inv = 1.0 / sqrt(q);
+        if (q != 0.0 && isfinite(inv)) w = inv;   // span 0 (m is NaN, q stays 0.0), span 1 and equal rows: q == 0
+      }
+      W[i] = w;
+    }
+  }
+}
+
+// Per query: b, the entry with the largest L; per entry k: L_b - L_k, the opponent k* = argmax (L_k' - L_k) w_kk' over the
+// pairs not skipped with L_k* - L_k, and T_k, that maximum.  Ties as the winner's: the smaller branch id, then the
+// smaller entry index.  b and its copies get no opponent: the weighted tests give them 1.0 as KH does.  One 64-thread workgroup per query, the entries dealt to its threads
+__global__ void __launch_bounds__(64) k_rell_kh_thresholds(const RellKhArgs ka) {
+#pragma clang fp contract(off)
+  const RellArgs& a = ka.r;
+  for (uint32_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+    const RellGroup grp = a.groups[g];
+    const uint32_t E = grp.count;
+    const double* __restrict__ L = ka.L + grp.start;
+    const uint32_t* __restrict__ ord = a.order + grp.start;
+    const double* __restrict__ W = ka.W + ka.woff[g];
+    uint32_t b = 0, b_br = a.pairs[ord[0]].branch_id;
+    double Lb = L[0];
+    for (uint32_t k = 1; k < E; ++k) {
+      const double Lk = L[k];
+      const uint32_t br = a.pairs[ord[k]].branch_id;
+      if (Lk > Lb || (Lk == Lb && br < b_br)) { b = k; b_br = br; Lb = Lk; }
+    }
+    if (threadIdx.x == 0) ka.best[g] = b;
+    for (uint32_t k = threadIdx.x; k < E; k += 64) {
+      const double Lk = L[k];
+      uint32_t ks = KH_NONE, ks_br = 0;
+      double T = 0.0;
+      // the best entry, and a copy of it (its pair with b skipped, the same L), is never rejected: no opponent
+      const bool top = k == b || (Lb - Lk == 0.0 && !(W[(size_t)b * E + k] >= 0.0));
+      for (uint32_t kp = 0; kp < E && !top; ++kp) {
+        const double w = W[(size_t)k * E + kp];
+        if (!(w >= 0.0)) continue;
+        const double val = (L[kp] - Lk) * w;
+        const uint32_t br = a.pairs[ord[kp]].branch_id;
+        if (ks == KH_NONE || val > T || (val == T && br < ks_br)) { ks = kp; ks_br = br; T = val; }
+      }
+      const uint32_t pos = grp.start + k;
+      ka.D[pos] = Lb - Lk;
+      ka.opp[pos] = ks;
+      ka.Dw[pos] = ks != KH_NONE ? L[ks] - Lk : 0.0;
+      ka.Tw[pos] = T;
+    }
+  }
+}
+
+// the replicates of one wave in which entry `k` of the query is counted by the three tests, added to its counters
+__device__ __forceinline__ void rell_kh_count(bool kh, bool wkh, bool wsh, uint32_t lane, uint32_t* c0, uint32_t* c1, uint32_t* c2) {
+  const uint32_t n0 = (uint32_t)__popcll(__ballot(kh)), n1 = (uint32_t)__popcll(__ballot(wkh)), n2 = (uint32_t)__popcll(__ballot(wsh));
+  if (lane == 0) {
+    if (n0) atomicAdd(c0, n0);
+    if (n1) atomicAdd(c1, n1);
+    if (n2) atomicAdd(c2, n2);
+  }
+}
+
+// The three counts of epa_dev_rell_kh: the shape of k_rell_tests -- one workgroup per query, thread = replicate, tiles of
+// TE entries staged in LDS, the draws regenerated per tile -- and then every entry's centred score against all others.
+// SPILL false serves the queries of up to KH_RES entries: the centred scores stay in registers, w and the thresholds in
+// LDS.  SPILL true serves the larger ones: a thread writes its centred scores to its own column of the workgroup's row
+// of ka.spill ([entry][thread]: a wave's 64 columns are 512 contiguous bytes) and sweeps them in blocks of KH_RES entries
+// k against all k', w read from L2 at wave-uniform addresses (w[k'][k .. k + 8): contiguous, w is symmetric).  Integer
+// atomics only, in LDS for up to KH_CNT_LDS entries
+template <bool SPILL>
+__global__ void __launch_bounds__(RELL_THREADS) k_rell_kh(const RellKhArgs ka) {
+#pragma clang fp contract(off)
+  constexpr uint32_t NC = SPILL ? KH_CNT_LDS : (uint32_t)KH_RES;
+  __shared__ __attribute__((aligned(16))) double mat[LDS_SITES * TE];   // [site][TE]
+  __shared__ uint32_t cnt_l[3][NC];
+  __shared__ double w_l[KH_RES * KH_RES], L_l[KH_RES], D_l[KH_RES], Dw_l[KH_RES], Tw_l[KH_RES];   // SPILL false only
+  __shared__ uint32_t opp_l[KH_RES];
+  const RellArgs& a = ka.r;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  for (uint32_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+    const RellGroup grp = a.groups[g];
+    const uint32_t E = grp.count;
+    if (E < ka.lo || E > ka.hi) continue;   // workgroup-uniform, as everything below that guards a barrier
+    uint32_t* __restrict__ cnt0 = ka.cnt + grp.start;
+    uint32_t* __restrict__ cnt1 = ka.cnt + (size_t)ka.n + grp.start;
+    uint32_t* __restrict__ cnt2 = ka.cnt + 2 * (size_t)ka.n + grp.start;
+    if (E == 1) {   // nothing to compare with: 1, 1, 1
+      if (tid == 0) { cnt0[0] = a.R; cnt1[0] = a.R; cnt2[0] = a.R; }
+      continue;
+    }
+    const uint32_t nq = a.span[grp.q];
+    const uint64_t t = a.stream_id ? a.stream_id[grp.q] : (uint64_t)grp.q;
+    const uint32_t tlo = (uint32_t)t, thi = (uint32_t)(t >> 32);
+    const double* __restrict__ rows = a.rows + (size_t)(grp.start - a.pos0) * a.pitch;
+    const double* __restrict__ L = ka.L + grp.start;
+    const double* __restrict__ D = ka.D + grp.start;
+    const double* __restrict__ Dw = ka.Dw + grp.start;
+    const double* __restrict__ Tw = ka.Tw + grp.start;
+    const uint32_t* __restrict__ opp = ka.opp + grp.start;
+    const double* __restrict__ W = ka.W + ka.woff[g];
+    const uint32_t b = ka.best[g];
+    const bool in_lds = nq <= LDS_SITES, cnt_lds = E <= NC;
+    const uint32_t ntiles = (E + TE - 1) / TE;
+    double* __restrict__ col = SPILL ? ka.spill + (size_t)blockIdx.x * ka.spill_pitch + tid : nullptr;   // col[k * 256]
+    __syncthreads();   // the previous query's tile, tables and counters are no longer read
+    if (cnt_lds)
+      for (uint32_t i = tid; i < E; i += RELL_THREADS) { cnt_l[0][i] = 0; cnt_l[1][i] = 0; cnt_l[2][i] = 0; }
+    if (!SPILL) {
+      if (tid < (uint32_t)KH_RES) {
+        const bool on = tid < E;
+        L_l[tid] = on ? L[tid] : 0.0;
+        D_l[tid] = on ? D[tid] : 0.0;
+        Dw_l[tid] = on ? Dw[tid] : 0.0;
+        Tw_l[tid] = on ? Tw[tid] : 0.0;
+        opp_l[tid] = on ? opp[tid] : KH_NONE;
+      }
+      if (tid < (uint32_t)(KH_RES * KH_RES)) {
+        const uint32_t k = tid / KH_RES, kp = tid % KH_RES;
+        w_l[tid] = k < E && kp < E ? W[k * E + kp] : -1.0;
+      }
+    }
+    __syncthreads();
+    for (uint32_t rbase = 0; rbase < a.R; rbase += RELL_THREADS) {
+      const uint32_t r = rbase + tid;
+      const bool active = r < a.R;
+      double c[KH_RES] = {};   // SPILL false: indexed by unrolled loops only: registers
+      // ---- the centred scores c_k = s_k - L_k of the replicate
+      for (uint32_t tile = 0; tile < ntiles; ++tile) {
+        const uint32_t e0 = tile * TE, te = min((uint32_t)TE, E - e0);
+        if (in_lds && (ntiles > 1 || rbase == 0)) {   // as k_rell: a query of one tile keeps it for all rounds
+          __syncthreads();
+          rell_stage_tile(mat, rows, a.pitch, e0, te, nq, tid);
+          __syncthreads();
+        }
+        if (!active) continue;
+        double sc[TE];
+        rell_tile_scores(mat, rows, a.pitch, e0, te, nq, nq, in_lds, r, tlo, thi, a.k0, a.k1, sc);
+        if (SPILL) {
+#pragma unroll
+          for (int k = 0; k < TE; ++k)
+            if ((uint32_t)k < te) col[(size_t)(e0 + k) * RELL_THREADS] = sc[k] - L[e0 + k];
+        } else {
+#pragma unroll
+          for (int u = 0; u < KH_RES / TE; ++u)
+            if (tile == (uint32_t)u) {
+#pragma unroll
+              for (int k = 0; k < TE; ++k) c[u * TE + k] = sc[k] - L_l[u * TE + k];
+            }
+        }
+      }
+      // ---- every entry against the others; every lane of every wave takes part in the ballots
+      if (!SPILL) {
+#pragma unroll
+        for (int k = 0; k < KH_RES; ++k) {
+          if ((uint32_t)k < E) {
+            const uint32_t ks = opp_l[k];
+            double tk = -INFINITY, d_kh = 0.0, d_wkh = 0.0;
+#pragma unroll
+            for (int kp = 0; kp < KH_RES; ++kp) {
+              if ((uint32_t)kp < E) {
+                const double diff = c[kp] - c[k];
+                const double w = w_l[k * KH_RES + kp];
+                if (w >= 0.0) {
+                  const double v = diff * w;
+                  tk = v > tk ? v : tk;
+                }
+                if ((uint32_t)kp == b) d_kh = diff;
+                if ((uint32_t)kp == ks) d_wkh = diff;
+              }
+            }
+            const bool none = ks == KH_NONE;
+            rell_kh_count(active && d_kh >= D_l[k], active && (none || d_wkh >= Dw_l[k]), active && (none || tk >= Tw_l[k]), lane,
+                          &cnt_l[0][k], &cnt_l[1][k], &cnt_l[2][k]);
+          }
+        }
+      } else {
+        const double cb = active ? col[(size_t)b * RELL_THREADS] : 0.0;
+        for (uint32_t k0 = 0; k0 < E; k0 += KH_RES) {
+          const uint32_t nk = min((uint32_t)KH_RES, E - k0);
+          double tk[KH_RES];
+#pragma unroll
+          for (int u = 0; u < KH_RES; ++u) {
+            c[u] = active && (uint32_t)u < nk ? col[(size_t)(k0 + u) * RELL_THREADS] : 0.0;
+            tk[u] = -INFINITY;
+          }
+          if (active)
+            for (uint32_t kp = 0; kp < E; ++kp) {
+              const double cp = col[(size_t)kp * RELL_THREADS];
+              const double* __restrict__ wr = W + (size_t)kp * E + k0;   // w[kp][k0 + u] = w[k0 + u][kp]
+#pragma unroll
+              for (int u = 0; u < KH_RES; ++u) {
+                if ((uint32_t)u < nk) {
+                  const double w = wr[u];
+                  if (w >= 0.0) {
+                    const double v = (cp - c[u]) * w;
+                    tk[u] = v > tk[u] ? v : tk[u];
+                  }
+                }
+              }
+            }
+#pragma unroll
+          for (int u = 0; u < KH_RES; ++u) {
+            if ((uint32_t)u < nk) {
+              const uint32_t k = k0 + u, ks = opp[k];
+              const bool none = ks == KH_NONE;
+              const double d_wkh = active && !none ? col[(size_t)ks * RELL_THREADS] - c[u] : 0.0;
+              rell_kh_count(active && cb - c[u] >= D[k], active && (none || d_wkh >= Dw[k]), active && (none || tk[u] >= Tw[k]), lane,
+                            cnt_lds ? &cnt_l[0][k] : cnt0 + k, cnt_lds ? &cnt_l[1][k] : cnt1 + k, cnt_lds ? &cnt_l[2][k] : cnt2 + k);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (cnt_lds)
+      for (uint32_t i = tid; i < E; i += RELL_THREADS) { cnt0[i] = cnt_l[0][i]; cnt1[i] = cnt_l[1][i]; cnt2[i] = cnt_l[2][i]; }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_rell_kh_out(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ order,
+                                                     uint32_t n, double R, double* __restrict__ p_kh,
+                                                     double* __restrict__ p_wkh, double* __restrict__ p_wsh) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t e = order[i];
+  if (p_kh) p_kh[e] = (double)cnt[i] / R;
+  if (p_wkh) p_wkh[e] = (double)cnt[(size_t)n + i] / R;
+  if (p_wsh) p_wsh[e] = (double)cnt[2 * (size_t)n + i] / R;
+}
+
 // What the RELL calls share (rell_run): the entries grouped by query, the groups dealt into batches of whole
 // queries, the site rows' scratch, the win counters cleared.  `who` names the entry point in error texts
 struct RellBatch {
@@ -630,8 +917,8 @@ int rell_batch_rows(epa_ctx* ctx, const RellPlan& plan, const RellBatch& b, cons
   return EPA_OK;
 }
 
-// One RELL call, timed as `timer`.  The variant supplies prepare(a) -> status: its own scratch cleared, a.wins redirected if
-// it counts elsewhere; batch(plan, b, a, grid): its kernels on a batch whose site rows are ready, `grid` the workgroups of
+// One RELL call, timed as `timer`.  The variant supplies prepare(plan, a) -> status: its own scratch cleared, a.wins
+// redirected if it counts elsewhere, whatever of the plan it refuses; batch(plan, b, a, grid): its kernels on a batch whose site rows are ready, `grid` the workgroups of
 // the kernel that runs one query each; finish(plan, grid): the kernel that writes the outputs, one thread per entry
 template <class Prepare, class Batch, class Finish>
 int rell_run(epa_ctx* ctx, const char* who, int timer, const EntryStage& e, const RellDraws& dr, Prepare prepare, Batch batch,
@@ -642,7 +929,7 @@ int rell_run(epa_ctx* ctx, const char* who, int timer, const EntryStage& e, cons
   int rc = rell_plan(ctx, who, e.d_pairs, n, e.h_span, e.Q, plan);
   if (rc) return rc;
   RellArgs a = rell_args(plan, e, dr);
-  rc = prepare(a);
+  rc = prepare(plan, a);
   if (rc) return rc;
   for (const RellBatch& b : plan.batches) {
     rc = rell_batch_rows(ctx, plan, b, e, a);
@@ -660,7 +947,7 @@ int rell_run(epa_ctx* ctx, const char* who, int timer, const EntryStage& e, cons
 
 int launch_rell(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support) {
   return rell_run(
-      ctx, "rell_support", epa_ctx::T_RELL, e, dr, [](RellArgs&) -> int { return EPA_OK; },
+      ctx, "rell_support", epa_ctx::T_RELL, e, dr, [](const RellPlan&, RellArgs&) -> int { return EPA_OK; },
       [&](const RellPlan&, const RellBatch&, const RellArgs& a, dim3 grid) {
         hipLaunchKernelGGL(k_rell, grid, dim3(RELL_THREADS), 0, ctx->stream, a);
       },
@@ -676,7 +963,7 @@ int launch_rell_tests(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, do
   RellTestsArgs ta{};
   return rell_run(
       ctx, "rell_tests", epa_ctx::T_RELL_TESTS, e, dr,
-      [&](RellArgs&) -> int {
+      [&](const RellPlan&, RellArgs&) -> int {
         // [L n | T n | weight sums n | SH counts n]; the two accumulators are cleared per call, L and T written in full
         const size_t db = (sizeof(double) * (size_t)n + 255) & ~(size_t)255;
         char* base = (char*)epa_scratch(ctx, SLOT_RELL_TESTS, 3 * db + sizeof(uint32_t) * (size_t)n);
@@ -713,7 +1000,7 @@ int launch_rell_au(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, const
   ma.n = n;
   return rell_run(
       ctx, "rell_au", epa_ctx::T_RELL_AU, e, dr,
-      [&](RellArgs& a) -> int {   // the win counters [scale][n] by sorted position, cleared per call
+      [&](const RellPlan&, RellArgs& a) -> int {   // the win counters [scale][n] by sorted position, cleared per call
         a.wins = d_ms = (uint32_t*)epa_scratch(ctx, SLOT_RELL_AU, cbytes);
         if (!d_ms) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_au counters)");
         EPA_HIP(ctx, hipMemsetAsync(d_ms, 0, cbytes, ctx->stream));
@@ -726,5 +1013,121 @@ int launch_rell_au(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, const
       [&](const RellPlan& plan, dim3 grid) {
         hipLaunchKernelGGL(k_rell_au_fit, grid, dim3(256), 0, ctx->stream, d_ms, plan.d_order, e.d_pairs, e.d_span, ma.sc, n,
                            dr.replicates, d_p_au, d_counts, d_fit);
+      });
+}
+
+int launch_rell_kh(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_p_kh, double* d_p_wkh, double* d_p_wsh) {
+  const uint32_t n = (uint32_t)e.n;
+  // a batch's queries are worked off in ranges whose scale matrices fit KH_W_BUDGET (one query's always do)
+  struct Range {
+    size_t g0, g1;                    // groups [g0, g1)
+    uint32_t small, large, widest;    // queries of up to KH_RES entries, of more, and the most entries among those
+  };
+  std::vector<Range> ranges;
+  std::vector<uint64_t> woff;         // per group: where its matrix begins in the range's W
+  size_t next_range = 0;
+  uint32_t spill_grid = 0;
+  const uint64_t* d_woff = nullptr;
+  uint32_t* d_best = nullptr;
+  RellKhArgs ka{};
+  return rell_run(
+      ctx, "rell_kh", epa_ctx::T_RELL_KH, e, dr,
+      [&](const RellPlan& plan, RellArgs&) -> int {
+        const size_t G = plan.groups.size();
+        woff.resize(G);
+        size_t w_most = 0, large_most = 0;
+        uint32_t widest = 0;
+        for (const RellBatch& b : plan.batches)
+          for (size_t g = b.g0; g < b.g1;) {
+            Range r{g, g, 0, 0, 0};
+            size_t w = 0;
+            while (r.g1 < b.g1) {
+              const uint32_t K = plan.groups[r.g1].count;
+              if (K > KH_MAX_ENTRIES)
+                return epa_fail(ctx, EPA_ERR_INVALID_ARG, "rell_kh: query " + std::to_string(plan.groups[r.g1].q) + " has " +
+                                                              std::to_string(K) + " entries; at most " +
+                                                              std::to_string(KH_MAX_ENTRIES) + " per query in this call");
+              if (r.g1 > g && (w + (size_t)K * K) * sizeof(double) > KH_W_BUDGET) break;
+              woff[r.g1] = w;
+              w += (size_t)K * K;
+              if (K > (uint32_t)KH_RES) { ++r.large; r.widest = std::max(r.widest, K); }
+              else ++r.small;
+              ++r.g1;
+            }
+            w_most = std::max(w_most, w);
+            large_most = std::max(large_most, (size_t)r.large);
+            widest = std::max(widest, r.widest);
+            ranges.push_back(r);
+            g = r.g1;
+          }
+        // the workgroups of the spilling launch: what KH_SPILL_BUDGET holds of rows of `widest` entries x 256 threads
+        const size_t spill_row = sizeof(double) * (size_t)widest * RELL_THREADS;
+        if (widest)
+          spill_grid = (uint32_t)std::min<size_t>(std::min<size_t>(large_most, (size_t)ctx->n_cu * 8),
+                                                  std::max<size_t>(1, KH_SPILL_BUDGET / spill_row));
+        // [L n | D n | Dw n | Tw n | opp n | counters 3 n | woff G | best G | W | spill]; the counters are cleared per call,
+        // everything else is written before it is read
+        auto al = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+        const size_t db = al(sizeof(double) * (size_t)n), ub = al(sizeof(uint32_t) * (size_t)n);
+        const size_t cb = al(3 * sizeof(uint32_t) * (size_t)n), wo = al(sizeof(uint64_t) * G), bb = al(sizeof(uint32_t) * G);
+        const size_t wb = al(sizeof(double) * w_most);
+        char* base = (char*)epa_scratch(ctx, SLOT_RELL_KH, 4 * db + ub + cb + wo + bb + wb + spill_row * spill_grid);
+        if (!base) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell_kh scratch)");
+        ka.L = (double*)base;
+        ka.D = (double*)(base + db);
+        ka.Dw = (double*)(base + 2 * db);
+        ka.Tw = (double*)(base + 3 * db);
+        ka.opp = (uint32_t*)(base + 4 * db);
+        ka.cnt = (uint32_t*)(base + 4 * db + ub);
+        d_woff = (const uint64_t*)(base + 4 * db + ub + cb);
+        d_best = (uint32_t*)(base + 4 * db + ub + cb + wo);
+        ka.W = (double*)(base + 4 * db + ub + cb + wo + bb);
+        ka.spill = (double*)(base + 4 * db + ub + cb + wo + bb + wb);
+        ka.spill_pitch = widest * RELL_THREADS;
+        ka.n = n;
+        EPA_HIP(ctx, hipMemsetAsync(ka.cnt, 0, 3 * sizeof(uint32_t) * (size_t)n, ctx->stream));
+        EPA_HIP(ctx, hipMemcpyAsync((void*)d_woff, woff.data(), sizeof(uint64_t) * G, hipMemcpyHostToDevice, ctx->stream));
+        return EPA_OK;
+      },
+      [&](const RellPlan& plan, const RellBatch& b, const RellArgs& a, dim3) {
+        const uint32_t npos = (uint32_t)b.rows;
+        hipLaunchKernelGGL(k_rell_observed, dim3((npos + 255) / 256), dim3(256), 0, ctx->stream, plan.d_rows, b.pitch, a.pos0,
+                           npos, plan.d_order, e.d_pairs, e.d_span, (double*)ka.L);
+        for (; next_range < ranges.size() && ranges[next_range].g1 <= b.g1; ++next_range) {
+          const Range& r = ranges[next_range];
+          ka.r = a;
+          ka.r.groups = plan.d_groups + r.g0;
+          ka.r.n_groups = (uint32_t)(r.g1 - r.g0);
+          ka.woff = d_woff + r.g0;
+          ka.best = d_best + r.g0;
+          const uint32_t per_query = (uint32_t)std::min<uint64_t>(ka.r.n_groups, (uint64_t)ctx->n_cu * 32);   // one wave each
+          if (r.small) {
+            ka.lo = 1;
+            ka.hi = KH_RES;
+            hipLaunchKernelGGL(k_rell_pair_scale, dim3(per_query), dim3(64), 0, ctx->stream, ka);
+          }
+          if (r.large) {
+            ka.lo = KH_RES + 1;
+            ka.hi = KH_MAX_ENTRIES;
+            const uint32_t slices = std::min<uint32_t>(64, (r.widest * r.widest + 63) / 64);
+            hipLaunchKernelGGL(k_rell_pair_scale, dim3(per_query, slices), dim3(64), 0, ctx->stream, ka);
+          }
+          hipLaunchKernelGGL(k_rell_kh_thresholds, dim3(per_query), dim3(64), 0, ctx->stream, ka);
+          if (r.small) {
+            ka.lo = 1;
+            ka.hi = KH_RES;
+            hipLaunchKernelGGL(k_rell_kh<false>, dim3((uint32_t)std::min<uint64_t>(ka.r.n_groups, (uint64_t)ctx->n_cu * 8)),
+                               dim3(RELL_THREADS), 0, ctx->stream, ka);
+          }
+          if (r.large) {
+            ka.lo = KH_RES + 1;
+            ka.hi = KH_MAX_ENTRIES;
+            hipLaunchKernelGGL(k_rell_kh<true>, dim3(std::min(r.large, spill_grid)), dim3(RELL_THREADS), 0, ctx->stream, ka);
+          }
+        }
+      },
+      [&](const RellPlan& plan, dim3 grid) {
+        hipLaunchKernelGGL(k_rell_kh_out, grid, dim3(256), 0, ctx->stream, ka.cnt, plan.d_order, n, (double)dr.replicates, d_p_kh,
+                           d_p_wkh, d_p_wsh);
       });
 }

@@ -576,6 +576,53 @@ int epa_dev_rell_au(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, 
                     double* fit /* [n][2] = (d, c) or NULL */);
 
 /*
+ * The p-values of the Kishino-Hasegawa (KH) test, the weighted KH test and the weighted SH test (Shimodaira & Hasegawa
+ * 1999, Shimodaira 1998; CONSEL's and IQ-TREE's p-KH, p-WKH, p-WSH) of every entry, from the RELL replicates above.  The
+ * SH p-value of epa_dev_rell_tests grows more conservative with every competing entry; the weighted tests divide every
+ * difference of two entries by its standard deviation under the resampling, so that an entry far off does not set the
+ * scale for the others.  Generator, draws and score are those of epa_dev_rell_support and nothing else; the same (seed,
+ * stream_id, replicates) give the same replicates.  Every step below is ONE fp64 operation, nothing fused or
+ * reassociated: the three counts are a function of the site values alone and a restatement reaches them as integers.
+ * For a query with span n_q, entries k (in the caller's order) with site values x_k[j] (epa_dev_site_lnl), replicate r:
+ *   score      s_k^(r): epa_dev_rell_support's score
+ *   observed   L_k: 0.0 plus x_k[j] for j = 0 .. n_q - 1 in this order, as in epa_dev_rell_tests
+ *   centred    c_k^(r) = s_k^(r) - L_k
+ *   best       b: the entry with the largest L; ties go to the smaller branch_id, then to the smaller entry index
+ *   pair scale for k != k':  d_j = x_k'[j] - x_k[j];  a = 0.0 plus the d_j, j = 0 .. n_q - 1 in this order (sequential, no
+ *              blocking);  m = a / n_q;  q = 0.0 plus (d_j - m) * (d_j - m) in the same order, the product rounded before
+ *              it is added;  v = sqrt(q), the exact standard deviation of the resampled s_k' - s_k;  w_kk' = 1.0 / v.
+ *              The pair is SKIPPED when q == 0 or w is not finite: equal rows, span 0 (m is NaN, q stays 0), span 1.
+ *              w_kk' and w_k'k have the same bits
+ *   p_kh       #{ r : c_b^(r) - c_k^(r) >= L_b - L_k } / replicates.  The best entry gets exactly 1.0
+ *   p_wkh      the opponent k* maximises (L_k' - L_k) * w_kk' over the k' whose pair with k is not skipped; ties go to the
+ *              smaller branch_id, then to the smaller entry index.  p_wkh[k] = #{ r : c_k*^(r) - c_k^(r) >= L_k* - L_k } /
+ *              replicates; with no opponent (every pair skipped, or the best entry: below) it is 1.0
+ *   p_wsh      T_k = max (L_k' - L_k) * w_kk' and t_k^(r) = max (c_k'^(r) - c_k^(r)) * w_kk', both over the k' not skipped;
+ *              p_wsh[k] = #{ r : t_k^(r) >= T_k } / replicates; with no opponent it is 1.0.  p_wkh <= p_wsh, as counts
+ *   best entry all three are exactly 1.0 for b, and for a copy of b: an entry k with L_b - L_k == 0 whose pair with b is
+ *              skipped.  p_kh by its rule; for p_wkh and p_wsh such an entry has NO opponent whatever its other pairs are:
+ *              the tests ask whether an entry is worse than the best, and the best is never rejected.  (CONSEL and
+ *              IQ-TREE test the best entry against the one nearest below it instead and print values below 1 there.)
+ *   one entry, span 0   all three are 1.0
+ *   span 1     every pair is skipped: p_wkh = p_wsh = 1; p_kh by its rule: c = 0 for every entry, so it is 0 for an entry
+ *              strictly worse than the best and 1 for the others
+ *   bound      at most 1024 entries per query in this call; a larger group is EPA_ERR_INVALID_ARG, the text names the query
+ *              and its count.  A condition, not a measurement: it holds one query's [K][K] scales to 8 MiB and the
+ *              quadratic work of a replicate to a bounded launch
+ * Arguments, checks, error texts, the host-or-device pointer rule and query staging are epa_dev_rell_support's (errors
+ * name "rell_kh").  p_kh, p_wkh, p_wsh: [n] each (host or device), any of them NULL to leave it out; all three NULL is
+ * EPA_ERR_INVALID_ARG.  replicates: 1 .. 2^20; n < 2^32; n == 0 returns EPA_OK.  The same call returns the same bits
+ * every time: integer atomics for the counts, no floating-point atomics.
+ * Timer: "rell_kh" (grouping, site rows, observed sums, pair scales and resampling together).
+ */
+int epa_dev_rell_kh(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                    const double* proximal /* may be NULL */, uint64_t n,
+                    const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q,
+                    const uint64_t* stream_id /* [Q] or NULL = seq_id */,
+                    uint32_t replicates, uint64_t seed,
+                    double* p_kh /* [n] or NULL */, double* p_wkh /* [n] or NULL */, double* p_wsh /* [n] or NULL */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -812,7 +859,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
