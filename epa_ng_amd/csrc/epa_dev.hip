@@ -122,10 +122,10 @@ static void launch_unpack4(hipStream_t st, const uint8_t* d_packed, uint8_t* d_c
 
 const uint8_t* epa_codes_to_device(epa_ctx* ctx, const uint8_t* q_codes, uint32_t Q) {
   const size_t stride = ctx->code_stride ? ctx->code_stride : ctx->W;
-  if (!ctx->code_packed4) return (const uint8_t*)epa_to_device(ctx, 0, q_codes, (size_t)Q * stride);
+  if (!ctx->code_packed4) return (const uint8_t*)epa_to_device(ctx, SLOT_CODES, q_codes, (size_t)Q * stride);
   const size_t pstride = (stride + 1) / 2;
-  const uint8_t* d_packed = (const uint8_t*)epa_to_device(ctx, 10, q_codes, (size_t)Q * pstride);
-  uint8_t* d = (uint8_t*)epa_scratch(ctx, 0, (size_t)Q * stride + 1024);
+  const uint8_t* d_packed = (const uint8_t*)epa_to_device(ctx, SLOT_PACKED4, q_codes, (size_t)Q * pstride);
+  uint8_t* d = (uint8_t*)epa_scratch(ctx, SLOT_CODES, (size_t)Q * stride + 1024);
   if (!d_packed || !d) return nullptr;
   launch_unpack4(ctx->stream, d_packed, d, Q, (uint32_t)stride);
   return d;
@@ -1044,7 +1044,7 @@ static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const ep
 
   uint32_t* d_tipmap = nullptr;
   if (d->tipmap && d->tipmap_size) {
-    d_tipmap = (uint32_t*)epa_scratch(ctx, 2, sizeof(uint32_t) * d->tipmap_size);
+    d_tipmap = (uint32_t*)epa_scratch(ctx, SLOT_TIPMAP, sizeof(uint32_t) * d->tipmap_size);
     if (!d_tipmap) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(tipmap)");
     EPA_HIP(ctx, hipMemcpy(d_tipmap, d->tipmap, sizeof(uint32_t) * d->tipmap_size,
                            hipMemcpyHostToDevice));
@@ -1101,7 +1101,7 @@ static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const ep
       if (tip && !clv && !d_tipmap)
         return epa_fail(ctx, EPA_ERR_INVALID_ARG, "dist_tipchars given without tipmap");
       double* dst = ctx->refT + (2 * b + side) * cs * W;
-      const int slot = side;  // staging slots 0/1
+      const int slot = side == 0 ? SLOT_CLV_PROX : SLOT_CLV_DIST;
       if (clv) {
         const double* dclv = (const double*)epa_to_device(ctx, slot, clv, sizeof(double) * W * (size_t)c_in * s);
         if (!dclv) return epa_fail(ctx, EPA_ERR_HIP, "staging copy of CLV failed");
@@ -1114,7 +1114,7 @@ static int create_impl(const epa_ref_desc* d, int device, epa_ctx* ctx, const ep
         if (rc) return rc;
       }
       if (sc) {
-        const uint32_t* dsc = (const uint32_t*)epa_to_device(ctx, 3 + side, sc, sizeof(uint32_t) * W * cdim);
+        const uint32_t* dsc = (const uint32_t*)epa_to_device(ctx, side == 0 ? SLOT_SCALER_PROX : SLOT_SCALER_DIST, sc, sizeof(uint32_t) * W * cdim);
         if (!dsc) return epa_fail(ctx, EPA_ERR_HIP, "staging copy of scaler failed");
         hipLaunchKernelGGL(k_add_scaler, dim3((uint32_t)((W * cdim + 255) / 256)), dim3(256), 0, ctx->stream, dsc,
                            d_sc_side ? d_sc_side + (2 * b + side) * cdim * W : ctx->scSum + b * W, (uint32_t)W,
@@ -1507,7 +1507,7 @@ extern "C" int epa_dev_tree_logl(epa_ctx* ctx, uint32_t branch, double* lnl) {
   if (!ctx || !lnl || branch >= ctx->B) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "bad argument");
   EPA_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t nblk = (ctx->W + 255) / 256;
-  double* d_part = (double*)epa_scratch(ctx, 9, sizeof(double) * nblk);
+  double* d_part = (double*)epa_scratch(ctx, SLOT_TREE_LNL, sizeof(double) * nblk);
   if (!d_part) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(tree lnL partials)");
   const double len = ctx->h_blen[branch];
   if (ctx->s == 4)
@@ -1625,15 +1625,15 @@ extern "C" int epa_dev_preplace_bounded(epa_ctx* ctx, const uint8_t* q_codes, co
   unsigned long long* d_seg = nullptr;
   if (seg_keys) {   // the by-product the fused chunk body's selection reads (chunk_body_begin)
     if (nseg > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "preplace: segment maxima exist up to 4096 branches");
-    d_seg = (unsigned long long*)epa_scratch(ctx, 10, sizeof(unsigned long long) * (size_t)Q * segp);
+    d_seg = (unsigned long long*)epa_scratch(ctx, SLOT_SEGMAX, sizeof(unsigned long long) * (size_t)Q * segp);
     if (!d_seg) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(segment maxima)");
   }
   const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
-  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
-  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, win_span, sizeof(uint32_t) * Q);
   if (!d_codes || !d_begin || !d_span) return epa_fail(ctx, EPA_ERR_HIP, "query upload failed");
   const bool out_dev = epa_is_device_ptr(lnl);
-  double* d_lnl = out_dev ? lnl : (double*)epa_scratch(ctx, 3, sizeof(double) * (size_t)Q * ctx->B);
+  double* d_lnl = out_dev ? lnl : (double*)epa_scratch(ctx, SLOT_TABLE, sizeof(double) * (size_t)Q * ctx->B);
   if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(lnl)");
   if (d_seg) {
     ctx->segmax = d_seg;
@@ -1680,14 +1680,14 @@ extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_
         return epa_fail(ctx, EPA_ERR_INVALID_ARG, "pair index out of range");
   }
   const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
-  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
-  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
-  const epa_pair* d_pairs = (const epa_pair*)epa_to_device(ctx, 4, pairs, sizeof(epa_pair) * n_pairs);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, win_span, sizeof(uint32_t) * Q);
+  const epa_pair* d_pairs = (const epa_pair*)epa_to_device(ctx, SLOT_PAIRS, pairs, sizeof(epa_pair) * n_pairs);
   if (!d_codes || !d_begin || !d_span || !d_pairs)
     return epa_fail(ctx, EPA_ERR_HIP, "thorough input upload failed");
   const bool out_dev = epa_is_device_ptr(out);
-  epa_result* d_out = out_dev ? out : (epa_result*)epa_scratch(ctx, 5, sizeof(epa_result) * n_pairs);
-  unsigned long long* d_stats = (unsigned long long*)epa_scratch(ctx, 6, 256);
+  epa_result* d_out = out_dev ? out : (epa_result*)epa_scratch(ctx, SLOT_RESULTS, sizeof(epa_result) * n_pairs);
+  unsigned long long* d_stats = (unsigned long long*)epa_scratch(ctx, SLOT_STATS, 256);
   if (!d_out || !d_stats) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(thorough out)");
   rc = epa_zero_async(ctx, d_stats, 128);
   if (rc) return rc;
@@ -1984,10 +1984,10 @@ extern "C" int epa_dev_select_candidates(epa_ctx* ctx, const double* lnl, uint32
   *n_pairs = 0;
   if (Q == 0) return EPA_OK;
   EPA_HIP(ctx, hipSetDevice(ctx->device));
-  const double* d_lnl = (const double*)epa_to_device(ctx, 3, lnl, sizeof(double) * (size_t)Q * ctx->B);
+  const double* d_lnl = (const double*)epa_to_device(ctx, SLOT_TABLE, lnl, sizeof(double) * (size_t)Q * ctx->B);
   if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "lnl upload failed");
   const bool out_dev = epa_is_device_ptr(pairs);
-  epa_pair* d_pairs = out_dev ? pairs : (epa_pair*)epa_scratch(ctx, 4, sizeof(epa_pair) * max_pairs);
+  epa_pair* d_pairs = out_dev ? pairs : (epa_pair*)epa_scratch(ctx, SLOT_PAIRS, sizeof(epa_pair) * max_pairs);
   if (!d_pairs) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(pairs)");
   int rc = launch_select(ctx, d_lnl, Q, threshold, d_pairs, max_pairs, n_pairs);
   if (rc) return rc;
@@ -2011,16 +2011,16 @@ static int chunk_body_begin(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t
   // internal table: rows padded to whole 64-byte sectors (the preplacement kernels write 8
   // consecutive branches per burst; with rows of B doubles every burst straddled two sectors)
   const uint32_t pitch = (ctx->B + 7u) & ~7u;
-  double* d_lnl = (double*)epa_scratch(ctx, 3, sizeof(double) * (size_t)Q * pitch);
+  double* d_lnl = (double*)epa_scratch(ctx, SLOT_TABLE, sizeof(double) * (size_t)Q * pitch);
   if (!d_lnl) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(chunk table)");
   ctx->lnl_pitch = pitch;
   // per-(query, 64-branch segment) maxima of the table: a by-product of the preplacement fast paths that lets
-  // the dynamic rule read only the segments near a row's maximum (preplace.hip: seg_key, k_select_seg)
+  // the dynamic rule read only the segments near a row's maximum (preplace.hip SegTrack, select.hip k_select_seg)
   const uint32_t nseg = (ctx->B + 63) / 64;
   ctx->segmax = nullptr;
   if (nseg <= 64 && ctx->heur_mode == 0) {
     ctx->segp = (nseg + 7u) & ~7u;
-    ctx->segmax = (unsigned long long*)epa_scratch(ctx, 10, sizeof(unsigned long long) * (size_t)Q * ctx->segp);
+    ctx->segmax = (unsigned long long*)epa_scratch(ctx, SLOT_SEGMAX, sizeof(unsigned long long) * (size_t)Q * ctx->segp);
     if (!ctx->segmax) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(segment maxima)");
     // zeroed by launch_preplace together with its status words and key counts (one kernel: ctx->segmax_zero_bytes)
     ctx->segmax_zero_bytes = sizeof(unsigned long long) * (size_t)Q * ctx->segp;
@@ -2054,7 +2054,7 @@ static int chunk_body_begin(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t
     const bool off = !ctx->opt.queued_thorough;
     const int cls = epa_span_class(ctx->s, max_span);
     const bool eligible = !off && ctx->s == 4 && !ctx->generic_thorough && ctx->dna.ng == 1 && epa_th_ctr(ctx) &&
-                          (cls <= 2 || cls == 10 || cls == 11);
+                          epa_tip_class_ok(cls);   // the single-wave classes
     if (eligible) {
       rc = launch_select_emit(ctx, sp);
       if (!rc && ctx->clean_stats[ctx->bank] == d_stats) ctx->clean_stats[ctx->bank] = nullptr;
@@ -2084,7 +2084,7 @@ static int chunk_body_end(epa_ctx* ctx, SelectPending* sp, const uint8_t* d_code
   // the queued launch ran iff all n pairs are of its class (no overflow / window error: checked above) -- the test
   // k_thorough_dna applied to the same block
   // (both halves of the class where the selection counted its tip-distal pairs apart: the queued launch takes them all)
-  if (sp->queued_cls >= 0 && sp->rb[9 + sp->queued_cls] + sp->rb[9 + epa_tip_class(sp->queued_cls)] == (uint32_t)n) return EPA_OK;
+  if (sp->queued_cls >= 0 && sp->rb[RB_HIST + sp->queued_cls] + sp->rb[RB_HIST + epa_tip_class(sp->queued_cls)] == (uint32_t)n) return EPA_OK;
   if (ctx->clean_stats[ctx->bank] == d_stats && sp->queued_cls < 0) ctx->clean_stats[ctx->bank] = nullptr;   // cleared behind the selection
   else {
     ctx->clean_stats[ctx->bank] = nullptr;
@@ -2148,12 +2148,12 @@ extern "C" int epa_dev_place_chunk(epa_ctx* ctx, const uint8_t* q_codes, const u
   }
   if (max_span > ctx->W) max_span = ctx->W;
   const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
-  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
-  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, win_span, sizeof(uint32_t) * Q);
   if (!d_codes || !d_begin || !d_span) return epa_fail(ctx, EPA_ERR_HIP, "query upload failed");
   const bool pairs_dev = epa_is_device_ptr(pairs), res_dev = epa_is_device_ptr(results);
-  epa_pair* d_pairs = pairs_dev ? pairs : (epa_pair*)epa_scratch(ctx, 4, sizeof(epa_pair) * max_pairs);
-  epa_result* d_res = res_dev ? results : (epa_result*)epa_scratch(ctx, 5, sizeof(epa_result) * max_pairs);
+  epa_pair* d_pairs = pairs_dev ? pairs : (epa_pair*)epa_scratch(ctx, SLOT_PAIRS, sizeof(epa_pair) * max_pairs);
+  epa_result* d_res = res_dev ? results : (epa_result*)epa_scratch(ctx, SLOT_RESULTS, sizeof(epa_result) * max_pairs);
   if (!d_pairs || !d_res) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(chunk buffers)");
   // thorough counters: second half of the context's 256-byte counter block
   unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(epa_th_ctr(ctx)) + 128);
@@ -2795,26 +2795,26 @@ extern "C" int epa_dev_place_all(epa_ctx* ctx, const uint8_t* q_codes, const uin
   const uint64_t n = (uint64_t)ctx->B * Q;
   if (n > 0xffffffffull) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "place_all: more than 2^32 pairs per chunk");
   const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
-  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, 1, win_begin, sizeof(uint32_t) * Q);
-  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, 2, win_span, sizeof(uint32_t) * Q);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, win_span, sizeof(uint32_t) * Q);
   if (!d_codes || !d_begin || !d_span) return epa_fail(ctx, EPA_ERR_HIP, "query upload failed");
-  epa_pair* d_all = (epa_pair*)epa_scratch(ctx, 4, sizeof(epa_pair) * n);
-  epa_result* d_res = (epa_result*)epa_scratch(ctx, 5, sizeof(epa_result) * n);
-  unsigned long long* d_stats = (unsigned long long*)epa_scratch(ctx, 6, 256);
+  epa_pair* d_all = (epa_pair*)epa_scratch(ctx, SLOT_PAIRS, sizeof(epa_pair) * n);
+  epa_result* d_res = (epa_result*)epa_scratch(ctx, SLOT_RESULTS, sizeof(epa_result) * n);
+  unsigned long long* d_stats = (unsigned long long*)epa_scratch(ctx, SLOT_STATS, 256);
   if (!d_all || !d_res || !d_stats) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(all-pairs buffers)");
   ctx->d_status = nullptr;
   EPA_HIP(ctx, hipMemsetAsync(d_stats, 0, 256, ctx->stream));
   hipLaunchKernelGGL(k_all_pairs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_all, ctx->B, Q);
   rc = launch_thorough(ctx, d_all, n, d_codes, d_begin, d_span, max_span, d_res, d_stats);
   if (rc) return rc;
-  // filtered output: Q x filter_max slots, staged in scratch 3 when the caller's buffers are on the host
+  // filtered output: Q x filter_max slots, staged in SLOT_OUT when the caller's buffers are on the host
   const size_t slots = (size_t)Q * filter_max;
   const bool p_dev = epa_is_device_ptr(pairs), r_dev = epa_is_device_ptr(results), l_dev = epa_is_device_ptr(lwr),
              c_dev = epa_is_device_ptr(counts);
   const size_t off_r = (sizeof(epa_pair) * slots + 255) & ~(size_t)255;
   const size_t off_l = off_r + ((sizeof(epa_result) * slots + 255) & ~(size_t)255);
   const size_t off_c = off_l + ((sizeof(double) * slots + 255) & ~(size_t)255);
-  char* stage = (char*)epa_scratch(ctx, 3, off_c + sizeof(uint32_t) * Q);
+  char* stage = (char*)epa_scratch(ctx, SLOT_OUT, off_c + sizeof(uint32_t) * Q);
   if (!stage) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(filter output)");
   epa_pair* o_p = p_dev ? pairs : (epa_pair*)stage;
   epa_result* o_r = r_dev ? results : (epa_result*)(stage + off_r);
@@ -2900,8 +2900,8 @@ extern "C" int epa_dev_place_all_rows(epa_ctx* ctx, const uint8_t* q_codes, cons
   const size_t off_l = off_r + ((sizeof(epa_result) * slots + 255) & ~(size_t)255);
   const size_t off_c = off_l + ((sizeof(double) * slots + 255) & ~(size_t)255);
   const size_t off_n = off_c + ((sizeof(uint32_t) * Q + 255) & ~(size_t)255);
-  char* out = (char*)epa_scratch(ctx, 11, off_n + 256);
-  epa_row* rows = (epa_row*)epa_scratch(ctx, 12, sizeof(epa_row) * 2 * slots);
+  char* out = (char*)epa_scratch(ctx, SLOT_ROWS_OUT, off_n + 256);
+  epa_row* rows = (epa_row*)epa_scratch(ctx, SLOT_ROWS, sizeof(epa_row) * 2 * slots);
   if (!out || !rows) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(place_all rows)");
   int rc = epa_dev_place_all(ctx, q_codes, win_begin, win_span, Q, max_span, min_lwr, acc_threshold, filter_min, filter_max,
                              (epa_pair*)out, (epa_result*)(out + off_r), (double*)(out + off_l), (uint32_t*)(out + off_c), stats);

@@ -8,7 +8,15 @@
 #include <string>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "epa_dev.h"
+
+// rocprim's radix sort falls back to a merge sort (block sort + log2 n merge passes: ~19 launches for
+// the 262k candidate keys of a chunk) below one million items; the sorts of this library use a few key bits only
+// (branch id, window start, span class, query), where Onesweep digit passes do: 4 - 5 launches.
+using epa_radix_cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
+                                                 rocprim::default_config, 0>;
 
 #define EPA_MAX_STATES 20
 #define EPA_MAX_CATS 16
@@ -54,10 +62,44 @@ struct EvTimer {
   bool valid = false;
 };
 
+// class keys of the thorough launches: the span classes (epa_span_class below), then the tip-distal halves of the
+// single-wave DNA classes 0, 1, 2, 10, 11 (keys 12 .. 16: pairs whose branch has a tip on the distal side,
+// thorough_dna.hip TIPD)
+constexpr int EPA_N_CLS = 12;
+constexpr int EPA_N_CLSX = 17;
+
+// ---- the two word blocks of a candidate selection (select.hip)
+// Read-back block: everything the host waits for after a selection, packed on the device (k_pack_readback) so that ONE
+// small copy brings it.  launch_select_end, select_check_status and chunk_body_end read the host copy; a queued Newton
+// launch (k_thorough_dna, ThArgs::spec) reads the device copy.
+enum EpaReadback : int {   // int like the literals they replace: index arithmetic in the kernels keeps its type
+  RB_TOTAL = 0,                  // candidate pairs
+  RB_STATUS = RB_TOTAL + 1,      // the first eight words of the status block below
+  RB_HIST = RB_STATUS + 8,       // [EPA_N_CLSX] pairs per class key
+  RB_TIP_SPLIT = 30,             // 1: the histogram counts the tip-distal pairs apart (SelectPending::tip_split)
+  RB_WINDOW = 32,                // the preplacement's window validation: [0] an all-gap query, [1] a window past the width
+  RB_WORDS = RB_WINDOW + 4,
+};
+// Status block at the head of the selection's scratch (512 bytes, zeroed before the kernels)
+enum EpaSelStatus : int {
+  SEL_OVERFLOW = 2,              // staging form: the longest candidate list + 1 when a staging row was too short
+  SEL_HIST = 8,                  // [EPA_N_CLS] span-class histogram of the candidate counts (k_class_hist / k_select_seg)
+  SEL_TIP_TOTAL = 40,            // candidate pairs on branches that end in a tip (k_scan_counts)
+  SEL_READBACK = 64,             // the packed read-back block
+  SEL_WORDS = 128,
+};
+static_assert(RB_TOTAL == 0 && RB_STATUS == 1 && RB_HIST == 9 && RB_TIP_SPLIT == 30 && RB_WINDOW == 32 && RB_WORDS == 36,
+              "the read-back block's layout is shared with queued kernels: move a word everywhere or nowhere");
+static_assert(RB_HIST + EPA_N_CLSX <= RB_TIP_SPLIT && RB_TIP_SPLIT < RB_WINDOW, "read-back fields overlap");
+static_assert(SEL_HIST == 8 && SEL_TIP_TOTAL == 40 && SEL_READBACK == 64, "the selection's status block moved");
+static_assert(RB_HIST - RB_STATUS == SEL_HIST, "k_pack_readback copies status words and histogram in one run");
+static_assert(SEL_HIST + EPA_N_CLS <= SEL_TIP_TOTAL && SEL_TIP_TOTAL < SEL_READBACK && SEL_READBACK + RB_WORDS <= SEL_WORDS,
+              "status block fields overlap");
+
 // One slot of the double-buffered chunk pipeline (epa_dev_chunk_stage / _launch / _finish): the
 // query upload of chunk k+1 and the result download of chunk k-1 run on the context's copy stream
 // while the kernels of chunk k run on its compute stream.
-// state of a candidate selection between launch_select_begin and launch_select_end (preplace.hip)
+// state of a candidate selection between launch_select_begin and launch_select_end (select.hip)
 struct SelectPending {
   const double* d_lnl = nullptr;
   uint32_t Q = 0, cap = 0;
@@ -67,11 +109,11 @@ struct SelectPending {
   const uint32_t* d_span = nullptr;
   unsigned long long *stage = nullptr, *keys_a = nullptr, *keys_b = nullptr;
   uint32_t *counts = nullptr, *offsets = nullptr;
-  uint32_t *bitmap = nullptr, *boffs = nullptr;   // bitmap form of the selection (preplace.hip, SelOut)
+  uint32_t *bitmap = nullptr, *boffs = nullptr;   // bitmap form of the selection (select.hip, SelOut)
   uint32_t wpr = 0;
   void* temp = nullptr;
   size_t sort_bytes = 0;
-  uint32_t* rb = nullptr;   // host read-back block, 64 words
+  uint32_t* rb = nullptr;   // host read-back block (EpaReadback; the callers keep 64 words)
   bool have_status = false;
   bool rerun = false;
   hipEvent_t ev_rb = nullptr;      // recorded behind the read-back copy: launch_select_end waits for this, not for the stream
@@ -81,9 +123,9 @@ struct SelectPending {
   // span-class histogram of the pairs this selection emitted (launch_select_end, when d_span was given): handed to the
   // launch_thorough of the SAME chunk body (chunk_body_end), which saves that launch's device round trip.  It lives
   // and dies with the selection: nothing in epa_ctx remembers it, so no other call can be partitioned by it
-  uint32_t cls_hist[24] = {};      // [EPA_N_CLSX]
+  uint32_t cls_hist[EPA_N_CLSX] = {};
   bool have_hist = false;
-  bool tip_split = false;          // cls_hist counts the tip-distal pairs apart (classes EPA_N_CLS ..): rb[30]
+  bool tip_split = false;          // cls_hist counts the tip-distal pairs apart (classes EPA_N_CLS ..): rb[RB_TIP_SPLIT]
   const uint32_t* pre_status = nullptr;   // window-validation words of THIS chunk's preplacement (ctx->d_status may belong
                                           // to another pipeline slot by the time a widened re-run packs the read-back)
 };
@@ -218,21 +260,21 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 21;   // the post-placement calls name theirs: EpaSlot below
+  static constexpr int N_SCRATCH = 21;   // named by EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
   void* scratch[N_BANKS * N_SCRATCH] = {};
   size_t scratch_sz[N_BANKS * N_SCRATCH] = {};
 
-  uint32_t* d_status = nullptr;   // window-validation words of the last preplace (in scratch 6)
+  uint32_t* d_status = nullptr;   // window-validation words of the last preplace (the head of SLOT_PREPLACE)
   // (the span-class histogram of a selection's pairs is NOT context state: SelectPending::cls_hist)
   uint32_t select_cap = 64;       // staging slots per query of the candidate selection
   uint32_t* th_ctr = nullptr;  // work counters of the thorough kernel (one per XCD slice): 256 B per bank,
                                // [0, 64) the counters, [128, 256) the fused chunk's statistics
   uint32_t lnl_pitch = 0;  // row pitch (doubles) of the table handed to launch_preplace / launch_select; 0 = B
   // fused chunk body only: [Q][segp] order-preserving keys of the per-segment maxima of the table rows
-  // (written by the preplacement fast paths, read by k_select_seg; preplace.hip), or null
+  // (written by the preplacement fast paths of preplace.hip, read by k_select_seg of select.hip), or null
   unsigned long long* segmax = nullptr;
   uint32_t segp = 0;
   size_t segmax_zero_bytes = 0;   // chunk_body_begin -> launch_preplace: clear segmax with the status / key-count fill
@@ -278,6 +320,16 @@ struct epa_ctx {
 // ---- helpers (epa_dev.hip)
 int epa_fail(epa_ctx* ctx, int code, const std::string& msg);
 void* epa_scratch(epa_ctx* ctx, int slot, size_t bytes);
+// Bump carver of one scratch allocation: take<T>(n) hands out n elements and moves on to the next 256-byte boundary,
+// tail(bytes) hands out the last piece as it is.  With a null base it only measures, so a layout is written ONCE, as a
+// function of the carver that is run for the size (off) and again for the pointers.
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct Carver {
+  char* base = nullptr;
+  size_t off = 0;
+  void* tail(size_t bytes) { char* p = base ? base + off : nullptr; off += bytes; return p; }
+  template <typename T> T* take(size_t n) { return static_cast<T*>(tail(align256(sizeof(T) * n))); }
+};
 inline uint32_t* epa_th_ctr(epa_ctx* ctx) { return ctx->th_ctr ? ctx->th_ctr + 64 * ctx->bank : nullptr; }
 // Zero `bytes` at p (and optionally a second range) with ONE plain kernel on the context's stream.  A hipMemsetAsync is
 // a blit launch of its own with ~6 us of idle queue before and after it between kernels (profiles/r5_step_timeline.txt:
@@ -314,19 +366,50 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
       return epa_fail(ctx, EPA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
-// ---- scratch slots of the post-placement entry points (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support,
-// _rell_tests, _rell_au, _rell_kh: epa_dev.hip) and of their launchers (score_at.hip, marginal.hip, rell.hip).  The placement
-// path writes its slots as numbers: 0 .. 4 mean the same there, 5 .. 12 are its own (7 .. 9 too, within its own calls).
-// Among these seven, 7 and 9 have two meanings.  A call with per-entry lengths stages them in 7 .. 9 (EntryCall::stage); marginal_like has no
-// lengths -- it hands the staging null for all three, so nothing of its own call sits there -- and keeps its rule and
-// its waves' grid values in 7 and 9 instead.  Every call stages what it reads before it launches, so what the other
-// meaning left behind in an earlier call is never read.
+// ---- scratch slots of a bank (epa_scratch / epa_to_device).  0 .. 12: the placement path (epa_dev.hip and the
+// launchers of preplace.hip, select.hip, thorough_*.hip); 0 .. 4, 7 .. 9 and 13 .. 20: the post-placement entry points
+// (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au, _rell_kh) and their launchers
+// (score_at.hip, marginal.hip, rell.hip).  Names that share a number never hold live data at the same time:
+//   2   the tip map is read only by the transform kernels of epa_dev_create, queued before any call can stage a span
+//       (SLOT_CLV_*, SLOT_SCALER_*: creation only, in the same way)
+//   6   the preplacement's status words are read (preplace_check_status; k_pack_readback through SelectPending::
+//       pre_status) inside the call that ran the preplacement; epa_dev_thorough and epa_dev_place_all keep statistics
+//       there in calls of their own, which run no preplacement (place_all clears ctx->d_status), and the chunk bodies
+//       keep theirs elsewhere (th_ctr, ChunkSlot::d_stats)
+//   7   a Newton launch that carves its scratch here is queued on the bank's stream (or forked from it) behind the
+//       k_emit_pairs that reads the selection's bitmap, and a grow goes through hipFree, which waits for the device;
+//       the post-placement calls stage lengths / rule in calls of their own
+//   9   epa_dev_tree_logl and the TH_TIMING build use it in calls of their own
+//   10  the 4-bit codes are consumed by the unpack kernel (epa_codes_to_device) queued on the same stream ahead of the
+//       fill that clears the segment maxima (launch_preplace)
+// Among the post-placement calls 7 and 9 have two meanings.  A call with per-entry lengths stages them in 7 .. 9
+// (EntryCall::stage); marginal_like has no lengths -- it hands the staging null for all three, so nothing of its own
+// call sits there -- and keeps its rule and its waves' grid values in 7 and 9 instead.  Every call stages what it reads
+// before it launches, so what the other meaning left behind in an earlier call is never read.
 enum EpaSlot : int {
   SLOT_CODES = 0,         // query codes, one byte per site (epa_codes_to_device)
   SLOT_BEGIN = 1,         // win_begin [Q]
   SLOT_SPAN = 2,          // win_span [Q]
-  SLOT_OUT = 3,           // the outputs the caller wants in host memory, one after the other (EntryCall::run)
-  SLOT_PAIRS = 4,         // the entries' pairs [n]
+  SLOT_OUT = 3,           // the outputs the caller wants in host memory, one after the other (EntryCall::run, place_all)
+  SLOT_PAIRS = 4,         // the entries' / the chunk's pairs [n]
+  SLOT_CLV_PROX = 0,      // epa_dev_create: one side's CLV or tip characters of the branch being transformed
+  SLOT_CLV_DIST = 1,
+  SLOT_TIPMAP = 2,        // epa_dev_create: tip character -> state set
+  SLOT_SCALER_PROX = 3,   // epa_dev_create: one side's scaler counts
+  SLOT_SCALER_DIST = 4,
+  SLOT_TABLE = 3,         // the Q x B preplacement table (host-side callers; the fused chunk body pads its rows)
+  SLOT_RESULTS = 5,       // epa_result [n]
+  SLOT_PREPLACE = 6,      // launch_preplace: status words (ctx->d_status) | sort, groups, packed offsets
+  SLOT_STATS = 6,         // epa_dev_thorough, epa_dev_place_all: the Newton launch's 256-byte statistics block
+  SLOT_SELECT = 7,        // launch_select_begin: status block | bitmap or staging form
+  SLOT_NEWTON = 7,        // thorough kernels: sumtable slabs of the windows too long for registers / LDS
+  SLOT_CLASS_SORT = 8,    // launch_thorough: the pair order by class key
+  SLOT_TREE_LNL = 9,      // epa_dev_tree_logl: per-workgroup partial sums
+  SLOT_TH_TIMING = 9,     // TH_TIMING build of thorough_dna.hip: cycle stamps
+  SLOT_SEGMAX = 10,       // [Q][segp] segment maxima of the table (ctx->segmax)
+  SLOT_PACKED4 = 10,      // query codes in the 4-bit wire format, before the unpack into SLOT_CODES
+  SLOT_ROWS_OUT = 11,     // epa_dev_place_all_rows: the filtered output of place_all
+  SLOT_ROWS = 12,         //   and its rows
   SLOT_PENDANT = 7,       // per-entry lengths [n] each
   SLOT_DISTAL = 8,
   SLOT_PROXIMAL = 9,
@@ -359,11 +442,7 @@ struct EntryStage {
 // kernel instantiation, so one long window does not drag a whole chunk onto the big-register
 // variant.  DNA: sites per lane NCH in {1,2,3,4,6,8,12,16,24} (class 0..8), 9 = HBM-slab kernel;
 // 20 states: 0 / 1 / 2 = windows up to 64 / 128 / 192 sites (k_thorough_aa_mfma<1/2/3>: sumtable
-// in registers), 3 = longer (k_thorough_aa with the HBM slab).
-constexpr int EPA_N_CLS = 12;
-// class keys of the thorough launches: the span classes, then the tip-distal halves of the single-wave DNA classes
-// 0, 1, 2, 10, 11 (keys 12 .. 16: pairs whose branch has a tip on the distal side, thorough_dna.hip TIPD)
-constexpr int EPA_N_CLSX = 17;
+// in registers), 3 = longer (k_thorough_aa with the HBM slab).  (EPA_N_CLS of them, EPA_N_CLSX class keys: above)
 __host__ __device__ inline bool epa_tip_class_ok(int cls) { return cls <= 2 || cls == 10 || cls == 11; }
 __host__ __device__ inline int epa_tip_class(int cls) { return cls <= 2 ? 12 + cls : cls == 10 ? 15 : cls == 11 ? 16 : cls; }
 __host__ __device__ inline int epa_base_class(int key) { return key < 12 ? key : key <= 14 ? key - 12 : key == 15 ? 10 : 11; }
@@ -399,6 +478,11 @@ int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_look
 int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin,
                     const uint32_t* d_span, uint32_t Q, double* d_lnl, uint32_t max_span);
 int preplace_check_status(epa_ctx* ctx);
+__attribute__((visibility("hidden"))) int preplace_window_error(epa_ctx* ctx, const uint32_t* st);   // the two window-validation words -> error code and text
+// one workgroup: exclusive scan of cnt[0 .. K) in place; with tip_row also *tip_total = the sum over the first K - 1
+// entries whose tip_row is not 0xffffffff (k_scan_counts, preplace.hip: the counting sort's and the selection's scan)
+__attribute__((visibility("hidden"))) void launch_scan_counts(epa_ctx* ctx, uint32_t* cnt, uint32_t K, const uint32_t* tip_row = nullptr,
+                                                               uint32_t* tip_total = nullptr);
 int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, const uint8_t* d_codes,
                     const uint32_t* d_begin, const uint32_t* d_span, uint32_t max_span,
                     epa_result* d_out, unsigned long long* d_stats,
@@ -446,6 +530,7 @@ __attribute__((visibility("hidden"))) int launch_rell_kh(epa_ctx* ctx, const Ent
 // x_logw [Kx] | p_len [Kp] | p_logw [Kp]; d_grid: [n][Kx][Kp] or null
 int launch_marginal(epa_ctx* ctx, const EntryStage& e, const double* d_rule, uint32_t Kx, uint32_t Kp, double* d_marginal,
                     double* d_grid);
+// candidate selection (select.hip)
 int launch_select(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold,
                   epa_pair* d_pairs, uint64_t max_pairs, uint64_t* n_pairs,
                   const uint32_t* d_span = nullptr);  // d_span: also histogram the span classes

@@ -49,14 +49,9 @@
 #include "epa_dev_internal.hpp"
 #include "wave_util.hpp"
 
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <vector>
-
-// digit passes, never rocprim's merge-sort fallback (thorough_dna.hip)
-using epa_radix_cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                 rocprim::default_config, 0>;
 
 namespace {
 

@@ -518,7 +518,7 @@ int launch_thorough_aa(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* d_
     a.sscratch = nullptr;
   } else {
     a.Wpad = (max_span + 63) / 64 * 64;
-    a.sscratch = (double*)epa_scratch(ctx, 7, sizeof(double) * (size_t)nwg * 80 * a.Wpad);
+    a.sscratch = (double*)epa_scratch(ctx, SLOT_NEWTON, sizeof(double) * (size_t)nwg * 80 * a.Wpad);
     if (!a.sscratch) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(AA sumtable scratch)");
   }
   if (lds_slab) {

@@ -32,13 +32,6 @@
 #include "wave_util.hpp"
 
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-
-// rocprim's radix sort falls back to a merge sort (block sort + log2 n merge passes: ~19 launches for
-// the 262k candidate keys of a chunk) below one million items; the sorts here use a few key bits only
-// (branch id, window start, span class), where Onesweep digit passes do: 4 - 5 launches.
-using epa_radix_cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                 rocprim::default_config, 0>;
 
 #include <algorithm>
 #include <vector>
@@ -1123,10 +1116,11 @@ __global__ void __launch_bounds__(64 * NW * NG, TH_WAVES) k_thorough_dna(const T
   const uint32_t w = blockIdx.x >> 3, stride = gridDim.x >> 3;
   uint64_t n_pairs = a.n_pairs;
   if constexpr (NW == 1 && NG == 1) {
-    if (a.spec) {   // queued launch: count and validity come from the selection's read-back block
-      const uint32_t n = a.spec[0];
+    if (a.spec) {   // queued launch: count and validity come from the selection's read-back block (EpaReadback)
+      const uint32_t n = a.spec[RB_TOTAL];
       // (the selection may have counted the class's tip-distal pairs apart: this launch takes both halves)
-      if (n > a.spec_max || a.spec[9 + a.spec_cls] + a.spec[9 + epa_tip_class((int)a.spec_cls)] != n || a.spec[32] || a.spec[33]) return;
+      if (n > a.spec_max || a.spec[RB_HIST + a.spec_cls] + a.spec[RB_HIST + epa_tip_class((int)a.spec_cls)] != n ||
+          a.spec[RB_WINDOW] || a.spec[RB_WINDOW + 1]) return;
       n_pairs = n;
     }
   }
@@ -1534,7 +1528,7 @@ static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t m
   // single-wave classes: resident waves + a work counter per XCD slice (round 1: the oversubscribed
   // static grid instead cost 262k pairs 6.56 vs 6.47 ms)
 #ifdef TH_TIMING
-#define TH_TIMING_ALLOC a.sscratch = (double*)epa_scratch(ctx, 9, 2048 * 64); (void)hipMemsetAsync(a.sscratch, 0, 2048 * 64, ctx->stream);
+#define TH_TIMING_ALLOC a.sscratch = (double*)epa_scratch(ctx, SLOT_TH_TIMING, 2048 * 64); (void)hipMemsetAsync(a.sscratch, 0, 2048 * 64, ctx->stream);
 #define TH_TIMING_DUMP th_timing_dump(ctx, a.sscratch);
 #else
 #define TH_TIMING_ALLOC
@@ -1620,7 +1614,7 @@ static int launch_thorough_dna_class(epa_ctx* ctx, ThArgs a, int cls, uint32_t m
       // long windows: sumtable slab in HBM, one resident wave per slab
       const uint32_t nlong = (uint32_t)std::min<uint64_t>(n_pairs, 2048);
       a.Wpad = (max_span + 63) / 64 * 64;
-      a.sscratch = (double*)epa_scratch(ctx, 7, sizeof(double) * (size_t)nlong * 17 * a.Wpad);
+      a.sscratch = (double*)epa_scratch(ctx, SLOT_NEWTON, sizeof(double) * (size_t)nlong * 17 * a.Wpad);
       if (!a.sscratch) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(long-window sumtable scratch)");
       if (ctx->dna_zero0) hipLaunchKernelGGL((k_thorough_dna_long<true>), dim3(nlong), dim3(64), 0, ctx->stream, a);
       else hipLaunchKernelGGL((k_thorough_dna_long<false>), dim3(nlong), dim3(64), 0, ctx->stream, a);
@@ -1765,7 +1759,7 @@ int launch_thorough(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, con
   uint32_t* d_hist = nullptr;
   uint32_t *d_keys = nullptr, *d_idx = nullptr, *d_keys2 = nullptr, *d_order = nullptr;
   auto carve = [&]() -> int {
-    char* base = (char*)epa_scratch(ctx, 8, 256 + 4 * nb + temp_bytes);
+    char* base = (char*)epa_scratch(ctx, SLOT_CLASS_SORT, 256 + 4 * nb + temp_bytes);
     if (!base) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(span-class scratch)");
     d_hist = (uint32_t*)base;
     d_keys = (uint32_t*)(base + 256); d_idx = (uint32_t*)(base + 256 + nb);

@@ -381,7 +381,7 @@ int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pa
   a.Wpad = (std::max(max_span, 1u) + 63) / 64 * 64;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(n_pairs, (uint64_t)ctx->n_cu * 8);
   const size_t per = (size_t)(ctx->c * ctx->s + 1) * a.Wpad;
-  a.slab = (double*)epa_scratch(ctx, 7, sizeof(double) * per * grid);
+  a.slab = (double*)epa_scratch(ctx, SLOT_NEWTON, sizeof(double) * per * grid);
   if (!a.slab) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(generic sumtable scratch)");
   const bool timed = !d_order && !caller_times;   // a per-class launch is timed by its caller
   if (timed) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_THOROUGH));

@@ -1,4 +1,4 @@
-// Wavefront-level helpers shared by the thorough kernels (gfx950, wave64).
+// Wavefront-level helpers shared by the kernels (gfx950, wave64).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -88,6 +88,32 @@ __device__ __forceinline__ unsigned wave_min_u(unsigned v) {
   v = dpp_min_u<0x142, 0xa>(v);
   v = dpp_min_u<0x143, 0xc>(v);
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// Butterfly reductions over __shfl_xor (ds_bpermute): every lane ends with the result, none is read through scalar
+// registers.  The sum adds in another order than wave_sum, so the two are not interchangeable bit for bit; the
+// selection kernels k_select / k_select_wg / k_select_stream (select.hip) are built on these.
+__device__ __forceinline__ double shfl_max(double v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ double shfl_add(double v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// Order-preserving 64-bit key of a double (atomicMax on unsigned integers finds the maximum) and back; no double maps
+// to 0.  The preplacement publishes per-segment maxima of its table rows this way (preplace.hip, SegTrack), the
+// candidate selection reads them (select.hip, k_select_seg).
+__device__ __forceinline__ unsigned long long seg_key(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double seg_val(unsigned long long k) {
+  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
 }
 
 // exp(x) for the arguments of the Newton / P-matrix tables (x = lambda r t <= 0, |x| < 1e7):
