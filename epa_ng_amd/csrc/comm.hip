@@ -453,7 +453,7 @@ static int gather_post(epa_ctx* ctx, epa_comm* c, const epa_pair* d_pairs, const
 extern "C" int epa_dev_gather_slot(epa_ctx* ctx, epa_comm* c, int slot, uint32_t seq_offset, uint64_t* ticket) {
   if (!ctx || slot < 0 || slot >= epa_ctx::N_SLOTS) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "gather_slot: slot out of range");
   ChunkSlot* s = &ctx->slots[slot];
-  if (s->state != 2 || !(s->l_flags & EPA_CHUNK_NO_D2H))
+  if (s->state != SlotState::Launched || !(s->l_flags & EPA_CHUNK_NO_D2H))
     return epa_fail(ctx, EPA_ERR_INVALID_ARG, "gather_slot: the slot needs a finished launch with EPA_CHUNK_NO_D2H");
   if (s->leader >= 0)   // its rows are a range of the group's regrouped buffers, known to the host only at finish
     return epa_fail(ctx, EPA_ERR_INVALID_ARG, "gather_slot: the slot is part of a group launch: epa_dev_chunk_finish it and post its rows with epa_dev_gather_results");

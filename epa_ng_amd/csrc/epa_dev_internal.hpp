@@ -96,12 +96,20 @@ static_assert(RB_HIST - RB_STATUS == SEL_HIST, "k_pack_readback copies status wo
 static_assert(SEL_HIST + EPA_N_CLS <= SEL_TIP_TOTAL && SEL_TIP_TOTAL < SEL_READBACK && SEL_READBACK + RB_WORDS <= SEL_WORDS,
               "status block fields overlap");
 
-// One slot of the double-buffered chunk pipeline (epa_dev_chunk_stage / _launch / _finish): the
-// query upload of chunk k+1 and the result download of chunk k-1 run on the context's copy stream
-// while the kernels of chunk k run on its compute stream.
+// The table a preplacement writes (launch_preplace) and a candidate selection reads (launch_select_begin)
+struct PreTable {
+  double* lnl = nullptr;                  // [Q][pitch]
+  uint32_t pitch = 0;                     // row pitch in doubles: B, or more where the rows are padded
+  // [Q][segp] order-preserving keys of the per-segment maxima of the table rows (written by the preplacement fast
+  // paths of preplace.hip, which clears them first; read by k_select_seg of select.hip), or null: none wanted
+  unsigned long long* segmax = nullptr;
+  uint32_t segp = 0;
+};
+
 // state of a candidate selection between launch_select_begin and launch_select_end (select.hip)
 struct SelectPending {
-  const double* d_lnl = nullptr;
+  PreTable table;
+  const uint32_t* pre_status = nullptr;   // status words of the preplacement that wrote the table, or null
   uint32_t Q = 0, cap = 0;
   double threshold = 0.0;
   epa_pair* d_pairs = nullptr;
@@ -115,7 +123,6 @@ struct SelectPending {
   size_t sort_bytes = 0;
   uint32_t* rb = nullptr;   // host read-back block (EpaReadback; the callers keep 64 words)
   bool have_status = false;
-  bool rerun = false;
   hipEvent_t ev_rb = nullptr;      // recorded behind the read-back copy: launch_select_end waits for this, not for the stream
   const uint32_t* d_rb = nullptr;  // the packed read-back block on the device (bitmap form)
   bool emitted = false;            // k_emit_pairs (guarded by the total) is already queued behind the read-back
@@ -126,11 +133,26 @@ struct SelectPending {
   uint32_t cls_hist[EPA_N_CLSX] = {};
   bool have_hist = false;
   bool tip_split = false;          // cls_hist counts the tip-distal pairs apart (classes EPA_N_CLS ..): rb[RB_TIP_SPLIT]
-  const uint32_t* pre_status = nullptr;   // window-validation words of THIS chunk's preplacement (ctx->d_status may belong
-                                          // to another pipeline slot by the time a widened re-run packs the read-back)
 };
 
-struct ChunkSlot {
+// One slot of the double-buffered chunk pipeline (epa_dev_chunk_stage / _launch / _finish, chunk.hip): the
+// query upload of chunk k+1 and the result download of chunk k-1 run on the context's copy stream
+// while the kernels of chunk k run on its compute stream.
+enum class SlotState : int {
+  Free,         // nothing staged, no launch in flight
+  Staged,       // chunk_stage: the chunk waits for its launch (and stays so after a recoverable launch error)
+  Begun,        // chunk_launch_begin: preplacement and selection are queued (a group's leader: for the merged chunk)
+  Launched,     // chunk_launch_end: Newton kernels and downloads are queued; chunk_finish hands the rows out
+  GroupMember,  // staged member, not the leader, of a group whose launch was begun: the leader's launch_end moves it on
+};
+constexpr int EPA_MAX_GROUP = 8;
+
+struct ChunkInputs {          // the three query arrays of a chunk in HBM
+  const uint8_t* codes;
+  const uint32_t *begin, *span;
+};
+
+struct __attribute__((visibility("hidden"))) ChunkSlot {   // hidden: its inline functions are not exported
   void* h_in = nullptr;       // pinned bounce buffer: codes | win_begin | win_span
   size_t h_in_sz = 0;
   void* d_in = nullptr;       // the same three arrays in HBM
@@ -145,7 +167,7 @@ struct ChunkSlot {
   bool packed4 = false;
   epa_pair* d_pairs = nullptr;    // slot-owned result buffers (used when the caller passes none)
   epa_result* d_res = nullptr;
-  size_t cap = 0;
+  size_t d_pairs_sz = 0, d_res_sz = 0;
   void* h_out = nullptr;      // pinned: pairs | results
   size_t h_out_sz = 0;
   unsigned long long* h_stats = nullptr;  // pinned, 16 words
@@ -155,7 +177,14 @@ struct ChunkSlot {
   const epa_pair* out_pairs = nullptr;    // what finish() hands out
   const epa_result* out_res = nullptr;
   uint64_t n = 0;
-  int state = 0;              // 0 free, 1 staged, 3 launch begun (selection in flight), 2 launched, 4 member of a group whose launch was begun
+  SlotState state = SlotState::Free;
+  bool unfinished() const { return state == SlotState::Begun || state == SlotState::Launched || state == SlotState::GroupMember; }
+  ChunkInputs staged_inputs() const {   // the caller's arrays read in place, or the slot's upload
+    if (x_codes) return {x_codes, x_begin, x_span};
+    const char* d = (const char*)d_in;
+    const uint32_t* b = (const uint32_t*)(d + codes_bytes);
+    return {(const uint8_t*)d, b, b + Q};
+  }
   // between launch_begin and launch_end
   SelectPending sel;
   uint32_t* h_sel = nullptr;  // pinned, 64 words: the selection's read-back block
@@ -172,8 +201,8 @@ struct ChunkSlot {
   int g_index = 0;
   int g_n = 0;                // leader: members of the group in flight (0: an ordinary launch)
   int g_left = 0;             // leader: members not finished yet (their results live in the leader's buffers)
-  int g_slots[8] = {};
-  uint32_t g_qoff[9] = {};    // leader: first merged query index of every member
+  int g_slots[EPA_MAX_GROUP] = {};
+  uint32_t g_qoff[EPA_MAX_GROUP + 1] = {};   // leader: first merged query index of every member
   uint32_t own_Q = 0;         // leader: its own chunk (restored after the group launch / on a recoverable error)
   const uint8_t* own_x_codes = nullptr;
   const uint32_t *own_x_begin = nullptr, *own_x_span = nullptr;
@@ -184,8 +213,50 @@ struct ChunkSlot {
   size_t g_cap = 0;
   uint32_t* d_goff = nullptr;     // [9] member offsets into the regrouped rows (device / pinned)
   uint32_t* h_goff = nullptr;
+
+  // ---- a group's bookkeeping, kept in its leader (`all`: epa_ctx::slots)
+  // launch_many_begin: the leader stands for the merged chunk (read in place, like an HBM-resident one) ...
+  void lead_merged(uint32_t total, const uint8_t* codes, const uint32_t* begin, const uint32_t* span) {
+    own_Q = Q; own_x_codes = x_codes; own_x_begin = x_begin; own_x_span = x_span;
+    Q = total; x_codes = codes; x_begin = begin; x_span = span;
+  }
+  void restore_own() { Q = own_Q; x_codes = own_x_codes; x_begin = own_x_begin; x_span = own_x_span; }
+  // ... and once its launch is begun, the members are bound to it
+  void group_begun(ChunkSlot* all, const int* slots, int n, const uint32_t* qoff) {
+    g_n = n;
+    for (int i = 0; i <= n; ++i) g_qoff[i] = qoff[i];
+    for (int i = 0; i < n; ++i) {
+      g_slots[i] = slots[i];
+      all[slots[i]].leader = slots[0];
+      all[slots[i]].g_index = i;
+      if (i) all[slots[i]].state = SlotState::GroupMember;
+    }
+  }
+  // launch_end: the group is launched -- the leader has its own chunk back, every member waits for its finish
+  // (g_left counts them down: until then their rows live in the leader's buffers)
+  void group_launched(ChunkSlot* all) {
+    restore_own();
+    g_left = g_n;
+    for (int i = 1; i < g_n; ++i) {
+      all[g_slots[i]].state = SlotState::Launched;
+      all[g_slots[i]].l_flags = l_flags;
+    }
+  }
+  // The launch that was begun on this slot is over without results: the slot, and with it every member of its group,
+  // goes back to `to` -- Staged after a recoverable error, Free when the chunk is abandoned.  g_left is cleared as well:
+  // a failure after the members were marked must not leave the leader refusing chunk_stage for ever
+  void launch_over(ChunkSlot* all, SlotState to) {
+    state = to;
+    if (g_n <= 1) return;
+    restore_own();
+    for (int i = 0; i < g_n; ++i) {
+      all[g_slots[i]].leader = -1;
+      if (i) all[g_slots[i]].state = to;
+    }
+    g_n = 0;
+    g_left = 0;
+  }
 };
-constexpr int EPA_MAX_GROUP = 8;
 
 // Diagnostic switches of a context (epa_dev_set_option; include/epa_dev.h lists them).  They select between code
 // paths that return the same results -- cross-check kernels for the parity tests, A/B switches of the bench -- and
@@ -267,17 +338,12 @@ struct epa_ctx {
   void* scratch[N_BANKS * N_SCRATCH] = {};
   size_t scratch_sz[N_BANKS * N_SCRATCH] = {};
 
-  uint32_t* d_status = nullptr;   // window-validation words of the last preplace (the head of SLOT_PREPLACE)
-  // (the span-class histogram of a selection's pairs is NOT context state: SelectPending::cls_hist)
+  // (NOT context state, but arguments and results of the launchers: the preplacement table's layout, PreTable; the
+  // preplacement's status words, handed back by launch_preplace; the span-class histogram of a selection's pairs,
+  // SelectPending::cls_hist)
   uint32_t select_cap = 64;       // staging slots per query of the candidate selection
   uint32_t* th_ctr = nullptr;  // work counters of the thorough kernel (one per XCD slice): 256 B per bank,
                                // [0, 64) the counters, [128, 256) the fused chunk's statistics
-  uint32_t lnl_pitch = 0;  // row pitch (doubles) of the table handed to launch_preplace / launch_select; 0 = B
-  // fused chunk body only: [Q][segp] order-preserving keys of the per-segment maxima of the table rows
-  // (written by the preplacement fast paths of preplace.hip, read by k_select_seg of select.hip), or null
-  unsigned long long* segmax = nullptr;
-  uint32_t segp = 0;
-  size_t segmax_zero_bytes = 0;   // chunk_body_begin -> launch_preplace: clear segmax with the status / key-count fill
   bool code_packed4 = false;  // q_codes arrive in the 4-bit wire format (epa_dev_set_query_packing)
   int heur_mode = 0;        // EPA_HEUR_* (epa_dev_set_heuristic)
   double heur_param = 0.0;  // fixed: fraction of the branches
@@ -347,8 +413,14 @@ bool epa_is_device_ptr(const void* p);
 const void* epa_to_device(epa_ctx* ctx, int slot, const void* p, size_t bytes);
 // query code rows -> device in the one-byte layout the kernels read (unpacks the 4-bit wire format)
 const uint8_t* epa_codes_to_device(epa_ctx* ctx, const uint8_t* q_codes, uint32_t Q);
+// the 4-bit wire format of Q code rows -> one byte per code, on stream st (chunk.hip: a slot's own upload)
+__attribute__((visibility("hidden"))) void launch_unpack4(hipStream_t st, const uint8_t* d_packed, uint8_t* d_codes, uint32_t Q, uint32_t stride);
+// a small u32 array as the host sees it: p itself, or (device memory) a copy in buf made after st has drained; null: the copy failed
+__attribute__((visibility("hidden"))) const uint32_t* host_view(const uint32_t* p, size_t n, std::vector<uint32_t>& buf, hipStream_t st);
 // hst: the 16 statistics words of a thorough launch ([7] start, [8 + x] last exit of XCD x: ThArgs::xstamp)
 void epa_xcd_feedback(epa_ctx* ctx, uint64_t n_pairs, const unsigned long long* hst);
+// what a Newton launch over n pairs left in hst: XCD feedback, ctx->last_stats (and *stats), EPA_ERR_NEG_INF (chunk.hip)
+__attribute__((visibility("hidden"))) int chunk_stats(epa_ctx* ctx, uint64_t n, const unsigned long long* hst, epa_thorough_stats* stats);
 // in-kernel s_memrealtime stamps are kept to 43 bits (24 h at 100 MHz) so that the XCD's share fits below them
 #define EPA_XSTAMP_MASK 0x7ffffffffffull
 // Kernel-family timers (hipEventRecord on the context's stream).  Each record costs ~5.5 us of idle queue between two
@@ -373,9 +445,9 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
 //   2   the tip map is read only by the transform kernels of epa_dev_create, queued before any call can stage a span
 //       (SLOT_CLV_*, SLOT_SCALER_*: creation only, in the same way)
 //   6   the preplacement's status words are read (preplace_check_status; k_pack_readback through SelectPending::
-//       pre_status) inside the call that ran the preplacement; epa_dev_thorough and epa_dev_place_all keep statistics
-//       there in calls of their own, which run no preplacement (place_all clears ctx->d_status), and the chunk bodies
-//       keep theirs elsewhere (th_ctr, ChunkSlot::d_stats)
+//       pre_status) inside the call that ran the preplacement, through the pointer launch_preplace handed back to it;
+//       epa_dev_thorough and epa_dev_place_all keep statistics there in calls of their own, which run no preplacement,
+//       and the chunk bodies keep theirs elsewhere (th_ctr, ChunkSlot::d_stats)
 //   7   a Newton launch that carves its scratch here is queued on the bank's stream (or forked from it) behind the
 //       k_emit_pairs that reads the selection's bitmap, and a grow goes through hipFree, which waits for the device;
 //       the post-placement calls stage lengths / rule in calls of their own
@@ -399,14 +471,14 @@ enum EpaSlot : int {
   SLOT_SCALER_DIST = 4,
   SLOT_TABLE = 3,         // the Q x B preplacement table (host-side callers; the fused chunk body pads its rows)
   SLOT_RESULTS = 5,       // epa_result [n]
-  SLOT_PREPLACE = 6,      // launch_preplace: status words (ctx->d_status) | sort, groups, packed offsets
+  SLOT_PREPLACE = 6,      // launch_preplace: status words (handed back to the caller) | sort, groups, packed offsets
   SLOT_STATS = 6,         // epa_dev_thorough, epa_dev_place_all: the Newton launch's 256-byte statistics block
   SLOT_SELECT = 7,        // launch_select_begin: status block | bitmap or staging form
   SLOT_NEWTON = 7,        // thorough kernels: sumtable slabs of the windows too long for registers / LDS
   SLOT_CLASS_SORT = 8,    // launch_thorough: the pair order by class key
   SLOT_TREE_LNL = 9,      // epa_dev_tree_logl: per-workgroup partial sums
   SLOT_TH_TIMING = 9,     // TH_TIMING build of thorough_dna.hip: cycle stamps
-  SLOT_SEGMAX = 10,       // [Q][segp] segment maxima of the table (ctx->segmax)
+  SLOT_SEGMAX = 10,       // [Q][segp] segment maxima of the table (PreTable::segmax)
   SLOT_PACKED4 = 10,      // query codes in the 4-bit wire format, before the unpack into SLOT_CODES
   SLOT_ROWS_OUT = 11,     // epa_dev_place_all_rows: the filtered output of place_all
   SLOT_ROWS = 12,         //   and its rows
@@ -475,9 +547,11 @@ size_t epa_block_bytes(int s, uint32_t W, uint32_t blk, size_t* off2);
 void* epa_block_buffer(epa_ctx* ctx);
 int launch_build_lookup_block(epa_ctx* ctx, uint32_t b0, uint32_t nb, double* blk_lookup);
 int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_lookup, double* blk_lookup2);
-int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin,
-                    const uint32_t* d_span, uint32_t Q, double* d_lnl, uint32_t max_span);
-int preplace_check_status(epa_ctx* ctx);
+// fills t.lnl (and, after clearing them, t.segmax when given); *d_status: the call's status words in SLOT_PREPLACE,
+// [0 .. 4) the window validation -- for preplace_check_status after a synchronisation, or for the selection's read-back
+int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, uint32_t Q,
+                    const PreTable& t, uint32_t max_span, const uint32_t** d_status);
+int preplace_check_status(epa_ctx* ctx, const uint32_t* d_status);
 __attribute__((visibility("hidden"))) int preplace_window_error(epa_ctx* ctx, const uint32_t* st);   // the two window-validation words -> error code and text
 // one workgroup: exclusive scan of cnt[0 .. K) in place; with tip_row also *tip_total = the sum over the first K - 1
 // entries whose tip_row is not 0xffffffff (k_scan_counts, preplace.hip: the counting sort's and the selection's scan)
@@ -530,11 +604,12 @@ __attribute__((visibility("hidden"))) int launch_rell_kh(epa_ctx* ctx, const Ent
 // x_logw [Kx] | p_len [Kp] | p_logw [Kp]; d_grid: [n][Kx][Kp] or null
 int launch_marginal(epa_ctx* ctx, const EntryStage& e, const double* d_rule, uint32_t Kx, uint32_t Kp, double* d_marginal,
                     double* d_grid);
-// candidate selection (select.hip)
-int launch_select(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold,
+// candidate selection (select.hip) from table t; pre_status: the status words of the preplacement that wrote t (their
+// window validation travels in the read-back: select_check_status), or null when the table came from elsewhere
+int launch_select(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_status, uint32_t Q, double threshold,
                   epa_pair* d_pairs, uint64_t max_pairs, uint64_t* n_pairs,
                   const uint32_t* d_span = nullptr);  // d_span: also histogram the span classes
-int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold, epa_pair* d_pairs,
-                        uint64_t max_pairs, const uint32_t* d_span, uint32_t* rb, SelectPending* sp);
+int launch_select_begin(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_status, uint32_t Q, double threshold,
+                        epa_pair* d_pairs, uint64_t max_pairs, const uint32_t* d_span, uint32_t* rb, SelectPending* sp);
 int launch_select_end(epa_ctx* ctx, SelectPending* sp, uint64_t* n_pairs);
 int select_check_status(epa_ctx* ctx, const SelectPending* sp);

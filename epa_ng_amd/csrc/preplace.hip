@@ -1192,11 +1192,11 @@ int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_look
   return EPA_OK;
 }
 
-int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin,
-                    const uint32_t* d_span, uint32_t Q, double* d_lnl, uint32_t max_span) {
-  const uint32_t pitch = ctx->lnl_pitch ? ctx->lnl_pitch : ctx->B;  // row pitch of d_lnl in doubles
-  unsigned long long* const segmax = ctx->segmax;   // per-(query, 64-branch segment) maxima wanted by the fused chunk body, or null
-  const uint32_t segp = ctx->segp;
+int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, uint32_t Q,
+                    const PreTable& t, uint32_t max_span, const uint32_t** d_status) {
+  double* const d_lnl = t.lnl;
+  const uint32_t pitch = t.pitch, segp = t.segp;
+  unsigned long long* const segmax = t.segmax;
   const bool blocked = ctx->lookup_blocks;
   const bool pairs = ctx->s == 4 && (ctx->lookup2 || blocked) && !ctx->opt.preplace_generic;
   const bool sites = ctx->s == 20 && ctx->ncols == 24 && !ctx->opt.preplace_generic;
@@ -1235,11 +1235,9 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
   char* base = (char*)epa_scratch(ctx, SLOT_PREPLACE, layout(Carver{}));
   if (!base) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(preplace scratch)");
   layout(Carver{base});
-  ctx->d_status = status;
-  {   // status words + key counts, and the fused chunk body's segment maxima: one kernel
-    const size_t zb = ctx->segmax_zero_bytes;
-    ctx->segmax_zero_bytes = 0;
-    const int zr = epa_zero_async(ctx, status, (char*)iota - (char*)status, zb ? ctx->segmax : nullptr, zb);
+  *d_status = status;
+  {   // status words + key counts, and the segment maxima when they are wanted: one kernel
+    const int zr = epa_zero_async(ctx, status, (char*)iota - (char*)status, segmax, sizeof(unsigned long long) * (size_t)Q * segp);
     if (zr) return zr;
   }
   // wide slices for the pair path when a chunk puts few reads on a window start (see k_preplace_pairs)
@@ -1374,9 +1372,8 @@ int preplace_window_error(epa_ctx* ctx, const uint32_t* st) {
 }
 
 // reads the window-validation words written by k_make_groups (call after a stream sync)
-int preplace_check_status(epa_ctx* ctx) {
-  if (!ctx->d_status) return EPA_OK;
+int preplace_check_status(epa_ctx* ctx, const uint32_t* d_status) {
   uint32_t st[4];
-  EPA_HIP(ctx, hipMemcpy(st, ctx->d_status, sizeof(st), hipMemcpyDeviceToHost));
+  EPA_HIP(ctx, hipMemcpy(st, d_status, sizeof(st), hipMemcpyDeviceToHost));
   return preplace_window_error(ctx, st);
 }

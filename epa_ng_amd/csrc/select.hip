@@ -735,12 +735,12 @@ void emit_pairs(epa_ctx* ctx, const SelectPending* sp) {
 //          `rb` (pinned host memory for a truly asynchronous copy; 64 words) -- no synchronisation;
 //   end    waits for the stream, widens the staging rows and repeats on overflow (rare), then queues
 //          compaction, the stable sort into Work order and the key -> pair conversion.
-int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold, epa_pair* d_pairs,
-                        uint64_t max_pairs, const uint32_t* d_span, uint32_t* rb, SelectPending* sp) {
+int launch_select_begin(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_status, uint32_t Q, double threshold,
+                        epa_pair* d_pairs, uint64_t max_pairs, const uint32_t* d_span, uint32_t* rb, SelectPending* sp) {
   sp->have_hist = false;
   const uint32_t B = ctx->B;
-  const uint32_t pitch = ctx->lnl_pitch ? ctx->lnl_pitch : B;  // row pitch of d_lnl in doubles
-  if (!sp->rerun) sp->pre_status = (const uint32_t*)ctx->d_status;
+  const double* const d_lnl = t.lnl;
+  const uint32_t pitch = t.pitch;
   // selection rule of the context (epa_dev_set_heuristic); fixed: ceil(x * B) best, at least... none:
   // until_top_percent keeps ceil(x * B) elements, 0 for x == 0 (src/set_manipulators.cpp:82-88)
   const int mode = ctx->heur_mode;
@@ -786,7 +786,7 @@ int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double th
   layout(Carver{base});
   uint32_t* const counts = sp->counts;
   sp->wpr = wpr; sp->sort_bytes = sort_bytes;
-  sp->d_lnl = d_lnl; sp->Q = Q; sp->threshold = threshold; sp->d_pairs = d_pairs; sp->max_pairs = max_pairs;
+  sp->table = t; sp->pre_status = pre_status; sp->Q = Q; sp->threshold = threshold; sp->d_pairs = d_pairs; sp->max_pairs = max_pairs;
   sp->d_span = d_span; sp->cap = cap; sp->rb = rb;
   sp->ev_rb = nullptr; sp->d_rb = nullptr; sp->emitted = false; sp->queued_cls = -1;
   if (bm) {
@@ -801,13 +801,13 @@ int launch_select_begin(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double th
   auto select_rows = [&](const SelOut& so) -> bool {
     const int nr = (int)((B + 63) / 64);
     // A/B and test switch select_full_rows: the full-row kernels
-    if (so.bitmap && ctx->segmax && !ctx->opt.select_full_rows && mode == 0 && threshold < 1.0 && nr <= 64) {
+    if (so.bitmap && t.segmax && !ctx->opt.select_full_rows && mode == 0 && threshold < 1.0 && nr <= 64) {
       // band widths of the segment test (see k_select_seg): conservative margins, so the host's log is as good as the device's
       const double band_x = 1.0 - std::log((1.0 - threshold) / (double)B);
       const double band_t = std::max(band_x, std::log((double)B) + 38.0);
       constexpr uint32_t sel_grid = 16;   // workgroups per CU of the persistent selection grid
       const dim3 grid_seg(std::min<uint32_t>((Q + 3) / 4, (uint32_t)ctx->n_cu * sel_grid));
-      hipLaunchKernelGGL(k_select_seg<8>, grid_seg, dim3(256), 0, ctx->stream, d_lnl, ctx->segmax, ctx->segp, Q, B, pitch, threshold,
+      hipLaunchKernelGGL(k_select_seg<8>, grid_seg, dim3(256), 0, ctx->stream, d_lnl, t.segmax, t.segp, Q, B, pitch, threshold,
                          band_x, band_t, so, counts, status, d_span, ctx->s, d_span ? status + SEL_HIST : nullptr);
       return d_span != nullptr;
     }
@@ -875,9 +875,7 @@ int launch_select_end(epa_ctx* ctx, SelectPending* sp, uint64_t* n_pairs) {
     if (overflow && !sp->bitmap) {  // some query selected more candidates than the staging row holds: widen, redo
       if (sp->cap >= B) return epa_fail(ctx, EPA_ERR_HIP, "select_candidates: staging overflow");
       ctx->select_cap = std::min<uint32_t>(B, std::max(sp->cap * 4, overflow));
-      sp->rerun = true;    // keeps this chunk's preplacement status pointer
-      int rc = launch_select_begin(ctx, sp->d_lnl, Q, sp->threshold, sp->d_pairs, sp->max_pairs, sp->d_span, sp->rb, sp);
-      sp->rerun = false;
+      int rc = launch_select_begin(ctx, sp->table, sp->pre_status, Q, sp->threshold, sp->d_pairs, sp->max_pairs, sp->d_span, sp->rb, sp);
       if (rc) return rc;
       continue;
     }
@@ -918,11 +916,11 @@ int select_check_status(epa_ctx* ctx, const SelectPending* sp) {
   return sp->have_status ? preplace_window_error(ctx, sp->rb + RB_WINDOW) : EPA_OK;
 }
 
-int launch_select(epa_ctx* ctx, const double* d_lnl, uint32_t Q, double threshold,
+int launch_select(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_status, uint32_t Q, double threshold,
                   epa_pair* d_pairs, uint64_t max_pairs, uint64_t* n_pairs, const uint32_t* d_span) {
   uint32_t rb[64] = {};
   SelectPending sp;
-  int rc = launch_select_begin(ctx, d_lnl, Q, threshold, d_pairs, max_pairs, d_span, rb, &sp);
+  int rc = launch_select_begin(ctx, t, pre_status, Q, threshold, d_pairs, max_pairs, d_span, rb, &sp);
   if (rc) return rc;
   return launch_select_end(ctx, &sp, n_pairs);
 }
