@@ -458,9 +458,10 @@ __device__ __forceinline__ void pair_symbols(uint32_t e, uint32_t& s0, uint32_t&
   else { s0 = 4 + (e - 24) / NSYM; s1 = (e - 24) % NSYM; }
 }
 
-// state-set code (4-bit mask) -> symbol; 6 = any other ambiguity code (generic kernel)
+// state-set code (4-bit mask) -> symbol; 6 = any other ambiguity code (generic kernel).  Code 0 is a gap inside the
+// window: its lookup column has N's state set (column_mask) and so N's bits, and it takes N's symbol.
 __device__ __forceinline__ uint32_t dna_sym(uint32_t code) {
-  if (code == 15) return 4;
+  if (code == 15 || code == 0) return 4;
   if (code == 1 || code == 2 || code == 4 || code == 8) return (uint32_t)__ffs((int)code) - 1;
   return 6;
 }
@@ -498,7 +499,7 @@ struct PairTab {
       const uint32_t c[2] = {i >> 4, i & 15u};
       uint32_t s[2] = {0, 0};
       for (int k = 0; k < 2; ++k)
-        s[k] = c[k] == 15 ? 4u : c[k] == 1 ? 0u : c[k] == 2 ? 1u : c[k] == 4 ? 2u : c[k] == 8 ? 3u : 6u;   // = dna_sym
+        s[k] = (c[k] == 15 || c[k] == 0) ? 4u : c[k] == 1 ? 0u : c[k] == 2 ? 1u : c[k] == 4 ? 2u : c[k] == 8 ? 3u : 6u;   // = dna_sym
       const bool rare = s[0] > 4 || s[1] > 4;
       const uint32_t s0 = s[0] > 5 ? 5u : s[0], s1 = s[1] > 5 ? 5u : s[1];
       const uint32_t e = (s0 < 4 && s1 < 4) ? s0 * 4 + s1 : s0 < 4 ? 16 + s0 * 2 + (s1 - 4) : 24 + (s0 - 4) * NSYM + s1;   // = pair_entry

@@ -23,6 +23,7 @@ import epa_ng_amd as epa
 from epa_ng_amd import hostlib, synth
 from golden_util import GOLDEN, load_case
 from oracle_lib import Oracle
+from preplace_ref import _seg_values
 
 import large_tree_gen as gen
 
@@ -127,16 +128,6 @@ def test_preplace_table_dna_bit_identical(n_tips):
         assert ev.kernel_ms("lookup") < 0.0
         ev.close()
     evr.close()
-
-
-def _seg_values(keys):
-    """order-preserving keys of the segment maxima (include/epa_dev.h) -> doubles; 0 (not written) -> NaN"""
-    k = np.asarray(keys, np.uint64)
-    pos = (k >> np.uint64(63)) == 1
-    u = np.where(pos, k & np.uint64(0x7fffffffffffffff), ~k)
-    v = u.view(np.float64).copy()
-    v[k == 0] = np.nan
-    return v
 
 
 @pytest.mark.parametrize("n_tips", [96, 512])      # B = 189 and 1021
