@@ -19,7 +19,8 @@ __all__ = ["EpaError", "dev_lib", "device_count", "encode_queries", "Evaluator",
            "RESULT_DTYPE", "ROW_DTYPE", "DEV_SO", "Packed4", "pack_codes_4bit", "unpack_codes_4bit", "Comm",
            "comm_unique_id", "mapped_rccl_path", "comm_set_library", "comm_library_path", "comm_set_default_timeout",
            "pci_id_str", "FLAG_LOOKUP_BLOCKS", "FLAG_LOOKUP_AUTO", "LOOKUP_RESIDENT", "LOOKUP_BLOCKS", "ERR_NO_MEMORY",
-           "footprint", "lookup_plan", "set_mem_cap", "quadrature_legendre01", "quadrature_laguerre", "posterior_rule"]
+           "footprint", "lookup_plan", "set_mem_cap", "quadrature_legendre01", "quadrature_laguerre", "posterior_rule",
+           "profile_from_phred"]
 
 # lookup layout of a context (include/epa_dev.h: EPA_FLAG_LOOKUP_*, EPA_LOOKUP_*, EPA_ERR_NO_MEMORY)
 FLAG_LOOKUP_BLOCKS = 0x40
@@ -126,6 +127,21 @@ def dev_lib():
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
+        # profile queries: (prof, stride) in place of the codes
+        L.epa_dev_preplace_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.c_void_p]
+        L.epa_dev_thorough_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(_Stats)]
+        L.epa_dev_score_at_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.epa_dev_site_lnl_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                               C.c_void_p]
+        L.epa_dev_place_chunk_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                  C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(_Stats)]
+        L.epa_profile_from_phred.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
         L.epa_quadrature_legendre01.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.epa_quadrature_laguerre.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.epa_dev_set_heuristic.argtypes = [C.c_void_p, C.c_int, C.c_double]
@@ -338,6 +354,28 @@ def encode_queries(states, seqs, premasking=True, aa_x_as_n=False, compact=False
     check(L.epa_encode_queries_compact(states, W, Q, arr, int(premasking), int(aa_x_as_n), stride,
                                        codes.ctypes.data, wb.ctypes.data, ws.ctypes.data, C.byref(bad)))
     return codes, wb, ws
+
+
+def profile_from_phred(states, codes, phred, win_span, out=None):
+    """compact code rows [Q][stride] + Phred scores [Q][stride] (the scores themselves, 0 .. 93) -> profile rows float64
+    [Q][stride][states] (epa_profile_from_phred; needs no device): a pure-state code with score s gets 1 - eps at the
+    called state and eps / (states - 1) elsewhere, eps = min(10^(-s / 10), (states - 1) / states); any other code keeps
+    its 0/1 state set.  Rows beyond a query's span are left as they are (zeros when `out` is None)."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    phred = np.ascontiguousarray(phred, np.uint8)
+    win_span = np.ascontiguousarray(win_span, np.uint32)
+    if codes.ndim != 2 or phred.shape != codes.shape or len(win_span) != codes.shape[0]:
+        raise ValueError("profile_from_phred: codes and phred must be [Q][stride] arrays of one shape, win_span [Q]")
+    Q, stride = codes.shape
+    if out is None:
+        out = np.zeros((Q, stride, states), np.float64)
+    assert out.shape == (Q, stride, states) and out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+    L = dev_lib()
+    rc = L.epa_profile_from_phred(states, Q, stride, codes.ctypes.data, phred.ctypes.data, win_span.ctypes.data,
+                                  out.ctypes.data)
+    if rc:
+        raise EpaError(rc, (L.epa_dev_last_error(None) or b"").decode())
+    return out
 
 
 class Evaluator:
@@ -603,6 +641,90 @@ class Evaluator:
                                            int(replicates), int(seed), _ptr(out.get("p_kh")), _ptr(out.get("p_wkh")),
                                            _ptr(out.get("p_wsh"))))
         return out
+
+    # ---- profile queries (include/epa_dev.h, "Profile queries"): prof is float64 [Q][stride][states] -- numpy on the
+    # host or a torch cuda tensor -- holding the per-state likelihoods of every window position; the rows from a
+    # query's span up to the stride are padding
+    @staticmethod
+    def _prof(prof):
+        if isinstance(prof, np.ndarray):
+            prof = np.ascontiguousarray(prof, dtype=np.float64)
+        return prof, int(prof.shape[1])
+
+    def _stats(self, st):
+        self.last_stats = {"pairs": st.pairs, "rounds": st.rounds, "newton_evals": st.newton_evals, "reverts": st.reverts}
+
+    def preplace_profile(self, prof, win_begin, win_span, Q=None, out=None):
+        """preplace() for profile rows (epa_dev_preplace_profile) -> lnl [Q][B]"""
+        Q = len(win_begin) if Q is None else Q
+        prof, stride = self._prof(prof)
+        if out is None:
+            out = np.empty((Q, self.B), np.float64)
+        self._check(self.L.epa_dev_preplace_profile(self.h, _ptr(prof), stride, _ptr(win_begin), _ptr(win_span), Q, _ptr(out)))
+        return out
+
+    def thorough_profile(self, pairs, prof, win_begin, win_span, Q=None, n_pairs=None, out=None):
+        """thorough() for profile rows, on the general Newton kernel (epa_dev_thorough_profile) -> RESULT_DTYPE array"""
+        Q = len(win_begin) if Q is None else Q
+        n = len(pairs) if n_pairs is None else n_pairs
+        prof, stride = self._prof(prof)
+        if out is None:
+            out = np.empty(n, RESULT_DTYPE)
+        st = _Stats()
+        self._check(self.L.epa_dev_thorough_profile(self.h, _ptr(pairs), n, _ptr(prof), stride, _ptr(win_begin), _ptr(win_span),
+                                                    Q, _ptr(out), C.byref(st)))
+        self._stats(st)
+        return out
+
+    def _profile_entries(self, pairs, pendant, distal, proximal, win_begin, Q):
+        host = (np.ndarray, list, tuple)
+        pendant, distal, proximal = (np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, host) else a
+                                     for a in (pendant, distal, proximal))
+        return len(pairs), (len(win_begin) if Q is None else Q), pendant, distal, proximal
+
+    def score_at_profile(self, pairs, pendant, distal, prof, win_begin, win_span, proximal=None, Q=None, out=None):
+        """score_at() for profile rows (epa_dev_score_at_profile) -> float64 [n]"""
+        n, Q, pendant, distal, proximal = self._profile_entries(pairs, pendant, distal, proximal, win_begin, Q)
+        prof, stride = self._prof(prof)
+        if out is None:
+            out = np.empty(n, np.float64)
+        self._check(self.L.epa_dev_score_at_profile(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                                    _ptr(prof), stride, _ptr(win_begin), _ptr(win_span), Q, _ptr(out)))
+        return out
+
+    def site_lnl_profile(self, pairs, pendant, distal, prof, win_begin, win_span, proximal=None, pitch=None, Q=None, out=None):
+        """site_lnl() for profile rows (epa_dev_site_lnl_profile) -> float64 [n][pitch]; pitch None: the longest window"""
+        n, Q, pendant, distal, proximal = self._profile_entries(pairs, pendant, distal, proximal, win_begin, Q)
+        prof, stride = self._prof(prof)
+        if pitch is None:
+            pitch = int(np.max(np.asarray(win_span)[:Q])) if Q else 0
+        if out is None:
+            out = np.empty((n, int(pitch)), np.float64)
+        self._check(self.L.epa_dev_site_lnl_profile(self.h, _ptr(pairs), _ptr(pendant), _ptr(distal), _ptr(proximal), n,
+                                                    _ptr(prof), stride, _ptr(win_begin), _ptr(win_span), Q, int(pitch),
+                                                    _ptr(out)))
+        return out
+
+    def place_chunk_profile(self, prof, win_begin, win_span, Q=None, threshold=0.99999, max_pairs=None, pairs_out=None,
+                            results_out=None):
+        """preplace_profile -> the context's heuristic -> thorough_profile on the device (epa_dev_place_chunk_profile).
+        Returns (pairs, results) numpy arrays, or n_pairs when device buffers are supplied."""
+        Q = len(win_begin) if Q is None else Q
+        if max_pairs is None:
+            max_pairs = Q * 64
+        prof, stride = self._prof(prof)
+        host = pairs_out is None
+        if host:
+            pairs_out = np.empty(max_pairs, PAIR_DTYPE)
+            results_out = np.empty(max_pairs, RESULT_DTYPE)
+        n, st = C.c_uint64(0), _Stats()
+        self._check(self.L.epa_dev_place_chunk_profile(self.h, _ptr(prof), stride, _ptr(win_begin), _ptr(win_span), Q,
+                                                       threshold, _ptr(pairs_out), _ptr(results_out), max_pairs,
+                                                       C.byref(n), C.byref(st)))
+        self._stats(st)
+        if host:
+            return pairs_out[:n.value], results_out[:n.value]
+        return n.value
 
     def set_heuristic(self, mode="dynamic", param=0.0):
         """selection rule of select() / place_chunk(): "dynamic" (the call's threshold), "fixed"

@@ -430,6 +430,8 @@ static uint32_t column_mask(int s, int col) {
   return (1u << 20) - 1;  // '-' and 'X'
 }
 
+uint32_t epa_column_mask(int s, int col) { return column_mask(s, col); }
+
 // upper limit on the host threads of the query encoder (0 = hardware concurrency, at most 32)
 static std::atomic<unsigned> g_encode_threads{0};
 extern "C" void epa_encode_set_threads(unsigned n) { g_encode_threads.store(n, std::memory_order_relaxed); }
@@ -737,6 +739,7 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
   if (ctx->blen) (void)hipFree(ctx->blen);
   if (ctx->lookup) (void)hipFree(ctx->lookup);
   if (ctx->lookup2) (void)hipFree(ctx->lookup2);
+  if (ctx->prof_tab) (void)hipFree(ctx->prof_tab);
   for (void* p : ctx->blk_buf) if (p) (void)hipFree(p);
   for (auto& v : ctx->blk_ev) for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e);
   if (ctx->th_ctr) (void)hipFree(ctx->th_ctr);
@@ -1711,6 +1714,8 @@ struct EntryArgs {
   const uint8_t* q_codes;
   const uint32_t *win_begin, *win_span;
   uint32_t Q;
+  const double* prof = nullptr;   // profile queries (epa_dev_score_at_profile, _site_lnl_profile): rows in place of q_codes
+  uint32_t prof_stride = 0;
 };
 
 // One call of the seven: begin(), output() for every output, run()
@@ -1731,7 +1736,8 @@ struct EntryCall {
     const uint32_t* hb = host_view(a.win_begin, a.Q, hb_buf, ctx->stream);
     st.h_span = host_view(a.win_span, a.Q, hs_buf, ctx->stream);
     if (!hb || !st.h_span) return epa_fail(ctx, EPA_ERR_HIP, "cannot read window arrays");
-    int rc = check_windows(ctx, hb, st.h_span, a.Q, &st.max_span, true);   // an empty window is the empty sum: lnL 0
+    // an empty window is the empty sum: lnL 0 (profile rows: the windows are checked with the rows, below)
+    int rc = a.prof ? (int)EPA_OK : check_windows(ctx, hb, st.h_span, a.Q, &st.max_span, true);
     if (rc) return rc;
     // host arrays are validated (device arrays are the caller's responsibility)
     const bool hp = !epa_is_device_ptr(a.pairs), hpe = a.pendant && !epa_is_device_ptr(a.pendant);
@@ -1752,14 +1758,22 @@ struct EntryCall {
     auto lengths = [&](int slot, const double* t) { return t ? (const double*)epa_to_device(ctx, slot, t, sizeof(double) * a.n) : nullptr; };
     st.n = a.n;
     st.Q = a.Q;
-    st.d_codes = epa_codes_to_device(ctx, a.q_codes, a.Q);
     st.d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, a.win_begin, sizeof(uint32_t) * a.Q);
     st.d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, a.win_span, sizeof(uint32_t) * a.Q);
+    if (a.prof) {
+      if (!st.d_span) return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
+      const double* d_prof = nullptr;
+      rc = epa_profile_stage(ctx, who, a.prof, a.prof_stride, hb, st.h_span, st.d_span, a.Q, true, &st.max_span, &d_prof, &st.d_qe);
+      if (rc) return rc;
+      st.qe_stride = a.prof_stride;
+    } else {
+      st.d_codes = epa_codes_to_device(ctx, a.q_codes, a.Q);
+    }
     st.d_pairs = (const epa_pair*)epa_to_device(ctx, SLOT_PAIRS, a.pairs, sizeof(epa_pair) * a.n);
     st.d_pen = lengths(SLOT_PENDANT, a.pendant);
     st.d_dis = lengths(SLOT_DISTAL, a.distal);
     st.d_prx = lengths(SLOT_PROXIMAL, a.proximal);
-    if (!st.d_codes || !st.d_begin || !st.d_span || !st.d_pairs || (a.pendant && !st.d_pen) || (a.distal && !st.d_dis) ||
+    if ((!st.d_codes && !st.d_qe) || !st.d_begin || !st.d_span || !st.d_pairs || (a.pendant && !st.d_pen) || (a.distal && !st.d_dis) ||
         (a.proximal && !st.d_prx))
       return epa_fail(ctx, EPA_ERR_HIP, std::string(who) + " input upload failed");
     return EPA_OK;
@@ -1771,7 +1785,7 @@ struct EntryCall {
   // its stream ids uploaded.
   template <class Checks>
   int begin(std::initializer_list<const void*> need, const uint64_t* const* stream_id, Checks own_checks) {
-    bool null_arg = !ctx || (a.n && (!a.pairs || !a.q_codes || !a.win_begin || !a.win_span));
+    bool null_arg = !ctx || (a.n && (!a.pairs || (!a.q_codes && !a.prof) || !a.win_begin || !a.win_span));
     for (const void* p : need) null_arg |= a.n && !p;
     if (null_arg) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
     int rc = own_checks();
@@ -1845,6 +1859,35 @@ extern "C" int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const doubl
     return epa_fail(ctx, EPA_ERR_INVALID_ARG, "site_lnl: pitch " + std::to_string(pitch) + " is smaller than the longest window (" +
                                                   std::to_string(need) + ")");
   if (pitch == 0) return EPA_OK;   // every window is empty: there is nothing to write
+  c.output(site_lnl, sizeof(double) * (size_t)n * pitch);
+  return c.run([&] { return launch_site_lnl(ctx, c.st, nullptr, n, pitch, c.dev<double>(0), SITES_PAD | SITES_TIMED); });
+}
+
+// the two calls above on profile queries: rows of per-state likelihoods in place of the column codes (profile.hip)
+extern "C" int epa_dev_score_at_profile(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                        const double* proximal, uint64_t n, const double* prof, uint32_t stride,
+                                        const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, double* lnl) {
+  EntryCall c{ctx, "score_at_profile", {pairs, pendant, distal, proximal, n, nullptr, win_begin, win_span, Q, prof, stride}};
+  int rc = c.begin({pendant, distal, lnl}, nullptr, [] { return EPA_OK; });
+  if (rc || c.empty) return rc;
+  c.output(lnl, sizeof(double) * n);
+  return c.run([&] { return launch_score_at(ctx, c.st, c.dev<double>(0)); });
+}
+
+extern "C" int epa_dev_site_lnl_profile(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                                        const double* proximal, uint64_t n, const double* prof, uint32_t stride,
+                                        const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, uint32_t pitch,
+                                        double* site_lnl) {
+  EntryCall c{ctx, "site_lnl_profile", {pairs, pendant, distal, proximal, n, nullptr, win_begin, win_span, Q, prof, stride}};
+  int rc = c.begin({pendant, distal, site_lnl}, nullptr, [] { return EPA_OK; });
+  if (rc || c.empty) return rc;
+  uint32_t need = 0;   // as epa_dev_site_lnl: the pitch must hold the longest window among the entries' queries
+  if (!epa_is_device_ptr(pairs)) for (uint64_t i = 0; i < n; ++i) need = std::max(need, c.st.h_span[pairs[i].seq_id]);
+  else need = c.st.max_span;
+  if (pitch < need)
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "site_lnl_profile: pitch " + std::to_string(pitch) + " is smaller than the longest window (" +
+                                                  std::to_string(need) + ")");
+  if (pitch == 0) return EPA_OK;
   c.output(site_lnl, sizeof(double) * (size_t)n * pitch);
   return c.run([&] { return launch_site_lnl(ctx, c.st, nullptr, n, pitch, c.dev<double>(0), SITES_PAD | SITES_TIMED); });
 }
@@ -2271,6 +2314,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "rell_tests")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_TESTS]][epa_ctx::T_RELL_TESTS];
   else if (!strcmp(which, "rell_au")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_AU]][epa_ctx::T_RELL_AU];
   else if (!strcmp(which, "rell_kh")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_KH]][epa_ctx::T_RELL_KH];
+  else if (!strcmp(which, "preplace_profile")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_PREPLACE_PROFILE]][epa_ctx::T_PREPLACE_PROFILE];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

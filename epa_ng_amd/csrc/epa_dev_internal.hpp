@@ -320,6 +320,9 @@ struct epa_ctx {
   uint8_t* tipmask = nullptr;
   double* tipd = nullptr;
   bool lookup_built = false;
+  // profile queries (profile.hip): [B][s + 1][W] per (branch, site) exp(T_m - T_any) of the lookup table's pure-state
+  // columns and, as component s, T_any itself; derived from `lookup` on the first profile preplacement (resident layout)
+  double* prof_tab = nullptr;
   // Blocked lookup layout (EPA_FLAG_LOOKUP_BLOCKS): lookup / lookup2 / refI / resc0 stay null; every scratch bank that
   // runs a preplacement owns one block buffer -- lookup [blk][W][ncols], then (4 states) lookup2 [blk][2][ceil(W/2)][36]
   // -- rebuilt block by block inside launch_preplace (allocated exactly, on first use: epa_block_buffer)
@@ -331,7 +334,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 21;   // named by EpaSlot below
+  static constexpr int N_SCRATCH = 23;   // named by EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -356,7 +359,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, N_TIMERS = 10 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, N_TIMERS = 11 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -495,6 +498,8 @@ enum EpaSlot : int {
   SLOT_RELL_TESTS = 18,   // rell_tests: [L n | T n | weight sums n | SH counts n]
   SLOT_RELL_AU = 19,      // rell_au: win counters [scale][n]
   SLOT_RELL_KH = 20,      // rell_kh: [L n | L_b - L n | L_k* - L n | T n | k* n | counters 3 n | matrix offsets | b | scale matrices | spilled scores]
+  SLOT_PROFILE = 21,      // profile calls (profile.hip): the rows [Q][stride][s] of a call whose rows live on the host
+  SLOT_PROFILE_EIGEN = 22,//   and [fault key, 256 bytes | the rows in the eigenbasis [Q][stride][s]] (k_profile_eigen)
 };
 
 // The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,
@@ -506,6 +511,9 @@ struct EntryStage {
   const uint8_t* d_codes = nullptr;
   const uint32_t *d_begin = nullptr, *d_span = nullptr;
   const uint32_t* h_span = nullptr;   // the host's view of win_span
+  // profile queries: eigen-space rows [Q][qe_stride][s] in place of d_codes (null: coded queries)
+  const double* d_qe = nullptr;
+  uint32_t qe_stride = 0;
   uint32_t Q = 0;
   uint32_t max_span = 0;              // the longest window of the Q queries
 };
@@ -571,11 +579,20 @@ int launch_thorough_aa(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* d_
 int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, const uint8_t* d_codes,
                             const uint32_t* d_begin, const uint32_t* d_span, uint32_t max_span,
                             epa_result* d_out, unsigned long long* d_stats,
-                            const uint32_t* d_order = nullptr, bool caller_times = false);   // caller_times: a per-class launch inside launch_thorough's timed region
+                            const uint32_t* d_order = nullptr, bool caller_times = false,   // caller_times: a per-class launch inside launch_thorough's timed region
+                            const double* d_qe = nullptr, uint32_t qe_stride = 0);   // d_qe: profile queries, eigen-space rows [Q][qe_stride][s] in place of d_codes
 int launch_thorough_aa_mfma(epa_ctx* ctx, const epa_pair* d_pairs, const uint32_t* d_order, uint64_t n_pairs,
                             const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span,
                             uint32_t max_span, epa_result* d_out, unsigned long long* d_stats);
-// lnL of the entries at their lengths (score_at.hip)
+// lookup column -> state set (epa_dev.hip)
+__attribute__((visibility("hidden"))) uint32_t epa_column_mask(int s, int col);
+// Profile queries (profile.hip): the rows of a call checked (host rows here, device rows by the kernel's fault key; the
+// first offending query and position are named), staged and brought to the eigenbasis.  hb / hs: the host's view of the
+// windows, checked against the width and the stride; *d_prof: the rows in HBM, *d_qe: their eigen-space image
+__attribute__((visibility("hidden"))) int epa_profile_stage(epa_ctx* ctx, const char* who, const double* prof, uint32_t stride,
+                                                            const uint32_t* hb, const uint32_t* hs, const uint32_t* d_span, uint32_t Q,
+                                                            bool allow_empty, uint32_t* max_span, const double** d_prof, const double** d_qe);
+// lnL of the entries at their lengths (score_at.hip); e.d_qe set: profile queries
 int launch_score_at(epa_ctx* ctx, const EntryStage& e, double* d_lnl);
 // per-site log-likelihoods of the same entries (k_score_at<S, true>): row i of d_rows [n_rows][pitch] takes entry
 // d_order[i] (null: entry i), columns [0, span).  SITES_PAD: the columns from the span up to the pitch are written as

@@ -103,7 +103,8 @@ int epa_host_parse_model(const char* file, char* out, size_t cap) {
 long epa_host_premask(const char* ref_file, const char* query_file, uint8_t* mask, size_t cap) {
   long sites = -1;
   if (guarded([&] {
-        epa::MSA_Info r = epa::MSA_Info::from_file(ref_file), q = epa::MSA_Info::from_file(query_file);
+        epa::MSA_Info r = epa::MSA_Info::from_file(ref_file);
+        epa::MSA_Info q = epa::is_fastq_file(query_file) ? epa::fastq_msa_info(query_file) : epa::MSA_Info::from_file(query_file);
         epa::MSA_Info::or_mask(r, q);
         if (r.sites() > cap) throw std::runtime_error{"epa_host_premask: mask buffer too small"};
         std::memcpy(mask, r.gap_mask().data(), r.sites());
@@ -111,6 +112,24 @@ long epa_host_premask(const char* ref_file, const char* query_file, uint8_t* mas
       }))
     return -1;
   return sites;
+}
+
+// test hook of the aligned-FASTQ reader: every record of `in_file` written again to `out_file` as the reader holds it
+// (@name, read, +, qualities).  Returns the number of records, -1 on error (epa_host_last_error names the record).
+long epa_host_fastq_copy(const char* in_file, const char* out_file) {
+  long n = -1;
+  if (guarded([&] {
+        if (!epa::is_fastq_file(in_file)) throw std::runtime_error{std::string(in_file) + ": not a FASTQ file (no leading '@')"};
+        epa::Fastq_Stream in(in_file);
+        std::vector<epa::Fastq_Record> recs;
+        while (in.read_next(recs, 2)) {}
+        std::ofstream os(out_file);
+        for (const auto& r : recs) os << '@' << r.header << '\n' << r.sequence << "\n+\n" << r.quality << '\n';
+        if (!os.flush()) throw std::runtime_error{std::string("cannot write ") + out_file};
+        n = (long)recs.size();
+      }))
+    return -1;
+  return n;
 }
 
 // rooted input tree: placement (edge, distal) on the unrooted working tree -> on the rooted tree

@@ -16,6 +16,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdint>
+#include <fstream>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -390,6 +391,24 @@ private:
   bool predict_ok_ = true;
   char up_[256];
 };
+// Aligned FASTQ (quality-aware queries, place_profile.cpp): four lines per record -- '@' name, the aligned read
+// (alignment width, '-' gaps), '+', one Phred+33 quality character per alignment column (ignored wherever the read shows
+// no pure state).  A file is taken as FASTQ when its first character is '@'.
+bool is_fastq_file(const std::string& path);
+struct Fastq_Record { std::string header, sequence, quality; };
+class Fastq_Stream {
+public:
+  explicit Fastq_Stream(const std::string& path);
+  // appends up to max_records records to `out` (reads upper-cased); returns how many (0 = end of file).  Throws, naming
+  // the record, on a read and a quality line of different widths, a quality character outside '!' .. '~', a broken record
+  size_t read_next(std::vector<Fastq_Record>& out, size_t max_records);
+private:
+  std::string path_;
+  std::ifstream in_;
+  size_t records_ = 0;
+};
+MSA_Info fastq_msa_info(const std::string& path);   // MSA_Info::from_file for an aligned FASTQ
+
 // v in fixed notation with `precision` digits, correctly rounded (= printf %.*f); returns the length written to buf
 size_t format_fixed(char* buf, size_t cap, double v, unsigned int precision);
 // optional row fields behind pendant_length, written in this order and named in "fields": kJplaceRell
@@ -507,6 +526,7 @@ struct Run_Stats {
   // lookup layout of the device context(s): "resident" or "blocks", branches per block (0: resident)
   std::string lookup_mode = "resident";
   uint32_t lookup_block = 0;
+  std::string query_kind = "coded";   // "profile": a FASTQ query, placed as per-site state likelihoods (place_profile.cpp)
 };
 // Reads per device chunk that fit a device: `slots` pipeline slots each own a preplacement table of
 // Q x pitch(branches) x 8 bytes (pitch: the row rounded up to 64 bytes), plus a quarter of that for codes, bitmap and
@@ -534,6 +554,12 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
 // device is created; any error leaves no output file.
 Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::string& query_file, const MSA_Info& msa_info,
                   const std::string& outdir, const Options& options, const std::string& invocation, int device = 0);
+
+// -q reads.fastq: every chunk of an aligned FASTQ premasked (both lines), encoded, turned into rows of state
+// likelihoods (epa_profile_from_phred) and placed by epa_dev_place_chunk_profile; LWR, filter and jplace as simple_mpi.
+// Synchronous, one device, the resident lookup layout; --no-heur and --memsave on are refused
+Run_Stats place_profile_file(const Tree& tree, const std::string& query_file, const MSA_Info& msa_info, const std::string& outdir,
+                             const Options& options, const std::string& invocation, int device = 0);
 
 // one process per GPU: rank's contiguous slice of the query file on `device`, results gathered to rank 0
 // over the product library's RCCL gather (place_ranks.cpp; src/net/epa_mpi_util.cpp:10-30)

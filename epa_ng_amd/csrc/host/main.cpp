@@ -19,7 +19,11 @@ static void usage() {
       "epa-ng-amd - Evolutionary Placement Algorithm, MI355X placement evaluator\n"
       "  -t,--tree FILE        reference tree (newick, unrooted or rooted)\n"
       "  -s,--ref-msa FILE     reference MSA (fasta)\n"
-      "  -q,--query FILE       query MSA (fasta, aligned to the reference)\n"
+      "  -q,--query FILE       query MSA (fasta, aligned to the reference), or an aligned FASTQ (leading '@'): per record\n"
+      "                        the aligned read and one Phred+33 quality character per alignment column.  Every base then\n"
+      "                        enters as state likelihoods (called state 1 - e, every other state e / (states - 1), e = 10^(-Q / 10)) instead\n"
+      "                        of a hard call: one device, chunk by chunk; --devices a,b / --rank / --world / --no-heur /\n"
+      "                        --rescore / --memsave on are refused with it\n"
       "  -m,--model STR|FILE   model descriptor, e.g. GTR{..}+FU{..}+G4{a} (default GTR+G), or a RAxML 8\n"
       "                        info / RAxML-NG .bestModel / IQ-TREE report file\n"
       "  -w,--outdir DIR       output directory (default ./)\n"
@@ -90,7 +94,8 @@ int main(int argc, char** argv) {
   std::vector<std::string> placing_flags;   // flags that steer heuristic, optimiser or filter: meaningless with --rescore
   Options opt;
   int device = 0;
-  bool device_given = false, rell_given = false, prior_given = false, nodes_given = false;
+  bool device_given = false, rell_given = false, prior_given = false, nodes_given = false, rank_given = false;
+  std::string diag_flag;   // --host-heuristic / --device-min-chunk: steer the coded chunk loop only
   std::vector<int> devices;
   // one process per GPU (place_ranks.cpp): --rank / --world / --comm-file, or what torchrun / mpirun export
   auto env_int = [](const char* a, const char* b, int dflt) {
@@ -150,7 +155,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--precision") opt.precision = (unsigned)std::stoul(need(i));
     else if (a == "--chunk-size") { opt.chunk_size = (unsigned)std::stoul(need(i)); opt.chunk_size_given = true; }
-    else if (a == "--device-min-chunk") { opt.device_min_chunk = (unsigned)std::stoul(need(i)); opt.device_min_chunk_given = true; }
+    else if (a == "--device-min-chunk") { diag_flag = a; opt.device_min_chunk = (unsigned)std::stoul(need(i)); opt.device_min_chunk_given = true; }
     else if (a == "--no-pre-mask") opt.premasking = false;
     else if (a == "--raxml-blo") opt.sliding_blo = false;   // src/main.cpp:239-242
     else if (a == "--rate-scalers") {                       // src/main.cpp:248-250,399-407
@@ -183,15 +188,15 @@ int main(int argc, char** argv) {
       std::string tok;
       while (std::getline(ls, tok, ',')) if (!tok.empty()) devices.push_back(std::stoi(tok));
     }
-    else if (a == "--rank") rank = std::stoi(need(i));
-    else if (a == "--world") world = std::stoi(need(i));
-    else if (a == "--comm-file") comm_file = need(i);
+    else if (a == "--rank") { rank = std::stoi(need(i)); rank_given = true; }
+    else if (a == "--world") { world = std::stoi(need(i)); rank_given = true; }
+    else if (a == "--comm-file") { comm_file = need(i); rank_given = true; }
     else if (a == "--comm-nonce") opt.comm_nonce = need(i);
     else if (a == "--comm-probe-seconds") opt.comm_probe_seconds = std::stod(need(i));
     else if (a == "--comm-timeout") opt.comm_timeout_seconds = std::stod(need(i));
     else if (a == "--comm-rows-per-read") opt.comm_rows_per_read = std::stoi(need(i));
     else if (a == "--comm-self-send") opt.comm_self_send = true;       // test hook
-    else if (a == "--host-heuristic") opt.host_heuristic = true;       // diagnostics
+    else if (a == "--host-heuristic") { diag_flag = a; opt.host_heuristic = true; }   // diagnostics
     else if (a == "--no-pipeline") opt.no_pipeline = true;
     else if (a == "--stats-json") stats_json = need(i);
     else if (a == "--redo" || a == "--verbose") {}
@@ -261,6 +266,24 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  // an aligned FASTQ query runs the profile chunk loop (place_profile.cpp): synchronous, one device, resident tables.
+  // What that loop does not do is refused here, before any file is parsed or a device is opened
+  const bool fastq = is_fastq_file(query_file);
+  if (fastq) {
+    const char* const what = "a FASTQ query (quality-aware placement) ";
+    if (!rescore_file.empty()) { std::cerr << what << "is placed, not rescored: --rescore is not supported with it\n"; return 1; }
+    if (devices.size() > 1) { std::cerr << what << "runs on one device: --devices with several GPUs is not supported with it\n"; return 1; }
+    if (rank_given || world > 1 || !comm_file.empty()) {
+      std::cerr << what << "runs in one process: --rank / --world / --comm-file are not supported with it\n";
+      return 1;
+    }
+    if (!opt.prescoring) { std::cerr << what << "is preplaced from the lookup table: --no-heur is not supported with it\n"; return 1; }
+    if (opt.memsave == Options::Memsave::kOn) {
+      std::cerr << what << "is preplaced from the resident lookup table: --memsave on is not supported with it\n";
+      return 1;
+    }
+    if (!diag_flag.empty()) { std::cerr << what << "runs its own chunk loop: " << diag_flag << " is not supported with it\n"; return 1; }
+  }
   try {
     std::ifstream tf(tree_file);
     if (!tf) throw std::runtime_error{"file_check failed: " + tree_file};
@@ -269,7 +292,7 @@ int main(int argc, char** argv) {
     MSA ref = read_fasta(ref_file);
     // "Peeking into MSA files and generating masks" (src/main.cpp:468-494): columns that are all-gap in
     // the reference or in the whole query file leave both alignments (unless --no-pre-mask)
-    MSA_Info ref_info(ref), qry_info = MSA_Info::from_file(query_file);
+    MSA_Info ref_info(ref), qry_info = fastq ? fastq_msa_info(query_file) : MSA_Info::from_file(query_file);
     if (ref_info.sites() != qry_info.sites()) {
       std::cerr << "The reference and query alignment files do not seem to have the same alignment width! ("
                 << ref_info.sites() << " vs. " << qry_info.sites() << "). Are the query sequences not aligned?\n";
@@ -297,7 +320,9 @@ int main(int argc, char** argv) {
     const double secs_tree = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tree).count();
     if (devices.empty()) devices.push_back(device);
     const bool rank_mode = world > 1 || !comm_file.empty();   // a 1-rank communicator is legal (tests, 1-GPU nodes)
-    const Run_Stats st = !rescore_file.empty()
+    const Run_Stats st = fastq
+        ? place_profile_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
+        : !rescore_file.empty()
         ? rescore(tree, rescore_file, query_file, qry_info, outdir, opt, invocation, devices[0])
         : rank_mode
         ? simple_mpi_ranks(tree, query_file, qry_info, outdir, opt, invocation, device_given ? device : local_rank, rank, world, comm_file)
@@ -324,7 +349,8 @@ int main(int argc, char** argv) {
          << ", \"build_sample_s\": " << st.seconds_sample << ", \"lwr_filter_s\": " << st.seconds_post
          << ", \"jplace_text_s\": " << st.seconds_text << ", \"write_s\": " << st.seconds_write
          << ", \"chunk_path\": \"" << st.chunk_path << "\", \"device_chunk\": " << st.device_chunk
-         << ", \"lookup_mode\": \"" << st.lookup_mode << "\", \"lookup_block\": " << st.lookup_block << "}\n";
+         << ", \"lookup_mode\": \"" << st.lookup_mode << "\", \"lookup_block\": " << st.lookup_block
+         << ", \"query_kind\": \"" << st.query_kind << "\"}\n";
     }
   } catch (const std::exception& e) {
     std::cerr << e.what() << "\nAborting with a failure." << std::endl;

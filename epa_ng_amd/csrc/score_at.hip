@@ -36,6 +36,8 @@ struct ScArgs {
   const double* proximal;  // null: blen[b] - distal
   const uint8_t* codes;
   uint32_t cstride, crel;
+  const double* qe;        // PROFILE instantiations: eigen-space query rows [Q][qstride][S] in place of codes
+  uint32_t qstride;
   const uint32_t* win_begin;
   const uint32_t* win_span;
   double* lnl;
@@ -60,7 +62,9 @@ __device__ __forceinline__ void wave_sync() {
 
 // SITES: instead of the entry's lnL the kernel stores what it is the sum of -- per lane log(l0) - 256 count ln 2, one
 // coalesced 512-byte store per 64-site chunk -- into row i of a.rows; the lnL instantiation is the code it was.
-template <int S, bool SITES>
+// PROFILE: the query's eigen-space vector of a site is read from a.qe (a per-site likelihood row brought to the
+// eigenbasis by k_profile_eigen, profile.hip) instead of the table entry of the site's column code; nothing else differs.
+template <int S, bool SITES, bool PROFILE = false>
 __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
   __shared__ __attribute__((aligned(16))) double U[S * S];
   __shared__ __attribute__((aligned(16))) double UiT[S * S];   // [i][x] = U^-1[x][i]
@@ -83,7 +87,10 @@ __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
     const double* Xt = a.refT + (size_t)(2 * b) * cs * cW + begin;       // proximal side
     const double* Dt = a.refT + (size_t)(2 * b + 1) * cs * cW + begin;   // distal side
     const uint32_t* scp = a.scSum + (size_t)b * cW + begin;
-    const uint8_t* qc = a.codes + (size_t)q * a.cstride + (a.crel ? 0u : begin);
+    const uint8_t* qc = nullptr;
+    const double* qrow = nullptr;
+    if constexpr (PROFILE) qrow = a.qe + (size_t)q * a.qstride * S;
+    else qc = a.codes + (size_t)q * a.cstride + (a.crel ? 0u : begin);
     const double tp = a.pendant[e], td = a.distal[e];
     const double tx = a.proximal ? a.proximal[e] : a.blen[b] - td;
 
@@ -105,7 +112,9 @@ __global__ void __launch_bounds__(64) k_score_at(const ScArgs a) {
       const uint32_t site = ch * 64 + lane;
       const bool valid = site < n;
       const uint32_t s = valid ? site : 0;
-      const double* qv = m->qt + (size_t)qc[s] * S;
+      const double* qv;
+      if constexpr (PROFILE) qv = qrow + (size_t)s * S;
+      else qv = m->qt + (size_t)qc[s] * S;
       double l0 = 0.0;
       bool all_small = true;
       for (int k = 0; k < c; ++k) {
@@ -191,6 +200,8 @@ static void fill_args(epa_ctx* ctx, ScArgs& a, const EntryStage& e, uint64_t n) 
   a.distal = e.d_dis;
   a.proximal = e.d_prx;
   a.codes = e.d_codes;
+  a.qe = e.d_qe;
+  a.qstride = e.qe_stride;
   a.crel = ctx->code_stride ? 1u : 0u;
   a.cstride = a.crel ? ctx->code_stride : ctx->W;
   a.win_begin = e.d_begin;
@@ -211,7 +222,10 @@ int launch_score_at(epa_ctx* ctx, const EntryStage& e, double* d_lnl) {
   // persistent grid: neither n nor a branch id reaches a grid dimension
   const uint32_t grid = (uint32_t)std::min<uint64_t>(e.n, (uint64_t)ctx->n_cu * 8);
   epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_SCORE));
-  if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  if (a.qe) {   // profile queries
+    if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((k_score_at<20, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  } else if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
   else hipLaunchKernelGGL((k_score_at<20, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
   epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_SCORE));
   EPA_HIP(ctx, hipGetLastError());
@@ -229,7 +243,10 @@ int launch_site_lnl(epa_ctx* ctx, const EntryStage& e, const uint32_t* d_order, 
   const bool timed = flags & SITES_TIMED;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(n_rows, (uint64_t)ctx->n_cu * 8);
   if (timed) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_SITES));
-  if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  if (a.qe) {   // profile queries
+    if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, true, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((k_score_at<20, true, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  } else if (ctx->s == 4) hipLaunchKernelGGL((k_score_at<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
   else hipLaunchKernelGGL((k_score_at<20, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
   if (timed) epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_SITES));
   EPA_HIP(ctx, hipGetLastError());

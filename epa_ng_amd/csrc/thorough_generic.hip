@@ -36,6 +36,8 @@ struct ThArgsG {
   const uint32_t* order;
   const uint8_t* codes;
   uint32_t cstride, crel;
+  const double* qe;        // PROFILE instantiations: eigen-space query rows [Q][qstride][S] in place of codes
+  uint32_t qstride;
   const uint32_t* win_begin;
   const uint32_t* win_span;
   epa_result* out;
@@ -92,7 +94,9 @@ __device__ __forceinline__ double newton_g(Deriv&& deriv, double x1, double xgue
   return NAN;
 }
 
-template <int S>
+// PROFILE: the query's tip vector of a site (operand 0) is read from a.qe, a per-site likelihood row in the eigenbasis
+// (k_profile_eigen, profile.hip), instead of the table entry of the site's column code; nothing else differs.
+template <int S, bool PROFILE = false>
 __global__ void __launch_bounds__(64) k_thorough_generic(const ThArgsG a) {
   __shared__ double U[S * S], Ui[S * S];
   __shared__ double tab[3][EPA_MAX_CATS * S];
@@ -114,7 +118,10 @@ __global__ void __launch_bounds__(64) k_thorough_generic(const ThArgsG a) {
     const double* Xt = a.refT + (size_t)(2 * b) * cs * cW + begin;       // proximal side
     const double* Dt = a.refT + (size_t)(2 * b + 1) * cs * cW + begin;   // distal side
     const uint32_t* scp = a.scSum + (size_t)b * cW + begin;
-    const uint8_t* qc = a.codes + (size_t)q * a.cstride + (a.crel ? 0u : begin);
+    const uint8_t* qc = nullptr;
+    const double* qrow = nullptr;
+    if constexpr (PROFILE) qrow = a.qe + (size_t)q * a.qstride * S;
+    else qc = a.codes + (size_t)q * a.cstride + (a.crel ? 0u : begin);
     const double orig = a.blen[b];
 
     // wave-uniform tables: slot j entry i = (k, x) -> f_j(lam_x r_k) ; mode 0: exp(lr t_j) for
@@ -145,7 +152,9 @@ __global__ void __launch_bounds__(64) k_thorough_generic(const ThArgsG a) {
     // A is propagated with tab[0], B with tab[1], F is the other end of the branch being optimised.
     auto site_pass = [&](uint32_t site, bool valid, int opA, int opB, int opF, uint32_t& count) -> double {
       const uint32_t s = valid ? site : 0;
-      const double* qv = m->qt + (size_t)qc[s] * S;
+      const double* qv;
+      if constexpr (PROFILE) qv = qrow + (size_t)s * S;
+      else qv = m->qt + (size_t)qc[s] * S;
       auto operand = [&](int op, int k, int x) -> double {
         return op == 0 ? qv[x] : (op == 1 ? Dt : Xt)[(size_t)(k * S + x) * cW + s];
       };
@@ -358,7 +367,8 @@ __global__ void __launch_bounds__(64) k_thorough_generic(const ThArgsG a) {
 
 int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pairs, const uint8_t* d_codes,
                             const uint32_t* d_begin, const uint32_t* d_span, uint32_t max_span,
-                            epa_result* d_out, unsigned long long* d_stats, const uint32_t* d_order, bool caller_times) {
+                            epa_result* d_out, unsigned long long* d_stats, const uint32_t* d_order, bool caller_times,
+                            const double* d_qe, uint32_t qe_stride) {
   ThArgsG a;
   a.m = ctx->dmodel;
   a.blo = ctx->blo;
@@ -370,6 +380,8 @@ int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pa
   a.pairs = d_pairs;
   a.order = d_order;   // pair indices of this launch (one span class of a mixed call), or all pairs
   a.codes = d_codes;
+  a.qe = d_qe;
+  a.qstride = qe_stride;
   a.crel = ctx->code_stride ? 1u : 0u;
   a.cstride = a.crel ? ctx->code_stride : ctx->W;
   a.win_begin = d_begin;
@@ -385,7 +397,10 @@ int launch_thorough_generic(epa_ctx* ctx, const epa_pair* d_pairs, uint64_t n_pa
   if (!a.slab) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(generic sumtable scratch)");
   const bool timed = !d_order && !caller_times;   // a per-class launch is timed by its caller
   if (timed) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_THOROUGH));
-  if (ctx->s == 4) hipLaunchKernelGGL(k_thorough_generic<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
+  if (d_qe) {   // profile queries
+    if (ctx->s == 4) hipLaunchKernelGGL((k_thorough_generic<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((k_thorough_generic<20, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+  } else if (ctx->s == 4) hipLaunchKernelGGL(k_thorough_generic<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
   else hipLaunchKernelGGL(k_thorough_generic<20>, dim3(grid), dim3(64), 0, ctx->stream, a);
   if (timed) epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_THOROUGH));
   EPA_HIP(ctx, hipGetLastError());

@@ -290,6 +290,17 @@ def premask(ref_file, query_file):
     return buf[:n].copy()
 
 
+def fastq_copy(in_file, out_file):
+    """the aligned-FASTQ reader of the CLI (-q reads.fastq) as a round trip: every record of in_file written to out_file
+    as the reader holds it -> number of records; RuntimeError (naming the record) where the reader refuses the file"""
+    lib = host_lib()
+    lib.epa_host_fastq_copy.restype = C.c_long
+    n = lib.epa_host_fastq_copy(str(in_file).encode(), str(out_file).encode())
+    if n < 0:
+        raise RuntimeError(lib.epa_host_last_error().decode())
+    return int(n)
+
+
 def heuristic(lnl, mode="dynamic", thresh=0.99999):
     lnl = np.ascontiguousarray(lnl, np.float64)
     Q, B = lnl.shape

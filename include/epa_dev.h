@@ -407,6 +407,80 @@ int epa_dev_site_lnl(epa_ctx* ctx, const epa_pair* pairs, const double* pendant,
                      uint32_t pitch, double* site_lnl /* [n][pitch] */);
 
 /*
+ * Profile queries: a query given as per-site state LIKELIHOODS instead of one hard-called character per site -- reads
+ * with per-base qualities (the tip-error model, Felsenstein 2004; RAxML-NG --prob-msa), consensus or profile columns.
+ * A profile query q is a window (win_begin[q], win_span[q]) plus one row of S = states non-negative doubles per window
+ * position, in the compact-row idiom of epa_encode_queries_compact:
+ *   prof[((size_t)q * stride + j) * S + m],  j < win_span[q] <= stride,  is the likelihood of the observation at
+ *   alignment column win_begin[q] + j given true state m (libpll's state order: A C G T / A R N D C Q E G H I L K M F P
+ *   S T W Y V).  Rows from the span up to `stride` are padding and are never read.  prof may be a host or a device
+ *   pointer, by the library's usual rule.
+ * The site likelihood of the row v on branch b at given lengths is
+ *   (1 - p_inv) sum_k w_k sum_i pi_i [P_k(pendant) v]_i [P_k(distal) D_k]_i [P_k(proximal) X_k]_i  +  p_inv pi_inv(site)
+ * The +I term is added ONCE whatever v is: libpll's rule for coded queries (epa_ref_desc.invariant_state).  Scaler counts
+ * are handled as in epa_dev_score_at.  It follows that a 0/1 row equal to the state set of a column code reproduces the
+ * coded query: epa_dev_score_at_profile, _site_lnl_profile and _thorough_profile then return the bits of their coded
+ * twins (the latter under the option "thorough_generic"); epa_dev_preplace_profile agrees with epa_dev_preplace up to
+ * rounding (another order of operations).
+ * Conditions, stated and not measured: every entry of a window row is finite and >= 0, and the row's largest entry lies
+ * in [2^-64, 2^64], which keeps the kernels' scaling decisions the reference side's own.  Host rows are validated on the
+ * host, device rows on the device (a status word read back before the call goes on); EPA_ERR_INVALID_ARG names the first
+ * offending query and position: "... query Q position J: ...".  Windows are checked as for the coded calls; a window
+ * longer than `stride` is EPA_ERR_INVALID_ARG.
+ * The query layout and packing of the context (epa_dev_set_query_layout / _packing) do not concern profile calls and
+ * are left as they are.
+ *
+ *   epa_dev_preplace_profile     lnl[q*B + b] = sum over the window of log(site likelihood) at pendant_default and
+ *                                distal = proximal = branch_length[b] / 2: epa_dev_preplace for rows.  Computed from the
+ *                                resident lookup table's pure-state columns, sum_m v_m exp(T[b][site][column of m]), with
+ *                                the +I term, which every column holds once, counted once; the query-independent
+ *                                exp(T_m - T_any) are a table derived once per context ((S + 2) x 8 bytes per branch x
+ *                                site).  Timer: "preplace_profile"
+ *   epa_dev_thorough_profile     epa_dev_thorough for rows: always the general Newton kernel (k_thorough_generic), both
+ *                                BLO rules.  Timer: "thorough"
+ *   epa_dev_score_at_profile, epa_dev_site_lnl_profile
+ *                                the arguments, checks and outputs of epa_dev_score_at / epa_dev_site_lnl with
+ *                                (prof, stride) in place of q_codes.  Timers: "score_at" / "site_lnl"
+ *   epa_dev_place_chunk_profile  preplace_profile -> the context's candidate selection (epa_dev_set_heuristic, as
+ *                                epa_dev_select_candidates applies it to that table) -> thorough_profile; the table never
+ *                                leaves HBM.  Pairs and results are those of the three calls made one after the other, bit
+ *                                for bit.  EPA_ERR_PAIR_OVERFLOW as in epa_dev_place_chunk: call again with larger buffers
+ *                                (synchronous: nothing stays staged)
+ * A context in the blocked lookup layout (EPA_FLAG_LOOKUP_BLOCKS) has no resident table: the two entry points that
+ * preplace return EPA_ERR_UNSUPPORTED, the message names --memsave.  score_at / site_lnl / thorough on profiles read only
+ * the transformed CLVs and work in both layouts.
+ * Not available for profiles: pipeline slots and group launches, the RELL and marginal-likelihood statistics, the tuned
+ * Newton kernels.
+ */
+int epa_dev_preplace_profile(epa_ctx* ctx, const double* prof, uint32_t stride, const uint32_t* win_begin,
+                             const uint32_t* win_span, uint32_t Q, double* lnl);
+int epa_dev_thorough_profile(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_pairs, const double* prof, uint32_t stride,
+                             const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, epa_result* out,
+                             epa_thorough_stats* stats);
+int epa_dev_score_at_profile(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                             const double* proximal /* may be NULL */, uint64_t n, const double* prof, uint32_t stride,
+                             const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, double* lnl);
+int epa_dev_site_lnl_profile(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, const double* distal,
+                             const double* proximal /* may be NULL */, uint64_t n, const double* prof, uint32_t stride,
+                             const uint32_t* win_begin, const uint32_t* win_span, uint32_t Q, uint32_t pitch,
+                             double* site_lnl /* [n][pitch] */);
+int epa_dev_place_chunk_profile(epa_ctx* ctx, const double* prof, uint32_t stride, const uint32_t* win_begin,
+                                const uint32_t* win_span, uint32_t Q, double threshold, epa_pair* pairs,
+                                epa_result* results, uint64_t max_pairs, uint64_t* n_pairs, epa_thorough_stats* stats);
+/*
+ * Host only, no device needed: profile rows from column codes and Phred scores, the standard tip-error model.  codes and
+ * phred are compact rows ([Q][stride], the window only: epa_encode_queries_compact); phred holds the scores themselves
+ * (0 .. 93, not their ASCII form).  At window position j of query q:
+ *   a pure-state code with score s   eps = min(pow(10, -s / 10), (S - 1) / S);  v[called] = 1 - eps, v[other] = eps / (S - 1)
+ *   any other code (ambiguity, gap)  its 0/1 state set, the score is ignored
+ * Rows from the span up to the stride are left untouched.  EPA_ERR_INVALID_ARG: a score above 93 at a pure-state code, a
+ * window longer than the stride; EPA_ERR_INVALID_CHAR: a code that is no lookup column (epa_dev_last_error(NULL) names
+ * query and position).
+ */
+int epa_profile_from_phred(uint32_t states, uint32_t Q, uint32_t stride, const uint8_t* codes, const uint8_t* phred,
+                           const uint32_t* win_span, double* prof);
+
+/*
  * Marginal likelihood of "read q sits somewhere on edge b", integrated over where it attaches and how long its pendant
  * branch is.  The definition is this project's own (pplacer's -p mode, which writes the jplace fields marginal_like and
  * post_prob, is the motivation, not a parity target).  For an entry (branch b of length L_b, query q):
@@ -859,7 +933,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
