@@ -153,6 +153,11 @@ def dev_lib():
         L.epa_dev_place_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_double, C.c_void_p, C.c_void_p,
                                           C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_Stats)]
+        L.epa_dev_dedup_queries.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_uint32)]
+        L.epa_dev_place_chunk_dedup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                C.POINTER(_Stats), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.epa_dev_chunk_stage.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.epa_dev_chunk_launch.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_double, C.c_void_p,
                                            C.c_void_p, C.c_uint64, C.c_uint32]
@@ -767,6 +772,44 @@ class Evaluator:
         if host:
             return pairs_out[:n.value], results_out[:n.value]
         return n.value
+
+    def dedup_queries(self, codes, win_begin, win_span, Q=None, rep_out=None, first_out=None):
+        """classes of identical queries (epa_dev_dedup_queries: equal win_begin, win_span and window codes), numbered in
+        order of first appearance -> (rep uint32 [Q], first uint32 [n_unique]) numpy arrays, or n_unique when device
+        buffers rep_out [Q] / first_out [Q] are supplied"""
+        Q = len(win_begin) if Q is None else Q
+        host = rep_out is None
+        if host:
+            rep_out, first_out = np.empty(Q, np.uint32), np.empty(Q, np.uint32)
+        n = C.c_uint32(0)
+        self._layout(codes)
+        self._check(self.L.epa_dev_dedup_queries(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, _ptr(rep_out),
+                                                 _ptr(first_out), C.byref(n)))
+        return (rep_out, first_out[:n.value].copy()) if host else n.value
+
+    def place_chunk_dedup(self, codes, win_begin, win_span, Q=None, threshold=0.99999, max_span=0, max_pairs=None,
+                          pairs_out=None, results_out=None, rep_out=None, first_out=None):
+        """dedup_queries -> place_chunk over one representative per class (epa_dev_place_chunk_dedup); seq_id of a pair is
+        a class index.  Returns (pairs, results, rep, first) numpy arrays, or (n_pairs, n_unique) when device buffers are
+        supplied (all four, or none)"""
+        Q = len(win_begin) if Q is None else Q
+        if max_pairs is None:
+            max_pairs = Q * 64
+        host = pairs_out is None
+        if host:
+            pairs_out = np.empty(max_pairs, PAIR_DTYPE)
+            results_out = np.empty(max_pairs, RESULT_DTYPE)
+            rep_out, first_out = np.empty(Q, np.uint32), np.empty(Q, np.uint32)
+        n, nu, st = C.c_uint64(0), C.c_uint32(0), _Stats()
+        self._layout(codes)
+        self._check(self.L.epa_dev_place_chunk_dedup(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q, max_span,
+                                                     threshold, _ptr(pairs_out), _ptr(results_out), max_pairs, C.byref(n),
+                                                     C.byref(st), _ptr(rep_out), _ptr(first_out), C.byref(nu)))
+        self.last_stats = {"pairs": st.pairs, "rounds": st.rounds,
+                           "newton_evals": st.newton_evals, "reverts": st.reverts}
+        if host:
+            return pairs_out[:n.value], results_out[:n.value], rep_out, first_out[:nu.value].copy()
+        return n.value, nu.value
 
     # ---- double-buffered chunk pipeline (epa_dev_chunk_stage / _launch / _finish): the upload of
     # chunk k+1 and the download of chunk k-1 overlap the kernels of chunk k

@@ -642,6 +642,12 @@ extern "C" int epa_dev_set_option(epa_ctx* ctx, const char* key, int value) {
     ctx->lookup_block = (uint32_t)value;
     return EPA_OK;
   }
+  const bool dedup_key = strcmp(key, "dedup_key_bits") == 0;
+  if (dedup_key || strcmp(key, "dedup_sort_bits") == 0) {
+    if (value < 0 || value > 64) return epa_fail(ctx, EPA_ERR_INVALID_ARG, std::string("set_option: ") + key + " must be 0 .. 64");
+    (dedup_key ? ctx->opt.dedup_key_bits : ctx->opt.dedup_sort_bits) = value;
+    return EPA_OK;
+  }
   struct Entry { const char* name; int EpaOptions::*field; };
   static const Entry table[] = {
       {"thorough_generic", &EpaOptions::thorough_generic}, {"preplace_generic", &EpaOptions::preplace_generic},
@@ -2315,6 +2321,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "rell_au")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_AU]][epa_ctx::T_RELL_AU];
   else if (!strcmp(which, "rell_kh")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_KH]][epa_ctx::T_RELL_KH];
   else if (!strcmp(which, "preplace_profile")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_PREPLACE_PROFILE]][epa_ctx::T_PREPLACE_PROFILE];
+  else if (!strcmp(which, "dedup")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_DEDUP]][epa_ctx::T_DEDUP];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

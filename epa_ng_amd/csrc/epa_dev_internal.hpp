@@ -272,6 +272,8 @@ struct EpaOptions {
   int timers = 1;             // hipEvent records around the kernel families (epa_dev_last_kernel_ms)
   int newton_lds = 0;         // single-wave 4-state Newton kernels read their table through LDS instead of DPP
   int tip_distal = 1;         // pairs whose branch ends in a tip run the TIPD Newton kernels (0: the row form for all)
+  int dedup_key_bits = 64;    // low bits kept of a query's dedup key (dedup.hip): fewer force unequal rows into one run
+  int dedup_sort_bits = 32;   // low key bits the dedup sort looks at: rows equal there share a run, the full key and the codes part them
 };
 
 struct epa_ctx {
@@ -334,7 +336,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 23;   // named by EpaSlot below
+  static constexpr int N_SCRATCH = 26;   // named by EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -359,7 +361,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, N_TIMERS = 11 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, N_TIMERS = 12 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -444,7 +446,8 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
 // ---- scratch slots of a bank (epa_scratch / epa_to_device).  0 .. 12: the placement path (epa_dev.hip and the
 // launchers of preplace.hip, select.hip, thorough_*.hip); 0 .. 4, 7 .. 9 and 13 .. 20: the post-placement entry points
 // (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au, _rell_kh) and their launchers
-// (score_at.hip, marginal.hip, rell.hip).  Names that share a number never hold live data at the same time:
+// (score_at.hip, marginal.hip, rell.hip); 21 .. 22: profile queries; 23 .. 25: duplicate queries (dedup.hip).  Names that share a
+// number never hold live data at the same time:
 //   2   the tip map is read only by the transform kernels of epa_dev_create, queued before any call can stage a span
 //       (SLOT_CLV_*, SLOT_SCALER_*: creation only, in the same way)
 //   6   the preplacement's status words are read (preplace_check_status; k_pack_readback through SelectPending::
@@ -500,6 +503,10 @@ enum EpaSlot : int {
   SLOT_RELL_KH = 20,      // rell_kh: [L n | L_b - L n | L_k* - L n | T n | k* n | counters 3 n | matrix offsets | b | scale matrices | spilled scores]
   SLOT_PROFILE = 21,      // profile calls (profile.hip): the rows [Q][stride][s] of a call whose rows live on the host
   SLOT_PROFILE_EIGEN = 22,//   and [fault key, 256 bytes | the rows in the eigenbasis [Q][stride][s]] (k_profile_eigen)
+  SLOT_DEDUP = 23,        // dedup.hip: [status | keys Q | sorted keys Q | idx Q | order Q | lead Q | flags Q + 1 | scan Q + 1 | rocprim temp]
+  SLOT_DEDUP_IN = 24,     //   the chunk's codes | win_begin | win_span where the caller's live on the host (the chunk body behind
+                          //   the pass stages the compacted chunk in 0 .. 2 and 10)
+  SLOT_DEDUP_ROWS = 25,   //   the compacted chunk: codes | win_begin | win_span of the representatives, then rep | first for host callers
 };
 
 // The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,

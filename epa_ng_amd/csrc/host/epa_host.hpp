@@ -519,14 +519,17 @@ struct Run_Stats {
   double seconds_encode = 0, seconds_sample = 0, seconds_text = 0, seconds_loop = 0;
   int host_threads = 0;
   // which chunk body the run used: "pipelined" (staged device chunks, several in flight), "fused" (one
-  // epa_dev_place_chunk at a time), "place_all" (--no-heur on the device) or "host" (table round trip + host
-  // heuristics); and the reads per device chunk after the memory clamp (device_chunk_reads)
+  // epa_dev_place_chunk at a time), "place_all" (--no-heur on the device), "host" (table round trip + host
+  // heuristics), "profile" (FASTQ queries) or "dedup" (--dedup); and the reads per device chunk after the memory clamp (device_chunk_reads)
   std::string chunk_path;
   size_t device_chunk = 0;
   // lookup layout of the device context(s): "resident" or "blocks", branches per block (0: resident)
   std::string lookup_mode = "resident";
   uint32_t lookup_block = 0;
   std::string query_kind = "coded";   // "profile": a FASTQ query, placed as per-site state likelihoods (place_profile.cpp)
+  // --dedup (place_dedup.cpp): classes of identical reads summed over the chunks (of `queries` reads)
+  bool dedup = false;
+  size_t dedup_unique = 0;
 };
 // Reads per device chunk that fit a device: `slots` pipeline slots each own a preplacement table of
 // Q x pitch(branches) x 8 bytes (pitch: the row rounded up to 64 bytes), plus a quarter of that for codes, bitmap and
@@ -560,6 +563,12 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
 // Synchronous, one device, the resident lookup layout; --no-heur and --memsave on are refused
 Run_Stats place_profile_file(const Tree& tree, const std::string& query_file, const MSA_Info& msa_info, const std::string& outdir,
                              const Options& options, const std::string& invocation, int device = 0);
+
+// --dedup: every chunk encoded and placed by epa_dev_place_chunk_dedup, one representative per class of identical reads;
+// one placement object per class in order of first appearance, "n" = the class's names in file order; LWR, filter and
+// jplace as simple_mpi.  Synchronous, one device, classes per chunk; --no-heur is refused
+Run_Stats place_dedup_file(const Tree& tree, const std::string& query_file, const MSA_Info& msa_info, const std::string& outdir,
+                           const Options& options, const std::string& invocation, int device = 0);
 
 // one process per GPU: rank's contiguous slice of the query file on `device`, results gathered to rank 0
 // over the product library's RCCL gather (place_ranks.cpp; src/net/epa_mpi_util.cpp:10-30)

@@ -64,6 +64,11 @@ static void usage() {
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
       "                        (default 40000; 0: chunks of exactly --chunk-size)\n"
+      "  --dedup               place identical reads of a chunk once (amplicon / metabarcoding inputs): one placement object per\n"
+      "                        class of identical reads, in order of first appearance, its \"n\" listing all the class's names in\n"
+      "                        file order.  Classes are per chunk: equal reads in different chunks stay separate objects (raise\n"
+      "                        --chunk-size to merge them).  One device, chunk by chunk; --devices a,b / --rank / --world /\n"
+      "                        --no-heur / --rescore / a FASTQ query are refused with it\n"
       "  --no-pre-mask         evaluate all sites of every query\n"
       "  --raxml-blo           radius-1 local branch-length optimisation instead of the sliding rule\n"
       "  --rate-scalers auto|on|off  per-rate-category numerical scaling (auto: on above 2000 tips)\n"
@@ -94,6 +99,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> placing_flags;   // flags that steer heuristic, optimiser or filter: meaningless with --rescore
   Options opt;
   int device = 0;
+  bool dedup = false;   // --dedup: the loop of place_dedup.cpp
   bool device_given = false, rell_given = false, prior_given = false, nodes_given = false, rank_given = false;
   std::string diag_flag;   // --host-heuristic / --device-min-chunk: steer the coded chunk loop only
   std::vector<int> devices;
@@ -198,6 +204,7 @@ int main(int argc, char** argv) {
     else if (a == "--comm-self-send") opt.comm_self_send = true;       // test hook
     else if (a == "--host-heuristic") { diag_flag = a; opt.host_heuristic = true; }   // diagnostics
     else if (a == "--no-pipeline") opt.no_pipeline = true;
+    else if (a == "--dedup") dedup = true;
     else if (a == "--stats-json") stats_json = need(i);
     else if (a == "--redo" || a == "--verbose") {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -284,6 +291,22 @@ int main(int argc, char** argv) {
     }
     if (!diag_flag.empty()) { std::cerr << what << "runs its own chunk loop: " << diag_flag << " is not supported with it\n"; return 1; }
   }
+  // --dedup runs a chunk loop of its own (place_dedup.cpp): synchronous, one device.  Refused in the same way
+  if (dedup) {
+    const char* const what = "--dedup (identical reads placed once) ";
+    if (!rescore_file.empty()) { std::cerr << what << "places reads: --rescore is not supported with it\n"; return 1; }
+    if (devices.size() > 1) { std::cerr << what << "runs on one device: --devices with several GPUs is not supported with it\n"; return 1; }
+    if (rank_given || world > 1 || !comm_file.empty()) {
+      std::cerr << what << "runs in one process: --rank / --world / --comm-file are not supported with it\n";
+      return 1;
+    }
+    if (!opt.prescoring) { std::cerr << what << "runs the fused chunk body: --no-heur is not supported with it\n"; return 1; }
+    if (fastq) { std::cerr << what << "compares coded reads: a FASTQ query is not supported with it\n"; return 1; }
+    if (!diag_flag.empty() || opt.no_pipeline) {
+      std::cerr << what << "runs its own chunk loop: " << (diag_flag.empty() ? "--no-pipeline" : diag_flag) << " is not supported with it\n";
+      return 1;
+    }
+  }
   try {
     std::ifstream tf(tree_file);
     if (!tf) throw std::runtime_error{"file_check failed: " + tree_file};
@@ -322,6 +345,8 @@ int main(int argc, char** argv) {
     const bool rank_mode = world > 1 || !comm_file.empty();   // a 1-rank communicator is legal (tests, 1-GPU nodes)
     const Run_Stats st = fastq
         ? place_profile_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
+        : dedup
+        ? place_dedup_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
         : !rescore_file.empty()
         ? rescore(tree, rescore_file, query_file, qry_info, outdir, opt, invocation, devices[0])
         : rank_mode
@@ -350,7 +375,9 @@ int main(int argc, char** argv) {
          << ", \"jplace_text_s\": " << st.seconds_text << ", \"write_s\": " << st.seconds_write
          << ", \"chunk_path\": \"" << st.chunk_path << "\", \"device_chunk\": " << st.device_chunk
          << ", \"lookup_mode\": \"" << st.lookup_mode << "\", \"lookup_block\": " << st.lookup_block
-         << ", \"query_kind\": \"" << st.query_kind << "\"}\n";
+         << ", \"query_kind\": \"" << st.query_kind << "\"";
+      if (st.dedup) sj << ", \"dedup\": {\"reads\": " << st.queries << ", \"unique\": " << st.dedup_unique << "}";
+      sj << "}\n";
     }
   } catch (const std::exception& e) {
     std::cerr << e.what() << "\nAborting with a failure." << std::endl;

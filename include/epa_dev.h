@@ -241,6 +241,13 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
  *                          branch ends in a tip -- contexts created from the tree -- are launched apart on kernels that
  *                          read the tip's 4-bit state set per site instead of 16 rows of its eigen image; bit-identical
  *                          results)
+ *   "dedup_key_bits"    n: the duplicate search (epa_dev_dedup_queries) keeps only the low n bits of a query's 64-bit key,
+ *                          n = 0 .. 64 (default 64), else EPA_ERR_INVALID_ARG.  Classes do not depend on it: fewer bits give
+ *                          unequal rows one key, and the exact comparison takes them apart again (what the tests force).
+ *                          A run of m rows in k classes costs up to m k row comparisons: not for large chunks
+ *   "dedup_sort_bits"   n: the low key bits its sort looks at, n = 0 .. 64 (default 32: four digit passes; rows that agree
+ *                          there share a run and are parted by the full key first, then by their codes).  Classes do not
+ *                          depend on it either
  * Unknown key: EPA_ERR_INVALID_ARG.
  */
 int epa_dev_set_option(epa_ctx* ctx, const char* key, int value);
@@ -736,6 +743,47 @@ int epa_dev_place_chunk(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* wi
                         uint64_t* n_pairs, epa_thorough_stats* stats);
 
 /*
+ * Duplicate queries.  Amplicon and metabarcoding inputs hold each distinct read many times; a query's result does not
+ * depend on the other queries of its chunk, so placing one representative per class of identical queries and handing its
+ * rows to every member is exact.  (The reference has no counterpart: its users collapse duplicates in a step of their own
+ * before placement.)
+ * Two queries of a chunk are IDENTICAL when all three of these hold:
+ *   - win_begin is equal;
+ *   - win_span is equal;
+ *   - the codes of the win_span window positions are equal.
+ * Nothing else is compared: not the bytes of a compact row between span and stride, not the pad nibble of an odd 4-bit
+ * row, not the columns outside the window of a full-width (Q x W) row.  The answer is the same in all three layouts
+ * (full-width, compact, compact 4-bit: epa_dev_set_query_layout / _packing).  Queries with win_span == 0 are identical when
+ * their win_begin is equal.
+ * Classes are numbered in the order of their first appearance in the chunk:
+ *   first[u]  the smallest query index of class u; first is strictly increasing
+ *   rep[q]    the class of query q; rep[first[u]] == u
+ * The result is exact: a 64-bit key of (win_begin, win_span, window codes) only brings candidates together (a stable sort
+ * of (key, q) on the key's low bits), every member of a run is then compared code for code with the run's first member of
+ * the same key, and a member that differs goes on through the run until it meets an equal row.  No two different rows
+ * share a class and no two identical rows are split, whatever the keys do (options "dedup_key_bits", "dedup_sort_bits").
+ *   epa_dev_dedup_queries      rep [Q], first [Q] capacity (the first *n_unique entries are written), *n_unique.  An empty
+ *                              window is legal here; a window that leaves the alignment or its row is EPA_ERR_QUERY_WIDTH
+ *   epa_dev_place_chunk_dedup  the classes as above, the representatives' rows and windows gathered into compacted device
+ *                              arrays (the context's own layout and packing, row pitch unchanged), then epa_dev_place_chunk's
+ *                              body over those arrays in place.  seq_id of a returned pair is a CLASS index; pairs and
+ *                              results are bit for bit those of epa_dev_place_chunk on the representatives' rows alone, in
+ *                              that order (max_span: of the whole chunk, 0 = unknown).  EPA_ERR_PAIR_OVERFLOW and the window
+ *                              errors (an empty window included, the query named is the chunk's) as in epa_dev_place_chunk;
+ *                              rep, first and *n_unique are valid after an overflow.  Both lookup layouts
+ * Inputs and outputs may be host or device pointers; Q == 0 returns EPA_OK with *n_unique = 0.  Timer: "dedup" (keys,
+ * sort, classes, scan and gather together; the chunk body keeps its own timers).
+ * Out of scope: classes across chunks; pipeline slots and group launches; epa_dev_place_all; profile rows.
+ */
+int epa_dev_dedup_queries(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span,
+                          uint32_t Q, uint32_t* rep /* [Q] */, uint32_t* first /* [Q] capacity */, uint32_t* n_unique);
+int epa_dev_place_chunk_dedup(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin, const uint32_t* win_span,
+                              uint32_t Q, uint32_t max_span, double threshold,
+                              epa_pair* pairs, epa_result* results, uint64_t max_pairs, uint64_t* n_pairs,
+                              epa_thorough_stats* stats,
+                              uint32_t* rep /* [Q] */, uint32_t* first /* [Q] capacity */, uint32_t* n_unique);
+
+/*
  * The same chunk body as a double-buffered pipeline, the device-side counterpart of the
  * reference's read-ahead of the next chunk (src/seq/MSA_Stream.cpp:79-82, the prefetch in
  * src/core/place.cpp:190-215): the query upload of chunk k+1 and the result download of chunk k-1
@@ -933,7 +981,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
