@@ -111,6 +111,10 @@ def dev_lib():
                                        C.c_void_p]
         L.epa_dev_preplace_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                C.c_void_p, C.c_void_p]
+        L.epa_dev_preplace_screen_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                    C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.epa_dev_preplace_screen_runs.argtypes = [C.c_void_p]
+        L.epa_dev_preplace_screen_runs.restype = C.c_uint64
         L.epa_dev_thorough.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(_Stats)]
         L.epa_dev_score_at.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
@@ -501,6 +505,27 @@ class Evaluator:
         self._check(self.L.epa_dev_preplace_bounded(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q,
                                                     int(max_span), _ptr(out), _ptr(keys)))
         return (out, keys) if seg_keys else out
+
+    def preplace_screen_runs(self):
+        """internal: chunk bodies of this context whose preplacement took the screen's two-pass route"""
+        return int(self.L.epa_dev_preplace_screen_runs(self.h))
+
+    def preplace_screen_probe(self, codes, win_begin, win_span, max_span, threshold=0.99999, arrays=True):
+        """internal: the fp32 two-branch screen of the pair preplacement and its band test, alone
+        (epa_dev_preplace_screen_probe) -> dict: ran, delta, included (cells), M, nonfinite, band_t, ms_screen, ms_band
+        and, with arrays, seg32 float32 [Q][nseg] (NaN = no key) and mask uint64 [Q]"""
+        Q = len(win_begin)
+        nseg = (self.B + 63) // 64
+        seg32 = np.full((Q, nseg), np.nan, np.float32) if arrays else None
+        mask = np.zeros(Q, np.uint64) if arrays else None
+        info = np.zeros(8, np.float64)
+        self._layout(codes)
+        self._check(self.L.epa_dev_preplace_screen_probe(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q,
+                                                         int(max_span), float(threshold), _ptr(seg32), _ptr(mask),
+                                                         _ptr(info)))
+        return {"ran": bool(info[0]), "delta": float(info[1]), "included": int(info[2]), "M": float(info[3]),
+                "nonfinite": int(info[4]), "band_t": float(info[5]), "ms_screen": float(info[6]),
+                "ms_band": float(info[7]), "seg32": seg32, "mask": mask}
 
     def thorough(self, pairs, codes, win_begin, win_span, Q=None, n_pairs=None, out=None):
         """pairs: structured PAIR_DTYPE array (or device buffer) -> RESULT_DTYPE array."""

@@ -30,6 +30,8 @@ static int chunk_body_begin(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t
     t.segmax = (unsigned long long*)epa_scratch(ctx, SLOT_SEGMAX, sizeof(unsigned long long) * (size_t)Q * t.segp);
     if (!t.segmax) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(segment maxima)");
   }
+  // the selection below is this table's only reader: where it reads by segment maxima, the preplacement may screen
+  if (epa_select_takes_seg(ctx, t, Q, threshold)) t.band_t = epa_select_band_t(threshold, ctx->B);
   const uint32_t* pre_status = nullptr;
   int rc = launch_preplace(ctx, d_codes, d_begin, d_span, Q, t, max_span, &pre_status);
   if (!rc) rc = launch_select_begin(ctx, t, pre_status, Q, threshold, d_pairs, max_pairs, d_span, rb, sp);

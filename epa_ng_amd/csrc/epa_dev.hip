@@ -654,7 +654,8 @@ extern "C" int epa_dev_set_option(epa_ctx* ctx, const char* key, int value) {
       {"select_full_rows", &EpaOptions::select_full_rows}, {"select_sort", &EpaOptions::select_sort},
       {"queued_thorough", &EpaOptions::queued_thorough},   {"xcd_balance", &EpaOptions::xcd_balance},
       {"aa_valu", &EpaOptions::aa_valu},                   {"timers", &EpaOptions::timers},
-      {"newton_lds", &EpaOptions::newton_lds},             {"tip_distal", &EpaOptions::tip_distal}};
+      {"newton_lds", &EpaOptions::newton_lds},             {"tip_distal", &EpaOptions::tip_distal},
+      {"preplace_screen", &EpaOptions::preplace_screen},   {"preplace_screen_scale", &EpaOptions::preplace_screen_scale}};
   for (const Entry& e : table)
     if (strcmp(key, e.name) == 0) {
       ctx->opt.*e.field = value;
@@ -745,6 +746,7 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
   if (ctx->blen) (void)hipFree(ctx->blen);
   if (ctx->lookup) (void)hipFree(ctx->lookup);
   if (ctx->lookup2) (void)hipFree(ctx->lookup2);
+  if (ctx->lookup2f) (void)hipFree(ctx->lookup2f);
   if (ctx->prof_tab) (void)hipFree(ctx->prof_tab);
   for (void* p : ctx->blk_buf) if (p) (void)hipFree(p);
   for (auto& v : ctx->blk_ev) for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e);
@@ -1654,6 +1656,61 @@ extern "C" int epa_dev_preplace_bounded(epa_ctx* ctx, const uint8_t* q_codes, co
                                 epa_is_device_ptr(seg_keys) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
   EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return preplace_check_status(ctx, d_status);  // windows are validated on device (k_make_groups)
+}
+
+extern "C" uint64_t epa_dev_preplace_screen_runs(const epa_ctx* ctx) { return ctx ? ctx->screen_runs : 0; }
+
+extern "C" int epa_dev_preplace_screen_probe(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
+                                             const uint32_t* win_span, uint32_t Q, uint32_t max_span, double threshold,
+                                             float* seg32, uint64_t* seg_mask, double* info) {
+  if (!ctx || !q_codes || !win_begin || !win_span || !info)
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  for (int i = 0; i < 8; ++i) info[i] = 0.0;
+  if (Q == 0) return EPA_OK;
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = epa_dev_build_lookup(ctx);
+  if (rc) return rc;
+  if (max_span > ctx->W) max_span = ctx->W;
+  if (max_span && !epa_is_device_ptr(win_span))
+    for (uint32_t q = 0; q < Q; ++q)
+      if (win_span[q] > max_span) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "preplace: a window is longer than max_span");
+  if (ctx->s == 4 && ctx->lookup2 && (rc = launch_build_lookup2f(ctx))) return rc;
+  const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, win_span, sizeof(uint32_t) * Q);
+  if (!d_codes || !d_begin || !d_span) return epa_fail(ctx, EPA_ERR_HIP, "query upload failed");
+  PreScreenProbe probe;
+  probe.band_t = epa_select_band_t(threshold, ctx->B);
+  const uint32_t* d_status = nullptr;
+  rc = launch_preplace(ctx, d_codes, d_begin, d_span, Q, PreTable{}, max_span, &d_status, &probe);
+  if (rc) return rc;
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = preplace_check_status(ctx, d_status))) return rc;
+  info[0] = probe.ran ? 1.0 : 0.0;
+  info[3] = ctx->screen_M;
+  info[4] = (double)ctx->screen_nonfinite;
+  info[5] = probe.band_t;
+  if (!probe.ran) return EPA_OK;
+  const uint32_t nseg = (ctx->B + 63) / 64, segp = (nseg + 7u) & ~7u;
+  unsigned long long n_incl = 0;
+  EPA_HIP(ctx, hipMemcpy(&n_incl, probe.n_incl, sizeof(n_incl), hipMemcpyDeviceToHost));
+  info[1] = probe.delta;
+  info[2] = (double)n_incl;
+  info[6] = probe.ms_screen;
+  info[7] = probe.ms_band;
+  if (seg_mask) EPA_HIP(ctx, hipMemcpy(seg_mask, probe.mask, sizeof(uint64_t) * Q, hipMemcpyDeviceToHost));
+  if (seg32) {   // keys -> values on the host (seg_key32 of preplace.hip); NaN where the screen left no key
+    std::vector<uint32_t> keys((size_t)Q * segp);
+    EPA_HIP(ctx, hipMemcpy(keys.data(), probe.seg32, sizeof(uint32_t) * keys.size(), hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < Q; ++q)
+      for (uint32_t s = 0; s < nseg; ++s) {
+        const uint32_t k = keys[(size_t)q * segp + s], u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
+        float v = NAN;
+        if (k) memcpy(&v, &u, 4);
+        seg32[(size_t)q * nseg + s] = v;
+      }
+  }
+  return EPA_OK;
 }
 
 extern "C" int epa_dev_thorough(epa_ctx* ctx, const epa_pair* pairs, uint64_t n_pairs,

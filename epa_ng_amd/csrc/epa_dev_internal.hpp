@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -104,7 +106,22 @@ struct PreTable {
   // paths of preplace.hip, which clears them first; read by k_select_seg of select.hip), or null: none wanted
   unsigned long long* segmax = nullptr;
   uint32_t segp = 0;
+  // > 0: the table's only reader will be k_select_seg with this band (epa_select_takes_seg): the preplacement may then
+  // leave unwritten every segment whose maximum lies further below the row maximum, given the key it writes for it
+  double band_t = 0.0;
 };
+
+// Band widths of the selection from segment maxima (k_select_seg, dynamic rule, threshold < 1): candidates lie within
+// band_x of the row maximum, terms that can move the LWR denominator within band_t.  The preplacement's screen
+// (preplace.hip) decides with the same band_t which table segments it has to fill.
+inline double epa_select_band_x(double threshold, uint32_t B) { return 1.0 - std::log((1.0 - threshold) / (double)B); }
+inline double epa_select_band_t(double threshold, uint32_t B) {
+  return std::max(epa_select_band_x(threshold, B), std::log((double)B) + 38.0);
+}
+
+// true: launch_select_begin reads table t (of Q rows) through k_select_seg, i.e. only the segments within band_t of a
+// row's maximum (select.hip)
+bool epa_select_takes_seg(const epa_ctx* ctx, const PreTable& t, uint32_t Q, double threshold);
 
 // state of a candidate selection between launch_select_begin and launch_select_end (select.hip)
 struct SelectPending {
@@ -273,6 +290,9 @@ struct EpaOptions {
   int newton_lds = 0;         // single-wave 4-state Newton kernels read their table through LDS instead of DPP
   int tip_distal = 1;         // pairs whose branch ends in a tip run the TIPD Newton kernels (0: the row form for all)
   int dedup_key_bits = 64;    // low bits kept of a query's dedup key (dedup.hip): fewer force unequal rows into one run
+  int preplace_screen = 1;    // the pair path's fp32 two-branch screen where its conditions hold (preplace.hip);
+                              // 2: also for chunks below its size condition (tests)
+  int preplace_screen_scale = 1;   // test only: the screen's error bound delta is multiplied by this
   int dedup_sort_bits = 32;   // low key bits the dedup sort looks at: rows equal there share a run, the full key and the codes part them
 };
 
@@ -315,6 +335,13 @@ struct epa_ctx {
   double* cinv = nullptr;     // +I only: [W] p * pi[invariant state of the site] (0 where not invariant)
   double inv_w0 = 0.0;        // 1 / w_0: folds cinv into the zero-eigenvalue sumtable entry (thorough)
   double* lookup2 = nullptr;  // DNA only: [B][2][ceil(W/2)][36] site-pair sums (preplace.hip, k_preplace_pairs)
+  // the screen's table: [ceil(B/2)][2][ceil(W/2)][36] float2 = lookup2's entries of branches 2p and 2p + 1 in fp32
+  // (k_build_lookup2f; null until launch_build_lookup2f), the largest finite |entry| and the number of non-finite ones
+  float2* lookup2f = nullptr;
+  bool lookup2f_refused = false;   // no memory for it: the one-pass preplacement stays
+  uint64_t screen_runs = 0;        // preplacements that took the two-pass route (epa_dev_preplace_screen_runs)
+  double screen_M = 0.0;
+  uint64_t screen_nonfinite = 0;
   // 4 states, reference built from the tree: tip_row [B] = the tip at the distal end of the branch (its row of tipmask)
   // or 0xffffffff, tipmask [tips][W] = the 4-bit state set of every tip character, tipd [16][4] = U^-1 (state set) --
   // what the TIPD instantiations of k_thorough_dna read instead of such a branch's distal block of refT
@@ -555,6 +582,23 @@ int launch_transform(epa_ctx* ctx, const double* d_clv_or_null, const uint8_t* d
                      const uint32_t* d_tipmap, uint32_t tipmap_size, double* dst);
 int launch_build_lookup(epa_ctx* ctx);
 int launch_build_lookup2(epa_ctx* ctx);  // DNA site-pair table from `lookup` (preplace.hip)
+// the fp32 branch-pair table of the screen from lookup2, with screen_M / screen_nonfinite (synchronises the stream)
+int launch_build_lookup2f(epa_ctx* ctx);
+// The screen's error bound for windows of at most span_bound sites: with u = 2^-24 and n gathered entries of magnitude
+// <= M, |fp32 sum - fp64 sum| <= (n + 1) u n M (every entry rounded once, n - 1 additions); delta is twice that, times
+// the option preplace_screen_scale.  < 0: no screen for this context (a non-finite entry, or delta > 1).
+double epa_screen_delta(const epa_ctx* ctx, uint32_t span_bound);
+// what a screen-only run of launch_preplace leaves behind (device pointers into SLOT_PREPLACE, valid until the bank's
+// next preplacement): the tests' and the measurements' view of the screen
+struct PreScreenProbe {
+  double band_t = 0.0;                   // in: the selection's band (launch_select_begin)
+  bool ran = false;                      // the screen's conditions held
+  double delta = 0.0;
+  const uint32_t* seg32 = nullptr;       // [Q][segp] seg_key32 of the fp32 segment maxima, 0 = none
+  const unsigned long long* mask = nullptr;    // [Q] included segments
+  const unsigned long long* n_incl = nullptr;  // their total
+  float ms_screen = -1.f, ms_band = -1.f;
+};
 // blocked layout: branches per block buffer in effect, its bytes (lookup rows first, lookup2 rows at *off2), the
 // current bank's buffer (allocated on first use) and the build of the tables of branches [b0, b0 + nb) into it
 uint32_t epa_block_branches(const epa_ctx* ctx);
@@ -564,8 +608,9 @@ int launch_build_lookup_block(epa_ctx* ctx, uint32_t b0, uint32_t nb, double* bl
 int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_lookup, double* blk_lookup2);
 // fills t.lnl (and, after clearing them, t.segmax when given); *d_status: the call's status words in SLOT_PREPLACE,
 // [0 .. 4) the window validation -- for preplace_check_status after a synchronisation, or for the selection's read-back
+// probe: run the fp32 screen and its band test INSTEAD of the table kernels and report them (t.lnl is not written)
 int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, uint32_t Q,
-                    const PreTable& t, uint32_t max_span, const uint32_t** d_status);
+                    const PreTable& t, uint32_t max_span, const uint32_t** d_status, PreScreenProbe* probe = nullptr);
 int preplace_check_status(epa_ctx* ctx, const uint32_t* d_status);
 __attribute__((visibility("hidden"))) int preplace_window_error(epa_ctx* ctx, const uint32_t* st);   // the two window-validation words -> error code and text
 // one workgroup: exclusive scan of cnt[0 .. K) in place; with tip_row also *tip_total = the sum over the first K - 1

@@ -48,7 +48,7 @@ constexpr int CW = CH / 4;   // packed code words per chunk
 struct Group {
   uint32_t start;      // first index into the sorted order
   uint32_t count;      // 0 = unused slot of the over-provisioned group table
-  uint32_t min_begin;  // bucket start (key space)
+  uint32_t min_begin;  // 0; groups of the exact pass's cells (k_screen_band): their 64-branch segment
   uint32_t cls;        // 0 = site-pair fast path (or the only class), 1 = generic kernel
 };
 
@@ -147,13 +147,16 @@ __global__ void __launch_bounds__(256) k_scatter_sorted(const uint32_t* __restri
 // k_pack_pairs: block = key / Wp, blocks >= class_blocks are class 1).  Every block is cut into
 // runs of gq0 (class 0) / gq1 (class 1) consecutive queries; a run whose window starts spread over
 // SPREAD sites or more (sparse data) is subdivided along the fixed SPREAD grid, so every group
-// fits the staged slice.
+// fits the staged slice.  n_dev (or null): the number of sorted entries when only the device knows it (at most Q);
+// seg_div (or 0): a group's min_begin = its first key / seg_div (the exact pass's cells: the segment, see k_screen_band).
 __global__ void __launch_bounds__(256) k_make_groups(const uint32_t* __restrict__ sorted_keys, uint32_t Q,
                                                      uint32_t Wp, uint32_t n_blocks,
                                                      uint32_t class_blocks, uint32_t gq0, uint32_t gq1,
                                                      uint32_t spr0, uint32_t max_runs, Group* __restrict__ groups,
-                                                     uint32_t max_groups, uint32_t* __restrict__ status) {
+                                                     uint32_t max_groups, uint32_t* __restrict__ status,
+                                                     const uint32_t* __restrict__ n_dev = nullptr, uint32_t seg_div = 0) {
   extern __shared__ uint32_t sh[];
+  if (n_dev) Q = min(Q, *n_dev);
   uint32_t* lo = sh;                       // [n_blocks + 1] first sorted index of each block
   uint32_t* runbase = lo + n_blocks + 1;   // [n_blocks + 1] first run of each block
   uint32_t* run_start = runbase + n_blocks + 1;  // [max_runs]
@@ -215,14 +218,14 @@ __global__ void __launch_bounds__(256) k_make_groups(const uint32_t* __restrict_
     const uint32_t cls = b >= class_blocks ? 1u : 0u;
     const uint32_t start = run_start[r], end = run_end[r], g0 = run_off[r], n = run_off[r + 1] - g0;
     if (n == 1) {
-      if (g0 < max_groups) groups[g0] = Group{start, end - start, 0, cls};
+      if (g0 < max_groups) groups[g0] = Group{start, end - start, seg_div ? sorted_keys[start] / seg_div : 0u, cls};
     } else {
       const uint32_t spr = cls ? (uint32_t)SPREAD : spr0;
       const uint32_t kb = sorted_keys[start] / spr;
       uint32_t a = start;
       for (uint32_t k = 0; k < n; ++k) {
         const uint32_t e = k + 1 == n ? end : lower_bound(a, end, (uint64_t)(kb + k + 1) * spr);
-        if (g0 + k < max_groups) groups[g0 + k] = Group{a, e - a, 0, cls};
+        if (g0 + k < max_groups) groups[g0 + k] = Group{a, e - a, (seg_div && e > a) ? sorted_keys[a] / seg_div : 0u, cls};
         a = e;
       }
     }
@@ -723,7 +726,10 @@ __device__ __forceinline__ uint32_t choose_tile(uint32_t ng, uint32_t B, uint32_
 // A/Bs in profiles/r5_preplace_duo_ab.txt, r5_preplace_prio_ab.txt): slices of consecutive branches alternating between
 // two LDS buffers with one barrier per branch (0.966 / 0.949 against 0.930 / 0.910 ms), and two branches staged and
 // gathered between one pair of barriers (1.018 / 1.011 ms) -- the gather phase is bound by the LDS itself.
-template <bool ACC, int SPR, int ROWL>
+// SPARSE (the exact pass behind the fp32 screen, below): groups are groups of (query, segment) CELLS of one segment
+// (Group::min_begin), perm holds a cell's query, an item is one group over the segment's 64 branches; staging, gathers,
+// bursts and segment maxima are the same code, so a cell's value is the one the full pass writes.
+template <bool ACC, int SPR, int ROWL, bool SPARSE = false>
 __global__ void __launch_bounds__(GQ2, 4) k_preplace_pairs(
     const double* __restrict__ lookup2, const uint16_t* __restrict__ packed,
     const uint16_t* __restrict__ tails, const uint32_t* __restrict__ win_begin,
@@ -740,15 +746,18 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_pairs(
   constexpr uint32_t BSTR = GQ2 + 4;    // burst staging rows 4 doubles apart in the banks: conflict-free
   // persistent grid over (group, branch tile) items of class 0, see k_preplace
   const uint32_t ng = status[5];
-  const uint32_t NBP = ACC ? NB2_ACC : choose_tile(ng, B, gridDim.x);
-  const uint32_t ntiles = (B + NBP - 1) / NBP;
+  const uint32_t NBP = SPARSE ? 64u : ACC ? NB2_ACC : choose_tile(ng, B, gridDim.x);
+  const uint32_t ntiles = SPARSE ? 1u : (B + NBP - 1) / NBP;
   const int t = threadIdx.x;
-  const ItemWalk iw = item_walk(ng * ntiles);
+  // SPARSE: plain striding.  The cells crowd into the few segments around the reads' placements, whose full groups are
+  // neighbours in the segment-major order, so no XCD's contiguous eighth should hold them all; traced, the walk is
+  // worth little (0.316 -> 0.306 ms per launch, profiles/r9_preplace_screen_ab.txt)
+  const ItemWalk iw = SPARSE ? ItemWalk{blockIdx.x, ng, gridDim.x, 0u} : item_walk(ng * ntiles);
   for (uint32_t item = iw.pos; item < iw.end; item += iw.step) {
-  uint32_t item_g, item_t;
-  item_group_tile(item, iw.lo, iw.end, ng, ntiles, item_g, item_t);
+  uint32_t item_g = item, item_t = 0;
+  if (!SPARSE) item_group_tile(item, iw.lo, iw.end, ng, ntiles, item_g, item_t);
   const Group g = groups[item_g];
-  const uint32_t b0 = item_t * NBP;
+  const uint32_t b0 = SPARSE ? min(g.min_begin * 64u, B - 1u) : item_t * NBP;
   const uint32_t nb = min(NBP, B - b0);
   __syncthreads();  // the previous item's readers of s_maxspan / accs / the tile are done
   if (g.count == 0) continue;
@@ -946,6 +955,278 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_pairs(
     for (uint32_t j = 0; j < nb; ++j) out[j] = accs[j * GQ2 + t];
   }
   }  // work items
+}
+
+// ---------------------------------------------------------------------------------------------
+// fp32 two-branch screen of the pair path ("fp32 screen").  The selection reads only the table segments
+// whose maximum lies within band_t of the row maximum; of every other segment it uses that one fact, which fp32 sums
+// decide as well once the band is widened by their error bound.  lookup2f holds, per PAIR of branches (2p, 2p + 1) and
+// in lookup2's own [parity][pair row][PE] layout, the two branches' entries rounded to fp32 side by side: an entry is
+// still 8 bytes, so the packed 16-bit LDS offsets, the staged slice and the groups are those of k_preplace_pairs, and
+// one ds_read_b64 + one packed add serve two (query, branch) cells.
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// order-preserving 32-bit key of a float (atomicMax on unsigned integers), 0 = nothing written: seg_key in fp32
+__device__ __forceinline__ uint32_t seg_key32(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float seg_val32(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
+
+// lookup2f[p][i] = {fl32(lookup2[2p][i]), fl32(lookup2[2p + 1][i])}, i over [parity][pair row][PE].  An odd tree's last
+// pair has no second branch: -inf everywhere but the exact-zero (none, none) slot, so its sums are -inf and raise no
+// maximum.  Rows past the alignment (odd W, parity 1) are never staged and hold zeros.  stats[0]: the largest |entry|
+// as float bits, stats[1]: the number of non-finite entries (either disables the screen's error bound, see screen_delta).
+__global__ void __launch_bounds__(256) k_build_lookup2f(const double* __restrict__ lookup2, uint32_t W, uint32_t B,
+                                                        float2* __restrict__ lookup2f, uint32_t p0,
+                                                        uint32_t* __restrict__ stats) {
+  const uint32_t p = p0 + blockIdx.y, Wh = (W + 1) / 2, n = 2 * Wh * PE;
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  float amax = 0.f;
+  uint32_t bad = 0;
+  if (i < n) {
+    const uint32_t par = i / (Wh * PE), rem = i - par * Wh * PE, r = rem / PE, e = rem - r * PE;
+    const bool valid = 2 * r + par < W, two = 2 * p + 1 < B;
+    float x = 0.f, y = 0.f;
+    if (valid) {
+      x = (float)lookup2[(size_t)(2 * p) * n + i];
+      y = two ? (float)lookup2[(size_t)(2 * p + 1) * n + i] : (e == PE - 1 ? 0.f : -INFINITY);
+      const bool fx = isfinite(x), fy = !two || isfinite(y);
+      bad = (fx ? 0u : 1u) + (fy ? 0u : 1u);
+      if (fx) amax = fabsf(x);
+      if (two && fy) amax = fmaxf(amax, fabsf(y));
+    }
+    lookup2f[(size_t)p * n + i] = make_float2(x, y);
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    amax = fmaxf(amax, __shfl_xor(amax, off));
+    bad += (uint32_t)__shfl_xor((int)bad, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (amax > 0.f) atomicMax(&stats[0], __float_as_uint(amax));   // non-negative floats order as their bits
+    if (bad) atomicAdd(&stats[1], bad);
+  }
+}
+
+// The screening pass: the item walk, slice staging, register prefetch, gather batches and priorities of
+// k_preplace_pairs<false, SPR, ROWL> over BP = ceil(B / 2) branch PAIRS, sums in fp32 in the same association, no result
+// rows: only the running maximum per query and 64-branch segment (32 pairs: a pair never straddles a segment) leaves,
+// as a seg_key32 by atomicMax into seg32 [Q][segp] (cleared by the caller).
+template <int SPR, int ROWL>
+__global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
+    const float2* __restrict__ lookup2f, const uint16_t* __restrict__ packed,
+    const uint16_t* __restrict__ tails, const uint32_t* __restrict__ win_begin,
+    const uint32_t* __restrict__ win_span, const uint32_t* __restrict__ perm,
+    const Group* __restrict__ groups, uint32_t W, uint32_t BP, uint32_t NP16,
+    const uint32_t* __restrict__ status, uint32_t* __restrict__ seg32, uint32_t segp) {
+  constexpr int TR2 = (CH + SPR) / 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [TR2] rows of PE float2, ROWL bytes apart
+  static_assert(ROWL % 16 == 0 && ROWL >= PROWB && ((TR2 - 1) * ROWL + PROWB) < 65536, "16-bit LDS offsets");
+  __shared__ uint32_t s_maxspan;
+  const uint32_t ng = status[5];
+  const uint32_t NBP = choose_tile(ng, BP, gridDim.x);   // branch pairs per item
+  const uint32_t ntiles = (BP + NBP - 1) / NBP;
+  const int t = threadIdx.x;
+  const ItemWalk iw = item_walk(ng * ntiles);
+  for (uint32_t item = iw.pos; item < iw.end; item += iw.step) {
+    uint32_t item_g, item_t;
+    item_group_tile(item, iw.lo, iw.end, ng, ntiles, item_g, item_t);
+    const Group g = groups[item_g];
+    const uint32_t b0 = item_t * NBP;
+    const uint32_t nb = min(NBP, BP - b0);
+    __syncthreads();  // the previous item's readers of s_maxspan / the slice are done
+    if (g.count == 0) continue;
+    const bool active = t < (int)g.count;
+    uint32_t qi = 0, begin = 0, span = 0;
+    if (active) {
+      qi = perm[g.start + t];
+      begin = win_begin[qi];
+      span = win_span[qi];
+      if ((uint64_t)begin + span > W) span = 0;
+    }
+    if (t == 0) s_maxspan = 0;
+    __syncthreads();
+    {
+      uint32_t m = span;
+#pragma unroll
+      for (int off = 32; off; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off));
+      if ((t & 63) == 0) atomicMax(&s_maxspan, m);
+    }
+    __syncthreads();
+    const uint32_t gmin = win_begin[perm[g.start]];
+    const uint32_t gspread = win_begin[perm[g.start + g.count - 1]] - gmin;  // < SPR
+    const uint32_t rowoff = ((begin - gmin) >> 1) * ROWL;
+    const uint32_t rowoff2 = rowoff | (rowoff << 16);
+    const bool mine = active && span > 0;
+    uint32_t t0 = 0, t1 = 0, t2 = 0;
+    if (mine && (span & 3)) {
+      const uint16_t* tq = tails + (size_t)qi * 4;
+      t0 = tq[0] + rowoff; t1 = tq[1] + rowoff; t2 = tq[2] + rowoff;
+    }
+    auto at = [&](uint32_t off) -> f2 { return *reinterpret_cast<const f2*>(smem + off); };
+    uint32_t cw[PW];
+    if (mine) {
+      const uint4* p = reinterpret_cast<const uint4*>(packed + (size_t)qi * NP16);
+#pragma unroll
+      for (int i = 0; i < PW / 4; ++i) {
+        const uint4 v = p[i];
+        cw[4 * i] = v.x + rowoff2;
+        cw[4 * i + 1] = v.y + rowoff2;
+        cw[4 * i + 2] = v.z + rowoff2;
+        cw[4 * i + 3] = v.w + rowoff2;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < PW; ++i) cw[i] = 0;
+    }
+    const uint32_t row0 = gmin;
+    const uint32_t need = min((uint32_t)TR2, (gspread >> 1) + (min((uint32_t)CH, s_maxspan) + 1) / 2);
+    const uint32_t rows = (row0 < W) ? min(need, (W - row0 + 1) / 2) : 0;
+    const uint32_t n2 = rows * (PE / 2);
+    constexpr int PF = (TR2 * (PE / 2) + GQ2 - 1) / GQ2;
+    auto request = [&](uint32_t j, float4 (&pfs)[PF]) {
+      const float4* src = reinterpret_cast<const float4*>(
+          lookup2f + (((size_t)(b0 + j) * 2 + (row0 & 1u)) * ((W + 1) / 2) + (row0 >> 1)) * PE);
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const uint32_t i = u * GQ2 + t;
+        pfs[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < n2) pfs[u] = src[i];
+      }
+    };
+    auto stage = [&](const float4 (&pfs)[PF]) {
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const uint32_t i = u * GQ2 + t;   // 16-byte index in the compact [rows][PE / 2] slice
+        if (i < n2) {
+          if (ROWL == PROWB) {
+            reinterpret_cast<float4*>(smem)[i] = pfs[u];
+          } else {
+            const uint32_t r = i / (PE / 2), c2 = i - r * (PE / 2);
+            *reinterpret_cast<float4*>(smem + r * ROWL + c2 * 16) = pfs[u];
+          }
+        }
+      }
+    };
+    float segm = -INFINITY;
+    auto gather = [&](uint32_t j) {
+      if (!mine) return;
+      f2 sum = {0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < PW; ++i) asm volatile("" : "+v"(cw[i]));   // keep the extracted addresses out of VGPRs (k_preplace_pairs)
+      constexpr int WPB = PP_WPB, NBATCH = PW / WPB;
+      f2 rb[2][WPB * 2];
+      auto issue = [&](int bt) {
+#pragma unroll
+        for (int w = 0; w < WPB; ++w) {
+          const uint32_t v = cw[bt * WPB + w];
+          rb[bt & 1][2 * w] = at(v & 0xffffu);
+          rb[bt & 1][2 * w + 1] = at(v >> 16);
+        }
+      };
+      issue(0);
+#pragma unroll
+      for (int bt = 0; bt < NBATCH; ++bt) {
+        gather_prio<NBATCH>(bt);
+        if (bt + 1 < NBATCH) issue(bt + 1);
+#pragma unroll
+        for (int w = 0; w < WPB; ++w) {
+          const f2 s1 = rb[bt & 1][2 * w] + rb[bt & 1][2 * w + 1];  // (a0+a1) + (a2+a3), both branches
+          sum += s1;
+        }
+      }
+      if (span & 3) {  // singles of the window tail, in order
+        sum += at(t0);
+        sum += at(t1);
+        sum += at(t2);
+      }
+      segm = fmaxf(segm, fmaxf(sum.x, sum.y));
+      const uint32_t bp = b0 + j;
+      if ((bp & 31u) == 31u || j + 1 == nb) {
+        atomicMax(&seg32[(size_t)qi * segp + (bp >> 5)], seg_key32(segm));
+        segm = -INFINITY;
+      }
+    };
+    float4 pf[PF];
+    request(0, pf);
+    for (uint32_t j = 0; j < nb; ++j) {
+      __syncthreads();  // previous consumers of the slice are done
+      stage(pf);
+      __syncthreads();
+      if (j + 1 < nb) request(j + 1, pf);
+      gather(j);
+    }
+  }  // work items
+}
+
+// Band test of the screen, one thread per query of the pair path (qkeys[q] < KB: class 0; the others keep full rows
+// from the generic kernel and all-zero keys).  r = the fp32 row maximum; segment s is INCLUDED when
+// seg32[s] >= r - band, band = band_t + 2 delta: with |seg32 - exact segment maximum| <= delta an excluded segment's exact
+// maximum lies more than band_t below the exact row maximum, so the selection never reads it, and the segment of the
+// exact maximum is always included.  An excluded segment gets the key of seg32 + delta in segmax -- finite, not 0,
+// below the selection's bands, so its masks come out as from the full table -- an included one stays 0 for the exact
+// pass's SegTrack.  Every included (query, segment) cell is counted under the key s * KB + the query's sort key
+// (ccnt; the old value is its rank among equal keys, as in k_count_keys) for the cell sort.  mask[q]: the included
+// segments (0: not a query of the screen), *n_incl += their number.
+__global__ void __launch_bounds__(256) k_screen_band(const uint32_t* __restrict__ seg32, uint32_t Q, uint32_t nseg,
+                                                     uint32_t seg32p, double band, double delta,
+                                                     const uint32_t* __restrict__ qkeys, uint32_t KB,
+                                                     unsigned long long* __restrict__ segmax, uint32_t segp,
+                                                     uint32_t* __restrict__ ccnt, uint32_t* __restrict__ rank,
+                                                     unsigned long long* __restrict__ mask,
+                                                     unsigned long long* __restrict__ n_incl) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  uint32_t cnt = 0;
+  if (q < Q) {
+    const uint32_t* row = seg32 + (size_t)q * seg32p;
+    const uint32_t qk = qkeys[q];
+    float r = -INFINITY;
+    bool all = qk < KB;
+    for (uint32_t s = 0; s < nseg; ++s) {
+      const uint32_t k = row[s];
+      if (k) r = fmaxf(r, seg_val32(k)); else all = false;
+    }
+    unsigned long long m = 0;
+    if (all) {   // every segment has its key: a query the screening kernel served
+      const double lo = (double)r - band;
+      for (uint32_t s = 0; s < nseg; ++s) {
+        const double v = (double)seg_val32(row[s]);
+        if (v >= lo) {
+          m |= 1ull << s;
+          if (ccnt) rank[(size_t)q * seg32p + s] = atomicAdd(&ccnt[s * KB + qk], 1u);
+        } else if (segmax) {
+          segmax[(size_t)q * segp + s] = seg_key(v + delta);
+        }
+      }
+    }
+    mask[q] = m;
+    cnt = (uint32_t)__popcll(m);
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, off);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_incl, (unsigned long long)cnt);
+}
+
+// the cells into sorted order (k_scatter_sorted for cells): offs = the scanned counts, perm[pos] = the cell's QUERY
+__global__ void __launch_bounds__(256) k_scatter_cells(const unsigned long long* __restrict__ mask,
+                                                       const uint32_t* __restrict__ qkeys, const uint32_t* __restrict__ rank,
+                                                       const uint32_t* __restrict__ offs, uint32_t Q, uint32_t seg32p,
+                                                       uint32_t KB, uint32_t ncell, uint32_t* __restrict__ sorted_keys,
+                                                       uint32_t* __restrict__ perm) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= Q) return;
+  unsigned long long m = mask[q];
+  const uint32_t qk = qkeys[q];
+  while (m) {
+    const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+    m &= m - 1;
+    const uint32_t key = s * KB + qk, pos = offs[key] + rank[(size_t)q * seg32p + s];
+    if (pos < ncell) {
+      sorted_keys[pos] = key;
+      perm[pos] = q;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1193,8 +1474,49 @@ int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_look
   return EPA_OK;
 }
 
+int launch_build_lookup2f(epa_ctx* ctx) {
+  if (ctx->lookup2f || ctx->lookup2f_refused) return EPA_OK;
+  if (!ctx->lookup2) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "the fp32 pair table needs the resident site-pair table");
+  const uint32_t BP = (ctx->B + 1) / 2, n = 2 * ((ctx->W + 1) / 2) * PE;
+  const size_t bytes = sizeof(float2) * (size_t)BP * n;
+  char* buf = nullptr;
+  // Best effort, and never the last memory of the device: epa_dev_footprint does not count this table and the chunk
+  // scratch is allocated after it, so it is only taken while SCREEN_RESERVE stays free behind it.
+  constexpr size_t SCREEN_RESERVE = (size_t)4 << 30;
+  size_t free_b = 0, total_b = 0;
+  const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= bytes + 16 + SCREEN_RESERVE;
+  if (!room || hipMalloc(&buf, bytes + 16) != hipSuccess) {   // (the two statistics words behind the table)
+    (void)hipGetLastError();       // no room for it: the context keeps the one-pass preplacement
+    ctx->lookup2f_refused = true;
+    return EPA_OK;
+  }
+  uint32_t* stats = reinterpret_cast<uint32_t*>(buf + bytes);
+  EPA_HIP(ctx, hipMemsetAsync(stats, 0, 16, ctx->stream));
+  for (uint32_t p0 = 0; p0 < BP; p0 += EPA_GRID_Y)
+    hipLaunchKernelGGL(k_build_lookup2f, dim3((n + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, BP - p0)), dim3(256), 0, ctx->stream,
+                       ctx->lookup2, ctx->W, ctx->B, reinterpret_cast<float2*>(buf), p0, stats);
+  uint32_t h[4] = {0, 0, 0, 0};
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) { (void)hipFree(buf); EPA_HIP(ctx, e); }
+  float m;
+  memcpy(&m, &h[0], 4);
+  ctx->screen_M = (double)m;
+  ctx->screen_nonfinite = h[1];
+  ctx->lookup2f = reinterpret_cast<float2*>(buf);
+  return EPA_OK;
+}
+
+double epa_screen_delta(const epa_ctx* ctx, uint32_t span_bound) {
+  if (!ctx->lookup2f || ctx->screen_nonfinite) return -1.0;
+  const double u = 0x1p-24, n = 2.0 * (span_bound >> 2) + 3.0;   // pair entries of the full quads + the tail singles
+  const double delta = 2.0 * (n + 1.0) * u * n * ctx->screen_M * (double)std::max(ctx->opt.preplace_screen_scale, 1);
+  return delta <= 1.0 ? delta : -1.0;
+}
+
 int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, uint32_t Q,
-                    const PreTable& t, uint32_t max_span, const uint32_t** d_status) {
+                    const PreTable& t, uint32_t max_span, const uint32_t** d_status, PreScreenProbe* probe) {
   double* const d_lnl = t.lnl;
   const uint32_t pitch = t.pitch, segp = t.segp;
   unsigned long long* const segmax = t.segmax;
@@ -1217,12 +1539,45 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
   (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                   (uint32_t*)nullptr, (uint32_t*)nullptr, Q, 0, 32, ctx->stream);
   uint32_t *status, *key_cnt, *iota, *sorted_keys, *perm, *keys;
+  // The two-pass route (fp32 screen -> band test and cell list -> exact pass over the included cells):
+  // the single-chunk pair path on the resident tables, when the table's only reader is the selection from segment
+  // maxima (t.band_t) -- or a probe of the screen alone -- and the table's error bound allows it (epa_screen_delta).
+  const uint32_t nseg = (ctx->B + 63) / 64, seg32p = (nseg + 7u) & ~7u;
+  const uint32_t KB = 2 * Wp, n_blocks_c = 2 * nseg;      // cell keys: (segment, start parity, window start)
+  const uint64_t max_cells = (uint64_t)Q * nseg;
+  const uint32_t Kc = nseg * KB + 1;                      // + one counter nobody counts under: the scan leaves the total there
+  const uint32_t max_runs_c = (uint32_t)std::min<uint64_t>((max_cells + GQ2 - 1) / GQ2 + n_blocks_c, 0xffffffu);
+  const uint32_t max_groups_c = max_runs_c + n_blocks_c * n_buckets;
+  const size_t smem_c = sizeof(uint32_t) * (2 * (n_blocks_c + 1) + 4 * (size_t)max_runs_c + 2);   // k_make_groups over the cells
+  double delta = -1.0;
+  // Worth it only for large chunks: the band test, the cell sort (a scan, a scatter, a single-workgroup k_make_groups) and
+  // the wider clear cost ~ 60 us per chunk whatever its size, and the table build ~ 5 ms once; the two passes gain ~ 0.16 ms
+  // per 10^8 cells.  Measured (profiles/r9_preplace_screen_ab.txt): + 2.2 % at 100 000 reads x 1021 branches, a LOSS at 5 000
+  // reads (- 2 .. - 11 %), nothing at 50 000.  Chunks below SCREEN_MIN_CELLS -- twice the break-even -- stay on one pass and
+  // never build the table (option preplace_screen = 2: no size condition, for the tests).
+  constexpr uint64_t SCREEN_MIN_CELLS = 80000000ull;
+  const bool big = ctx->opt.preplace_screen >= 2 || probe || (uint64_t)Q * ctx->B >= SCREEN_MIN_CELLS;
+  if (pairs && !blocked && nseg <= 64 && max_span != 0 && max_span <= (uint32_t)CH && ctx->opt.preplace_screen && big &&
+      (probe || (segmax && t.band_t > 0.0)) && max_cells < 0x80000000ull && smem_c <= 65536) {
+    // the context's first chunk that screens builds the fp32 table, once (a chunk of this size takes milliseconds itself)
+    const int brc = launch_build_lookup2f(ctx);
+    if (brc) return brc;
+    delta = epa_screen_delta(ctx, span_bound);
+  }
+  const bool screen = delta >= 0.0;
+  uint32_t *seg32, *cstatus, *ccnt, *crank, *csorted, *cperm;
+  unsigned long long *seg_mask, *n_incl;
+  Group* cgroups;
   Group* groups;
   uint16_t *packed, *tails;
   void* temp;
   auto layout = [&](Carver c) {   // SLOT_PREPLACE
     status = c.take<uint32_t>(64);   // 256 B
     key_cnt = c.take<uint32_t>(K);
+    seg32 = c.take<uint32_t>(screen ? (size_t)Q * seg32p : 0);   // cleared with the status words
+    n_incl = c.take<unsigned long long>(screen ? 1 : 0);
+    cstatus = c.take<uint32_t>(screen ? 64 : 0);           // k_make_groups over the cells: [4], [5] = their groups
+    ccnt = c.take<uint32_t>(screen ? Kc : 0);
     iota = c.take<uint32_t>(Q);      // the counting sort keeps the arrival ranks here
     sorted_keys = c.take<uint32_t>(Q);
     perm = c.take<uint32_t>(Q);
@@ -1230,6 +1585,11 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
     groups = c.take<Group>(max_groups);
     packed = c.take<uint16_t>((size_t)Q * NP16);
     tails = c.take<uint16_t>((pairs || sites) ? 4 * (size_t)Q : 0);
+    seg_mask = c.take<unsigned long long>(screen ? Q : 0);
+    crank = c.take<uint32_t>(screen ? (size_t)Q * seg32p : 0);
+    csorted = c.take<uint32_t>(screen ? max_cells : 0);
+    cperm = c.take<uint32_t>(screen ? max_cells : 0);
+    cgroups = c.take<Group>(screen ? max_groups_c : 0);
     temp = c.tail(temp_bytes);       // rocprim
     return c.off;
   };
@@ -1297,9 +1657,9 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
   // The preplacement kernels over nB branches whose tables start at lk / lk2 (the resident tables, or a block
   // buffer), table rows at lnl, segment maxima at sm: the whole tree at once, or one block of it.  Which workgroup sums
   // which (query, branch) cell follows nB (choose_tile, ntiles); a cell's summation order does not.
-  auto kernels = [&](const double* lk, const double* lk2, uint32_t nB, double* lnl, unsigned long long* sm) {
+  auto kernels = [&](const double* lk, const double* lk2, uint32_t nB, double* lnl, unsigned long long* sm, bool fast = true) {
     // persistent grids: every resident workgroup slot of the device, work items strided over them
-    if (k_fast) {
+    if (k_fast && fast) {
       const uint32_t tile = fast_acc ? (pairs ? NB2_ACC : NB2_ACC_S) : 16;   // single chunk: choose_tile, >= 16
       const dim3 grid_f((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ((nB + tile - 1) / tile), (uint64_t)ctx->n_cu));  // 1 per CU
       hipLaunchKernelGGL(k_fast, grid_f, dim3(GQ2), (uint32_t)lds_fast, ctx->stream, pairs ? lk2 : lk, (const uint16_t*)packed,
@@ -1316,6 +1676,62 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
     hipLaunchKernelGGL(k_generic, grid, dim3(GQ), (uint32_t)lds, ctx->stream, lk, d_codes, d_begin, d_span, perm, groups, ctx->W,
                        cstride, crel, nB, pitch, codes_bytes, want_cls, status, lnl);
   };
+  if (probe) probe->ran = screen;
+  if (probe && !screen) return EPA_OK;
+  if (screen) {
+    using ScreenKernel = decltype(&k_preplace_screen<SPREAD, ROWL_NARROW>);
+    const ScreenKernel k_screen = wide ? k_preplace_screen<SPREAD_WIDE, ROWL_PACKED> : k_preplace_screen<SPREAD, ROWL_NARROW>;
+    const FastKernel k_exact = wide ? k_preplace_pairs<false, SPREAD_WIDE, ROWL_PACKED, true> : k_preplace_pairs<false, SPREAD, ROWL_NARROW, true>;
+    const size_t lds_scr = wide ? (size_t)((CH + SPREAD_WIDE) / 2) * ROWL_PACKED : (size_t)TROWS2 * ROWL_NARROW;
+    EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_screen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scr));
+    EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast));
+    const uint32_t BP = (ctx->B + 1) / 2;
+    struct Events {   // the probe's three stamps, destroyed on every way out
+      hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+      ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } evs;
+    hipEvent_t* const ev = evs.e;
+    if (probe) for (hipEvent_t& e : evs.e) EPA_HIP(ctx, hipEventCreate(&e));
+    if (probe) EPA_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+    else epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
+    const dim3 grid_s((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ((BP + 15) / 16), (uint64_t)ctx->n_cu));
+    hipLaunchKernelGGL(k_screen, grid_s, dim3(GQ2), (uint32_t)lds_scr, ctx->stream, (const float2*)ctx->lookup2f, (const uint16_t*)packed,
+                       (const uint16_t*)tails, d_begin, d_span, perm, groups, ctx->W, BP, NP16, status, seg32, seg32p);
+    if (probe) EPA_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+    const double band = (probe ? probe->band_t : t.band_t) + 2.0 * delta;
+    hipLaunchKernelGGL(k_screen_band, dim3((Q + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)seg32, Q, nseg, seg32p, band,
+                       delta, (const uint32_t*)keys, KB, probe ? nullptr : segmax, segp, probe ? nullptr : ccnt, crank, seg_mask, n_incl);
+    if (probe) {
+      EPA_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+      EPA_HIP(ctx, hipGetLastError());
+      EPA_HIP(ctx, hipEventSynchronize(ev[2]));
+      (void)hipEventElapsedTime(&probe->ms_screen, ev[0], ev[1]);
+      (void)hipEventElapsedTime(&probe->ms_band, ev[1], ev[2]);
+      probe->delta = delta;
+      probe->seg32 = seg32;
+      probe->mask = seg_mask;
+      probe->n_incl = n_incl;
+      return EPA_OK;
+    }
+    ++ctx->screen_runs;
+    // the included cells sorted by (segment, start parity, window start) and cut into groups of one segment: the
+    // queries' own counting sort and grouping, over cells (ranks by atomics as there: which lane a cell lands on
+    // varies, its sums do not)
+    launch_scan_counts(ctx, ccnt, Kc);
+    hipLaunchKernelGGL(k_scatter_cells, dim3((Q + 255) / 256), dim3(256), 0, ctx->stream, (const unsigned long long*)seg_mask,
+                       (const uint32_t*)keys, (const uint32_t*)crank, (const uint32_t*)ccnt, Q, seg32p, KB, (uint32_t)max_cells, csorted, cperm);
+    hipLaunchKernelGGL(k_make_groups, dim3(1), dim3(256), smem_c, ctx->stream, (const uint32_t*)csorted, (uint32_t)max_cells, Wp, n_blocks_c,
+                       n_blocks_c, (uint32_t)GQ2, (uint32_t)GQ2, (uint32_t)(wide ? SPREAD_WIDE : SPREAD), max_runs_c, cgroups, max_groups_c,
+                       cstatus, (const uint32_t*)(ccnt + (Kc - 1)), KB);
+    // exact pass: one item per group of cells, the 64 branches of its segment; groups dealt out in turn (see the kernel)
+    hipLaunchKernelGGL(k_exact, dim3(std::min<uint32_t>(max_groups_c, (uint32_t)ctx->n_cu)), dim3(GQ2), (uint32_t)lds_fast, ctx->stream,
+                       (const double*)ctx->lookup2, (const uint16_t*)packed, (const uint16_t*)tails, d_begin, d_span, (const uint32_t*)cperm,
+                       (const Group*)cgroups, ctx->W, ctx->B, pitch, NP16, (const uint32_t*)cstatus, d_lnl, segmax, segp);
+    kernels(ctx->lookup, ctx->lookup2, ctx->B, d_lnl, segmax, false);   // the queries with rare ambiguity codes: full rows
+    epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
+    EPA_HIP(ctx, hipGetLastError());
+    return EPA_OK;
+  }
   if (!blocked) {
     epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
     kernels(ctx->lookup, ctx->lookup2, ctx->B, d_lnl, segmax);

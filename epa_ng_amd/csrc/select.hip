@@ -735,6 +735,17 @@ void emit_pairs(epa_ctx* ctx, const SelectPending* sp) {
 //          `rb` (pinned host memory for a truly asynchronous copy; 64 words) -- no synchronisation;
 //   end    waits for the stream, widens the staging rows and repeats on overflow (rare), then queues
 //          compaction, the stable sort into Work order and the key -> pair conversion.
+// the bitmap form (SelOut) unless the bitmap is over 64 MB, or the option select_sort asks for the staging form
+static bool select_bitmap_form(const epa_ctx* ctx, uint32_t Q) {
+  return !ctx->opt.select_sort && (size_t)ctx->B * ((Q + 31) / 32) * sizeof(uint32_t) <= ((size_t)64 << 20);
+}
+
+bool epa_select_takes_seg(const epa_ctx* ctx, const PreTable& t, uint32_t Q, double threshold) {
+  // (A/B and test switch select_full_rows: the full-row kernels)
+  return select_bitmap_form(ctx, Q) && t.segmax && !ctx->opt.select_full_rows && ctx->heur_mode == 0 && threshold < 1.0 &&
+         (ctx->B + 63) / 64 <= 64;
+}
+
 int launch_select_begin(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_status, uint32_t Q, double threshold,
                         epa_pair* d_pairs, uint64_t max_pairs, const uint32_t* d_span, uint32_t* rb, SelectPending* sp) {
   sp->have_hist = false;
@@ -758,9 +769,8 @@ int launch_select_begin(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_sta
   const size_t worst = std::min<uint64_t>(max_pairs, (uint64_t)Q * cap);
   (void)rocprim::radix_sort_keys<epa_radix_cfg>(nullptr, sort_bytes, (unsigned long long*)nullptr,
                                  (unsigned long long*)nullptr, worst, 0, 64, ctx->stream);
-  // the bitmap form (SelOut) unless the bitmap is over 64 MB, or the option select_sort asks for the staging form
   const uint32_t wpr = (Q + 31) / 32;
-  const bool bm = !ctx->opt.select_sort && (size_t)B * wpr * sizeof(uint32_t) <= ((size_t)64 << 20);
+  const bool bm = select_bitmap_form(ctx, Q);
   uint32_t* status = nullptr;
   size_t fill = 0;
   auto layout = [&](Carver c) {   // SLOT_SELECT, either form behind the status block
@@ -800,11 +810,9 @@ int launch_select_begin(epa_ctx* ctx, const PreTable& t, const uint32_t* pre_sta
   // The selection kernel for this tree and rule, writing through `so`; true: it summed the span-class histogram itself
   auto select_rows = [&](const SelOut& so) -> bool {
     const int nr = (int)((B + 63) / 64);
-    // A/B and test switch select_full_rows: the full-row kernels
-    if (so.bitmap && t.segmax && !ctx->opt.select_full_rows && mode == 0 && threshold < 1.0 && nr <= 64) {
+    if (so.bitmap && epa_select_takes_seg(ctx, t, Q, threshold)) {
       // band widths of the segment test (see k_select_seg): conservative margins, so the host's log is as good as the device's
-      const double band_x = 1.0 - std::log((1.0 - threshold) / (double)B);
-      const double band_t = std::max(band_x, std::log((double)B) + 38.0);
+      const double band_x = epa_select_band_x(threshold, B), band_t = epa_select_band_t(threshold, B);
       constexpr uint32_t sel_grid = 16;   // workgroups per CU of the persistent selection grid
       const dim3 grid_seg(std::min<uint32_t>((Q + 3) / 4, (uint32_t)ctx->n_cu * sel_grid));
       hipLaunchKernelGGL(k_select_seg<8>, grid_seg, dim3(256), 0, ctx->stream, d_lnl, t.segmax, t.segp, Q, B, pitch, threshold,

@@ -248,6 +248,16 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
  *   "dedup_sort_bits"   n: the low key bits its sort looks at, n = 0 .. 64 (default 32: four digit passes; rows that agree
  *                          there share a run and are parted by the full key first, then by their codes).  Classes do not
  *                          depend on it either
+ *   "preplace_screen"   0: the chunk body's 4-state preplacement always fills the whole table in one pass (default 1: where
+ *                          the selection reads by segment maxima -- dynamic rule, threshold < 1, at most 4096 branches,
+ *                          resident tables, windows of one chunk -- and the chunk is large enough to pay for it -- reads x
+ *                          branches >= 8e7, and at most ~ 4 million (read, 64-branch segment) cells, the limit of the cell
+ *                          grouping's run table -- an fp32 pass over branch pairs finds the 64-branch segments that can
+ *                          matter and only those are summed exactly; same candidates, same results.  2: the same without
+ *                          the lower size condition, for tests.  The first screening chunk builds an fp32 table of half
+ *                          the site-pair table's size, if 4 GiB stay free behind it)
+ *   "preplace_screen_scale" n: test only, the screen's error bound is multiplied by n >= 1 (default 1); a bound above
+ *                          1 lnL unit turns the screen off for the context
  * Unknown key: EPA_ERR_INVALID_ARG.
  */
 int epa_dev_set_option(epa_ctx* ctx, const char* key, int value);
@@ -361,6 +371,19 @@ int epa_dev_preplace(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_b
  * inverted, else the sign bit set), 0 = not written (query served by another kernel, or max_span not bounded). */
 int epa_dev_preplace_bounded(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
                              const uint32_t* win_span, uint32_t Q, uint32_t max_span, double* lnl, uint64_t* seg_keys);
+
+/* Internal (tests and measurements): the fp32 two-branch screen of the pair preplacement and its band test, run alone on
+ * the queries of one chunk.  seg32 [Q][nseg] (or null): the fp32 maxima of the 64-branch segments, NaN where
+ * the screen left none (a query of the generic kernel); seg_mask [Q] (or null): the segments the exact pass has to fill
+ * for the dynamic rule at `threshold`; info [8]: 0 the screen ran (its conditions: 4 states, resident tables, max_span
+ * of at most one chunk, at most 4096 branches, a finite table, delta <= 1, option "preplace_screen"), 1 delta, 2 the
+ * number of included (query, segment) cells, 3 the table's largest |entry|, 4 its non-finite entries, 5 band_t,
+ * 6 / 7 the screening and the band kernel's time in ms. */
+int epa_dev_preplace_screen_probe(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
+                                  const uint32_t* win_span, uint32_t Q, uint32_t max_span, double threshold,
+                                  float* seg32, uint64_t* seg_mask, double* info);
+/* Internal (tests): the number of chunk bodies of this context whose preplacement took the screen's two-pass route. */
+uint64_t epa_dev_preplace_screen_runs(const epa_ctx* ctx);
 
 /*
  * Replaces place_thorough() (src/core/place.cpp:97-171) = Tiny_Tree::place with opt_branches
