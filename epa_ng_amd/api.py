@@ -128,6 +128,9 @@ def dev_lib():
         L.epa_dev_rell_au.argtypes = L.epa_dev_rell_support.argtypes[:-1] + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                                              C.c_void_p]
         L.epa_dev_rell_kh.argtypes = L.epa_dev_rell_tests.argtypes
+        L.epa_dev_set_topology.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.epa_dev_edpl.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                   C.c_void_p]
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -671,6 +674,35 @@ class Evaluator:
                                            int(replicates), int(seed), _ptr(out.get("p_kh")), _ptr(out.get("p_wkh")),
                                            _ptr(out.get("p_wsh"))))
         return out
+
+    # ---- tree geometry (include/epa_dev.h, epa_dev_set_topology / epa_dev_edpl)
+    def set_topology(self, node_prox, node_dist, n_nodes=None):
+        """attaches the tree's topology to the context: node_prox[b] / node_dist[b] are the node ids at the proximal and
+        the distal end of branch b, in score_at's orientation (distal lengths are measured from node_dist[b]).
+        n_nodes None: B + 1, what a tree has.  The root of the depths is node_prox[0]; a second call replaces the first."""
+        host = (np.ndarray, list, tuple)
+        node_prox, node_dist = (np.ascontiguousarray(a, dtype=np.uint32) if isinstance(a, host) else a
+                                for a in (node_prox, node_dist))
+        if isinstance(node_prox, np.ndarray) and isinstance(node_dist, np.ndarray) and not len(node_prox) == len(node_dist) == self.B:
+            raise ValueError("set_topology: node_prox and node_dist must have one entry per branch (%d)" % self.B)
+        n_nodes = self.B + 1 if n_nodes is None else int(n_nodes)
+        self._check(self.L.epa_dev_set_topology(self.h, n_nodes, _ptr(node_prox), _ptr(node_dist)))
+
+    def edpl(self, pairs, distal, weight, Q, row_dist=False, out=None, row_out=None):
+        """expected distance between placement locations (epa_dev_edpl) -> edpl float64 [Q], or (edpl, row_dist [n]) with
+        row_dist=True: per query the sum over its entries i, j of weight_i weight_j d_ij, d_ij the path length between
+        the attachment points (pairs[i].branch_id, distal[i]); row_dist[i] = sum_j weight_j d_ij.  Needs set_topology().
+        Host arrays are converted to float64; device buffers pass as is (out / row_out may be device buffers)."""
+        n = len(pairs)
+        host = (np.ndarray, list, tuple)
+        distal, weight = (np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, host) else a for a in (distal, weight))
+        if out is None:
+            out = np.empty(int(Q), np.float64)
+        if row_dist and row_out is None:
+            row_out = np.empty(n, np.float64)
+        self._check(self.L.epa_dev_edpl(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, int(Q),
+                                        _ptr(row_out) if row_dist else None, _ptr(out)))
+        return (out, row_out) if row_dist else out
 
     # ---- profile queries (include/epa_dev.h, "Profile queries"): prof is float64 [Q][stride][states] -- numpy on the
     # host or a torch cuda tensor -- holding the per-state likelihoods of every window position; the rows from a

@@ -748,6 +748,7 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
   if (ctx->lookup2) (void)hipFree(ctx->lookup2);
   if (ctx->lookup2f) (void)hipFree(ctx->lookup2f);
   if (ctx->prof_tab) (void)hipFree(ctx->prof_tab);
+  epa_topology_free(ctx);
   for (void* p : ctx->blk_buf) if (p) (void)hipFree(p);
   for (auto& v : ctx->blk_ev) for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e);
   if (ctx->th_ctr) (void)hipFree(ctx->th_ctr);
@@ -2379,6 +2380,7 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "rell_kh")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_RELL_KH]][epa_ctx::T_RELL_KH];
   else if (!strcmp(which, "preplace_profile")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_PREPLACE_PROFILE]][epa_ctx::T_PREPLACE_PROFILE];
   else if (!strcmp(which, "dedup")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_DEDUP]][epa_ctx::T_DEDUP];
+  else if (!strcmp(which, "edpl")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_EDPL]][epa_ctx::T_EDPL];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

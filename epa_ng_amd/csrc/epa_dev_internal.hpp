@@ -349,6 +349,8 @@ struct epa_ctx {
   uint8_t* tipmask = nullptr;
   double* tipd = nullptr;
   bool lookup_built = false;
+  // the tree's geometry (treepath.hip), or null: set by epa_dev_set_topology, read by epa_dev_edpl alone
+  struct EpaTopology* topo = nullptr;
   // profile queries (profile.hip): [B][s + 1][W] per (branch, site) exp(T_m - T_any) of the lookup table's pure-state
   // columns and, as component s, T_any itself; derived from `lookup` on the first profile preplacement (resident layout)
   double* prof_tab = nullptr;
@@ -363,7 +365,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 26;   // named by EpaSlot below
+  static constexpr int N_SCRATCH = 27;   // named by EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -388,7 +390,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, N_TIMERS = 12 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, T_EDPL = 12, N_TIMERS = 13 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -414,6 +416,9 @@ struct epa_ctx {
   int t_last[N_TIMERS] = {};
   epa_thorough_stats last_stats{};
 };
+
+// releases the context's topology, if any (treepath.hip)
+__attribute__((visibility("hidden"))) void epa_topology_free(epa_ctx* ctx);
 
 // ---- helpers (epa_dev.hip)
 int epa_fail(epa_ctx* ctx, int code, const std::string& msg);
@@ -473,7 +478,8 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
 // ---- scratch slots of a bank (epa_scratch / epa_to_device).  0 .. 12: the placement path (epa_dev.hip and the
 // launchers of preplace.hip, select.hip, thorough_*.hip); 0 .. 4, 7 .. 9 and 13 .. 20: the post-placement entry points
 // (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au, _rell_kh) and their launchers
-// (score_at.hip, marginal.hip, rell.hip); 21 .. 22: profile queries; 23 .. 25: duplicate queries (dedup.hip).  Names that share a
+// (score_at.hip, marginal.hip, rell.hip); 21 .. 22: profile queries; 23 .. 25: duplicate queries (dedup.hip); 26: path
+// distances (treepath.hip).  Names that share a
 // number never hold live data at the same time:
 //   2   the tip map is read only by the transform kernels of epa_dev_create, queued before any call can stage a span
 //       (SLOT_CLV_*, SLOT_SCALER_*: creation only, in the same way)
@@ -534,6 +540,9 @@ enum EpaSlot : int {
   SLOT_DEDUP_IN = 24,     //   the chunk's codes | win_begin | win_span where the caller's live on the host (the chunk body behind
                           //   the pass stages the compacted chunk in 0 .. 2 and 10)
   SLOT_DEDUP_ROWS = 25,   //   the compacted chunk: codes | win_begin | win_span of the representatives, then rep | first for host callers
+  SLOT_WEIGHT = 7,        // epa_dev_edpl (treepath.hip): weight [n]; its pairs and distal lengths in 4 and 8, its grouping in
+                          //   13 and 14 as the RELL calls keep theirs, its host outputs in 3: a call of its own
+  SLOT_EDPL = 26,         //   [status 256 bytes | D n | weight n | per-entry sums n | Euler index n], in grouped order
 };
 
 // The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,
@@ -658,6 +667,16 @@ struct RellDraws {
   uint32_t replicates;
   uint64_t seed;
 };
+// The entries of a call grouped by query (rell.hip): a stable radix sort of the entry indices by seq_id, so a group keeps
+// the caller's entry order.  sorted [n]: the seq_ids in grouped order; order [n]: grouped position -> entry; bounds
+// [2][Q]: first and one-past-last grouped position of every query that has entries, 0 and 0 for the others (a seq_id >= Q
+// owns no run); extra: extra_arrays x n further words of the same allocation for the caller (256-byte pitch), or null.
+// SLOT_RELL_SORT and SLOT_RELL_BOUNDS; queued on the context's stream, nothing is waited for
+struct EntryGroups {
+  uint32_t *sorted, *order, *bounds, *extra;
+};
+__attribute__((visibility("hidden"))) int launch_group_entries(epa_ctx* ctx, const epa_pair* d_pairs, uint32_t n, uint32_t Q,
+                                                               uint32_t extra_arrays, EntryGroups* g);
 // bootstrap support [n]
 int launch_rell(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support);
 // support, expected likelihood weights and SH p-values from the same replicates; each output [n] or null

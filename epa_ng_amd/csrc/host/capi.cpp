@@ -88,6 +88,17 @@ int epa_host_ref_numbered_newick(void* h, unsigned precision, char* out, size_t 
   return (int)s.size();
 }
 
+// host only: the node ids at both ends of every branch (Tree::fill_topology), prox / dist [branches]; returns the number
+// of nodes, tips first
+uint32_t epa_host_ref_topology(void* h, uint32_t* prox, uint32_t* dist) {
+  const Tree& t = *static_cast<Ref*>(h)->tree;
+  std::vector<uint32_t> p, d;
+  t.fill_topology(p, d);
+  std::memcpy(prox, p.data(), sizeof(uint32_t) * p.size());
+  std::memcpy(dist, d.data(), sizeof(uint32_t) * d.size());
+  return t.nums().nodes;
+}
+
 // model descriptor scraped from a model file (src/util/parse_model.hpp); returns the length, or
 // -needed if `cap` is too small, or INT_MIN on error (epa_host_last_error)
 int epa_host_parse_model(const char* file, char* out, size_t cap) {

@@ -81,6 +81,7 @@ struct Options {  // defaults: src/util/Options.hpp:13-34
   bool posterior = false;            // --posterior (with --rescore): marginal_like and post_prob of every row
   double prior_mean = 0.0;           // --prior-mean: mean of the pendant length's exponential prior; 0: the tree's mean branch length
   unsigned int posterior_kx = 8, posterior_kp = 16;   // --posterior-nodes KX,KP: Gauss-Legendre x Gauss-Laguerre nodes
+  bool edpl = false;                 // --edpl (with --rescore): exp_dist of every row and the object's edpl
 };
 
 class Sequence {
@@ -154,10 +155,15 @@ public:
   void marginal_like(double v) { marginal_like_ = v; }
   double post_prob() const { return post_prob_; }
   void post_prob(double v) { post_prob_ = v; }
+  double exp_dist() const { return exp_dist_; }   // --rescore --edpl only
+  void exp_dist(double v) { exp_dist_ = v; }
+  double edpl() const { return edpl_; }
+  void edpl(double v) { edpl_ = v; }
 private:
   size_t branch_id_ = 0;
   double likelihood_ = 0, lwr_ = 0, pendant_length_ = 0, distal_length_ = 0, rell_support_ = 0;
   double marginal_like_ = 0, post_prob_ = 0, elw_ = 0, p_sh_ = 0, p_au_ = 0, p_kh_ = 0, p_wkh_ = 0, p_wsh_ = 0;
+  double exp_dist_ = 0, edpl_ = 0;
 };
 
 class PQuery {  // src/sample/PQuery.hpp:12-92
@@ -308,6 +314,10 @@ public:
     std::vector<double> len_a, len_b, blen;
   };
   void fill_tree_desc(epa_tree_desc& d, Tree_Desc_Storage& store) const;
+  // the node ids at the proximal and the distal end of every branch, in branch_id order and in fill_tree_desc's
+  // orientation (a tip is the DISTAL end): tip t is node t, the inner nodes follow from tip_nodes on; nodes() ids in
+  // all.  What epa_dev_set_topology takes
+  void fill_topology(std::vector<uint32_t>& prox, std::vector<uint32_t>& dist) const;
   // host CLVs are computed on first use (Tree::branch / ref_tree_logl / fill_desc): the device
   // path of the product never needs them
   void ensure_host_clvs() const;
@@ -414,8 +424,9 @@ size_t format_fixed(char* buf, size_t cap, double v, unsigned int precision);
 // optional row fields behind pendant_length, written in this order and named in "fields": kJplaceRell
 // "rell_support" (Placement::rell_support), kJplaceRellTests "elw", "p_sh", kJplaceAu "p_au", kJplaceKh "p_kh", "p_wkh",
 // "p_wsh", kJplacePosterior
-// "marginal_like", "post_prob".  0: the five standard fields
-enum Jplace_Fields : unsigned int { kJplaceRell = 1u, kJplacePosterior = 2u, kJplaceRellTests = 4u, kJplaceAu = 8u, kJplaceKh = 16u };
+// "marginal_like", "post_prob", kJplaceEdpl "exp_dist", "edpl".  0: the five standard fields
+enum Jplace_Fields : unsigned int { kJplaceRell = 1u, kJplacePosterior = 2u, kJplaceRellTests = 4u, kJplaceAu = 8u, kJplaceKh = 16u,
+                                    kJplaceEdpl = 32u };
 void write_jplace(std::ostream& os, const std::vector<Sample>& chunks, const std::string& newick,
                   const std::string& invocation, unsigned int precision,
                   const Rtree_Mapper* mapper = nullptr, unsigned int extra = 0);
@@ -448,6 +459,8 @@ public:
   std::vector<epa_result>& result_buffer() { return res_buf_; }
   uint64_t& pair_capacity() { return pair_cap_; }  // candidate capacity the chunk pipeline last needed
   double ref_tree_logl(size_t branch = 0) const;  // Tree::ref_tree_logl evaluated on the device
+  // the tree's topology attached to the context (epa_dev_set_topology): only the caller that wants path distances pays
+  void set_topology(const Tree& tree);
   // lookup layout the context came out with (epa_dev_lookup_mode): blocks, branches per block (0: resident)
   bool lookup_blocks() const;
   uint32_t lookup_block() const;

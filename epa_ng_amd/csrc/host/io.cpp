@@ -670,8 +670,8 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
   const int nt_max = std::max(1, configure_host_threads());
   const long n = (long)sample.size();
   const bool rell = extra & kJplaceRell, tests = extra & kJplaceRellTests, au = extra & kJplaceAu,
-             kh = extra & kJplaceKh, posterior = extra & kJplacePosterior;
-  const int n_vals = 4 + (rell ? 1 : 0) + (tests ? 2 : 0) + (au ? 1 : 0) + (kh ? 3 : 0) + (posterior ? 2 : 0);
+             kh = extra & kJplaceKh, posterior = extra & kJplacePosterior, edpl = extra & kJplaceEdpl;
+  const int n_vals = 4 + (rell ? 1 : 0) + (tests ? 2 : 0) + (au ? 1 : 0) + (kh ? 3 : 0) + (posterior ? 2 : 0) + (edpl ? 2 : 0);
   // one contiguous buffer per thread over a contiguous range of pqueries (no string per pquery: 50 000 small heap
   // blocks per chunk were a third of this stage), every placement line assembled in a stack buffer with pointer bumps
   std::vector<std::string> part((size_t)nt_max);
@@ -699,13 +699,14 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
         char* w = line;
         std::memcpy(w, "      [", 7); w += 7;
         w = std::to_chars(w, line + 64, edge).ptr;
-        double vals[13] = {p.likelihood(), p.lwr(), distal, p.pendant_length()};
+        double vals[15] = {p.likelihood(), p.lwr(), distal, p.pendant_length()};
         int nv = 4;
         if (rell) vals[nv++] = p.rell_support();
         if (tests) { vals[nv++] = p.elw(); vals[nv++] = p.p_sh(); }
         if (au) vals[nv++] = p.p_au();
         if (kh) { vals[nv++] = p.p_kh(); vals[nv++] = p.p_wkh(); vals[nv++] = p.p_wsh(); }
         if (posterior) { vals[nv++] = p.marginal_like(); vals[nv++] = p.post_prob(); }
+        if (edpl) { vals[nv++] = p.exp_dist(); vals[nv++] = p.edpl(); }
         for (int k = 0; k < n_vals; ++k) {
           *w++ = ','; *w++ = ' ';
           w += format_fixed(w, (size_t)(line + sizeof(line) - w) - 8, vals[k], precision);
@@ -747,7 +748,8 @@ void write_jplace_text(std::ostream& os, const std::vector<std::string>& chunk_t
      << (extra & kJplaceRellTests ? ", \"elw\", \"p_sh\"" : "")
      << (extra & kJplaceAu ? ", \"p_au\"" : "")
      << (extra & kJplaceKh ? ", \"p_kh\", \"p_wkh\", \"p_wsh\"" : "")
-     << (extra & kJplacePosterior ? ", \"marginal_like\", \"post_prob\"" : "") << "]\n}\n";
+     << (extra & kJplacePosterior ? ", \"marginal_like\", \"post_prob\"" : "")
+     << (extra & kJplaceEdpl ? ", \"exp_dist\", \"edpl\"" : "") << "]\n}\n";
 }
 
 void write_jplace(std::ostream& os, const std::vector<Sample>& chunks, const std::string& newick,

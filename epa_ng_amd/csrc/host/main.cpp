@@ -60,6 +60,11 @@ static void usage() {
       "                        (after \"rell_support\", \"elw\", \"p_sh\", \"p_au\", \"p_kh\" .. when --rell, --rell-tests, --au, --kh are given).  Only edge_num of a row enters them\n"
       "  --prior-mean M        mean of the pendant prior (default: the mean branch length of the reference tree)\n"
       "  --posterior-nodes KX,KP  Gauss-Legendre nodes along the edge x Gauss-Laguerre pendant nodes, 1 .. 64 each (default 8,16)\n"
+      "  --edpl                with --rescore: the expected distance between placement locations (EDPL, Matsen et al.): are the\n"
+      "                        rows of an object neighbours or on opposite sides of the tree?  Two more fields after all others:\n"
+      "                        \"exp_dist\", the like_weight_ratio-weighted mean path distance from the row's attachment point to\n"
+      "                        the rows of its object, and \"edpl\", the object's value (the weighted mean of exp_dist), repeated\n"
+      "                        on each of its rows.  Weights are the recomputed like_weight_ratios; pendant lengths do not enter\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -143,6 +148,7 @@ int main(int argc, char** argv) {
     else if (a == "--au") opt.au = true;
     else if (a == "--kh") opt.kh = true;
     else if (a == "--posterior") opt.posterior = true;
+    else if (a == "--edpl") opt.edpl = true;
     else if (a == "--prior-mean") {
       const std::string v = need(i);
       char* end = nullptr;
@@ -209,6 +215,10 @@ int main(int argc, char** argv) {
     else if (a == "--redo" || a == "--verbose") {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else { std::cerr << "option " << a << " is outside the placement hot path of this build\n"; return 1; }
+  }
+  if (opt.edpl && rescore_file.empty()) {   // before anything else: no file is read, no device opened
+    std::cerr << "--edpl works on an existing result: place first, then run again with --rescore out.jplace --edpl\n";
+    return 1;
   }
   if (tree_file.empty() || ref_file.empty() || query_file.empty()) { usage(); return 1; }
   // the reference's CLI checks (src/main.cpp:165-218, 368-370)

@@ -127,6 +127,13 @@ double Device_Evaluator::ref_tree_logl(size_t branch) const {
   return v;
 }
 
+void Device_Evaluator::set_topology(const Tree& tree) {
+  std::vector<uint32_t> prox, dist;
+  tree.fill_topology(prox, dist);
+  const int rc = epa_dev_set_topology(ctx_, tree.nums().nodes, prox.data(), dist.data());
+  if (rc != EPA_OK) throw_dev(ctx_, rc);
+}
+
 Device_Evaluator::~Device_Evaluator() { epa_dev_destroy(ctx_); }
 
 Encoded_Chunk encode_chunk(const MSA& chunk, const Tree& tree, const Options& options) {

@@ -8,7 +8,9 @@
 // p-value from multiscale replicates of the same streams (epa_dev_rell_au, the default scales); --kh adds the p-values of
 // the KH, weighted KH and weighted SH tests from the replicates of --rell (epa_dev_rell_kh).  With --posterior the rows get
 // their marginal likelihood (epa_dev_marginal_like: only edge_num comes from the row; Gauss-Legendre x Gauss-Laguerre
-// rule, exponential pendant prior) and post_prob, its normalisation over the rows of the placement object.
+// rule, exponential pendant prior) and post_prob, its normalisation over the rows of the placement object.  With --edpl the
+// rows get exp_dist, the LWR-weighted mean path distance from the row's attachment point to the rows of its object, and
+// the object's edpl (epa_dev_edpl on the tree's topology, one call over the whole file once the LWRs are known).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -207,6 +209,28 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
       for (Placement& p : pq) p.post_prob(p.post_prob() / total);
     }
   for (PQuery& pq : sample) sort_by_lwr(pq);
+  if (options.edpl) {
+    // EDPL (epa_dev_edpl): ONE call over all rows, as the file will list them -- the object's index is the query, the
+    // recomputed like_weight_ratios are the weights, entry order is the LWR-sorted order of the output
+    dev.set_topology(tree);
+    std::vector<epa_pair> pairs;
+    std::vector<double> distal, weight;
+    pairs.reserve(n_rows); distal.reserve(n_rows); weight.reserve(n_rows);
+    for (size_t i = 0; i < sample.size(); ++i)
+      for (const Placement& p : sample[i]) {
+        pairs.push_back(epa_pair{(uint32_t)p.branch_id(), (uint32_t)i});
+        distal.push_back(p.distal_length());
+        weight.push_back(p.lwr());
+      }
+    std::vector<double> row_dist(pairs.size()), edpl(sample.size());
+    const int rc = epa_dev_edpl(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)sample.size(),
+                                row_dist.data(), edpl.data());
+    if (rc != EPA_OK)
+      throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+    size_t k = 0;
+    for (size_t i = 0; i < sample.size(); ++i)
+      for (Placement& p : sample[i]) { p.exp_dist(row_dist[k++]); p.edpl(edpl[i]); }
+  }
   st.seconds_post = std::chrono::duration<double>(clk::now() - ts).count();
   ts = clk::now();
   std::string dir = outdir;
@@ -217,7 +241,7 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
   write_jplace(os, std::vector<Sample>{sample}, tree.numbered_newick(options.precision), invocation, options.precision, nullptr,
                (options.rell_replicates ? kJplaceRell : 0u) | (options.rell_tests ? kJplaceRellTests : 0u) |
                    (options.au ? kJplaceAu : 0u) | (options.kh ? kJplaceKh : 0u) |
-                   (options.posterior ? kJplacePosterior : 0u));
+                   (options.posterior ? kJplacePosterior : 0u) | (options.edpl ? kJplaceEdpl : 0u));
   os.flush();
   if (!os) { os.close(); std::remove(out_path.c_str()); throw std::runtime_error{"writing " + out_path + " failed"}; }
   st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();

@@ -331,6 +331,27 @@ void Tree::fill_tree_desc(epa_tree_desc& d, Tree_Desc_Storage& st) const {
   d.branch_prox = st.prox.data(); d.branch_dist = st.dist.data();
 }
 
+void Tree::fill_topology(std::vector<uint32_t>& prox, std::vector<uint32_t>& dist) const {
+  // node ids: tip t is node t; an inner node is the ring of its three records, numbered from n on in the order of the
+  // ring's first record
+  const size_t B = nums_.branches, n = nums_.tip_nodes;
+  std::vector<uint32_t> node(recs_.size(), 0xffffffffu);
+  uint32_t next_inner = (uint32_t)n;
+  for (size_t r = 0; r < recs_.size(); ++r) {
+    if (recs_[r].tip >= 0) { node[r] = (uint32_t)recs_[r].tip; continue; }
+    if (node[r] != 0xffffffffu) continue;
+    for (int k = (int)r, i = 0; i < 3; ++i, k = recs_[k].next) node[k] = next_inner;
+    ++next_inner;
+  }
+  prox.resize(B); dist.resize(B);
+  for (size_t b = 0; b < B; ++b) {
+    int dd = branch_rec_.at(b), p = recs_[dd].back;
+    if (recs_[dd].tip < 0 && recs_[p].tip >= 0) std::swap(dd, p);  // the tip is always DISTAL (fill_tree_desc)
+    prox[b] = node[p];
+    dist[b] = node[dd];
+  }
+}
+
 void Tree::side(int rec, const double*& clv, const uint8_t*& tip, const uint32_t*& sc) const {
   const Rec& r = recs_[rec];
   if (r.tip >= 0) { clv = nullptr; tip = tipchars_[r.tip].data(); sc = nullptr; }

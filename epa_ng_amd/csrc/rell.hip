@@ -826,28 +826,15 @@ struct RellPlan {
 
 int rell_plan(epa_ctx* ctx, const char* who, const epa_pair* d_pairs, uint32_t n, const uint32_t* h_span, uint32_t Q,
               RellPlan& plan) {
-  const dim3 ngrid((n + 255) / 256);
   std::vector<RellGroup>& groups = plan.groups;
   std::vector<RellBatch>& batches = plan.batches;
   // ---- group by query: stable sort of the entry indices by seq_id
-  int bits = 1;
-  while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)Q) ++bits;
-  size_t temp_bytes = 0;
-  (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                 (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0, bits, ctx->stream);
-  const size_t nb = (sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255;
-  char* base = (char*)epa_scratch(ctx, SLOT_RELL_SORT, 5 * nb + temp_bytes);
-  uint32_t* d_bounds = (uint32_t*)epa_scratch(ctx, SLOT_RELL_BOUNDS, sizeof(uint32_t) * 2 * (size_t)Q);
-  if (!base || !d_bounds) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(rell grouping)");
-  uint32_t *d_keys = (uint32_t*)base, *d_idx = (uint32_t*)(base + nb), *d_sorted = (uint32_t*)(base + 2 * nb);
-  uint32_t *d_order = (uint32_t*)(base + 3 * nb), *d_wins = (uint32_t*)(base + 4 * nb);
-  void* temp = base + 5 * nb;
-  hipLaunchKernelGGL(k_rell_keys, ngrid, dim3(256), 0, ctx->stream, d_pairs, n, d_keys, d_idx);
-  EPA_HIP(ctx, rocprim::radix_sort_pairs<epa_radix_cfg>(temp, temp_bytes, d_keys, d_sorted, d_idx, d_order, (size_t)n, 0, bits,
-                                                        ctx->stream));
-  EPA_HIP(ctx, hipMemsetAsync(d_bounds, 0, sizeof(uint32_t) * 2 * (size_t)Q, ctx->stream));
+  EntryGroups eg;
+  int grc = launch_group_entries(ctx, d_pairs, n, Q, 1, &eg);
+  if (grc) return grc;
+  const uint32_t* d_bounds = eg.bounds;
+  uint32_t *d_order = eg.order, *d_wins = eg.extra;
   EPA_HIP(ctx, hipMemsetAsync(d_wins, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-  hipLaunchKernelGGL(k_rell_bounds, ngrid, dim3(256), 0, ctx->stream, d_sorted, n, Q, d_bounds);
   std::vector<uint32_t> bounds(2 * (size_t)Q);
   EPA_HIP(ctx, hipMemcpyAsync(bounds.data(), d_bounds, sizeof(uint32_t) * 2 * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
   EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -939,6 +926,30 @@ int rell_run(epa_ctx* ctx, const char* who, int timer, const EntryStage& e, cons
 }
 
 }  // namespace
+
+int launch_group_entries(epa_ctx* ctx, const epa_pair* d_pairs, uint32_t n, uint32_t Q, uint32_t extra_arrays, EntryGroups* g) {
+  const dim3 ngrid((n + 255) / 256);
+  int bits = 1;
+  while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)Q) ++bits;
+  size_t temp_bytes = 0;
+  (void)rocprim::radix_sort_pairs<epa_radix_cfg>(nullptr, temp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                 (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0, bits, ctx->stream);
+  const size_t nb = (sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255;
+  char* base = (char*)epa_scratch(ctx, SLOT_RELL_SORT, (4 + (size_t)extra_arrays) * nb + temp_bytes);
+  uint32_t* d_bounds = (uint32_t*)epa_scratch(ctx, SLOT_RELL_BOUNDS, sizeof(uint32_t) * 2 * (size_t)Q);
+  if (!base || !d_bounds) return epa_fail(ctx, EPA_ERR_HIP, "hipMalloc(entry grouping)");
+  uint32_t *d_keys = (uint32_t*)base, *d_idx = (uint32_t*)(base + nb), *d_sorted = (uint32_t*)(base + 2 * nb);
+  uint32_t* d_order = (uint32_t*)(base + 3 * nb);
+  void* temp = base + (4 + (size_t)extra_arrays) * nb;
+  hipLaunchKernelGGL(k_rell_keys, ngrid, dim3(256), 0, ctx->stream, d_pairs, n, d_keys, d_idx);
+  EPA_HIP(ctx, rocprim::radix_sort_pairs<epa_radix_cfg>(temp, temp_bytes, d_keys, d_sorted, d_idx, d_order, (size_t)n, 0, bits,
+                                                        ctx->stream));
+  EPA_HIP(ctx, hipMemsetAsync(d_bounds, 0, sizeof(uint32_t) * 2 * (size_t)Q, ctx->stream));
+  hipLaunchKernelGGL(k_rell_bounds, ngrid, dim3(256), 0, ctx->stream, d_sorted, n, Q, d_bounds);
+  EPA_HIP(ctx, hipGetLastError());
+  *g = EntryGroups{d_sorted, d_order, d_bounds, extra_arrays ? (uint32_t*)(base + 4 * nb) : nullptr};
+  return EPA_OK;
+}
 
 int launch_rell(epa_ctx* ctx, const EntryStage& e, const RellDraws& dr, double* d_support) {
   return rell_run(

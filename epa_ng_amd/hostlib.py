@@ -41,6 +41,8 @@ def host_lib():
         L.epa_host_ref_tree_logl.restype = C.c_double
         L.epa_host_ref_tree_logl.argtypes = [C.c_void_p, C.c_uint32]
         L.epa_host_ref_numbered_newick.argtypes = [C.c_void_p, C.c_uint, C.c_char_p, C.c_size_t]
+        L.epa_host_ref_topology.restype = C.c_uint32
+        L.epa_host_ref_topology.argtypes = [C.c_void_p, u32p, u32p]
         L.epa_host_ref_model.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, dp]
         L.epa_host_ref_subst.argtypes = [C.c_void_p, dp]
         L.epa_host_ref_model_string.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -155,6 +157,15 @@ class Reference:
         n = host_lib().epa_host_ref_numbered_newick(self.h, precision, buf, len(buf))
         assert n > 0
         return buf.value.decode()
+
+    def topology(self):
+        """-> (node_prox uint32 [B], node_dist uint32 [B], n_nodes): the node ids at both ends of every branch in
+        branch_id order, a tip always at the distal end; tip t is node t, the inner nodes follow (Tree::fill_topology).
+        What Evaluator.set_topology takes; needs no device."""
+        prox, dist = np.zeros(self.B, np.uint32), np.zeros(self.B, np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        n = host_lib().epa_host_ref_topology(self.h, prox.ctypes.data_as(u32p), dist.ctypes.data_as(u32p))
+        return prox, dist, int(n)
 
     def model(self):
         s, c = self.s, self.c

@@ -276,6 +276,8 @@ int epa_dev_build_lookup(epa_ctx* ctx);
  * block_branches: branches per block buffer (0 = the default 1024; at most B rounded up to 64 are allocated);
  * banks: scratch banks that will run a preplacement (the direct entry points are one, every pipeline slot in
  * use another).  refi is counted for the shapes the tuned Newton kernels serve (a proper GTR is assumed).
+ * Not counted, because it is optional: the path-distance table of epa_dev_set_topology, 8 (2 n - 1) (floor(log2(2 n - 1)) + 1)
+ * + 12 B bytes for n = B + 1 nodes (19.7 MB at 65 537 branches).
  */
 typedef struct {
   uint64_t reft;          /* both CLVs of every branch in the eigenbasis                                  */
@@ -727,6 +729,59 @@ int epa_dev_rell_kh(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, 
                     double* p_kh /* [n] or NULL */, double* p_wkh /* [n] or NULL */, double* p_wsh /* [n] or NULL */);
 
 /*
+ * Tree geometry: which branch touches which.  A context knows its branches' lengths but not how they join; this call
+ * attaches the topology that path distances need (epa_dev_edpl below).  node_prox[b] / node_dist[b] (HOST or device
+ * arrays, [B]) are the node ids, 0 .. n_nodes - 1, at the proximal and the distal end of branch b, in the orientation of
+ * epa_dev_score_at: distal[i] of an entry is measured from the node_dist[b] end, the remainder is branch_length[b] -
+ * distal[i].  The lengths are the context's own.
+ * Specified, so that a restatement anywhere reaches the same bits:
+ *   root       node_prox[0]; depth[root] = 0.0
+ *   depth      depth[child] = depth[parent] + branch_length[edge]: ONE fp64 add per level
+ *   child(b)   the end of b that is farther from the root
+ * EPA_ERR_INVALID_ARG, the text names the first offending branch: n_nodes != B + 1 (the text names both counts); a node id
+ * >= n_nodes; a branch with both ends on one node or a length that is negative or not finite; a graph that is not connected (with n_nodes - 1 branches that also
+ * rules out a cycle).  A refused call leaves the context, and a topology set before, as they were.  A second call
+ * replaces the first.  No other entry point reads the topology: their results are the same bits with and without one.
+ * Structure (treepath.hip): an Euler tour of the rooted tree and a sparse table of range minima over the tour's fp64
+ * DEPTHS.  Lengths are >= 0 and a rounded add never decreases, so the minimum over the tour between two nodes is the
+ * depth of their lowest common ancestor itself, zero-length branches included: a query is two 8-byte loads, O(1).
+ * Built once per call on the host without recursion (a ladder tree is an ordinary input), kept in device memory:
+ * 8 (2 n_nodes - 1) (floor(log2(2 n_nodes - 1)) + 1) + 12 B bytes, 19.7 MB at 65 537 branches.  The table is optional and
+ * therefore NOT part of epa_dev_footprint's numbers.  (An all-pairs node distance matrix would be 34 GB there.)
+ */
+int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32_t* node_prox /* [B] */,
+                         const uint32_t* node_dist /* [B] */);
+
+/*
+ * Expected distance between placement locations (EDPL, Matsen et al.; `guppy edpl`, `gappa examine edpl`): where a query's
+ * weight is spread over several rows, are they neighbours or on opposite sides of the tree?  Entry i is the point at
+ * distal[i] on branch pairs[i].branch_id with weight[i] (the caller passes like_weight_ratios; they are used as given);
+ * the entries of one query (seq_id) belong together as for epa_dev_rell_support: any order is accepted, they are
+ * grouped through the same stable grouping, and "entry order" below is the order of appearance within the query.
+ * Every line is ONE fp64 operation, nothing fused or reassociated; a restatement reaches the same bits.  Per query, with
+ * e_i the branch of entry i and depth / child of epa_dev_set_topology:
+ *   x_i        distal_i if child(e_i) == node_dist[e_i], else branch_length[e_i] - distal_i
+ *   D_i        depth[child(e_i)] - x_i
+ *   m_ij       min(depth[lca(child(e_i), child(e_j))], D_i, D_j)
+ *   d_ij       (D_i - m_ij) + (D_j - m_ij)
+ *   row_dist_i 0.0 plus weight_j * d_ij for j in entry order, the product rounded and then added
+ *   edpl_q     0.0 plus weight_i * row_dist_i for i in entry order, likewise
+ * The one rule for m_ij covers two points on one edge (|D_i - D_j|), an edge on the other's path to the root (D_j - D_i)
+ * and unrelated edges.  edpl_q is the full double sum over i and j of w_i w_j d_ij, Matsen's definition; pendant lengths
+ * do not enter, as in guppy and gappa.  A query with no entry gets 0.0, and so does a query with one.
+ * pairs, distal, weight, row_dist ([n], or NULL to leave it out) and edpl ([Q]) may be host or device pointers.  Host
+ * arrays are validated, EPA_ERR_INVALID_ARG names the first offending entry: branch_id >= B, seq_id >= Q, a distal length
+ * that is negative, not finite or beyond the branch's length, a weight that is negative or not finite (device pairs: an
+ * id out of range is found by the kernels, nothing is read through it, and the call is refused).  No topology set:
+ * EPA_ERR_INVALID_ARG, the text says so.  n == 0 returns EPA_OK and writes Q zeros.  n < 2^32; no bound on the entries per
+ * query.  No query codes: the call reads no CLV.
+ * The same call returns the same bits every time: sequential sums, no floating-point atomics.  Timer: "edpl" (grouping,
+ * points, pair sums and the per-query sum together).
+ */
+int epa_dev_edpl(epa_ctx* ctx, const epa_pair* pairs, const double* distal, const double* weight, uint64_t n, uint32_t Q,
+                 double* row_dist /* [n] or NULL */, double* edpl /* [Q] */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -1004,7 +1059,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
