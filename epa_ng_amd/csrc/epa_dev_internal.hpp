@@ -21,7 +21,7 @@ using epa_radix_cfg = rocprim::radix_sort_config<rocprim::default_config, rocpri
                                                  rocprim::default_config, 0>;
 
 #define EPA_MAX_STATES 20
-#define EPA_MAX_CATS 16
+// EPA_MAX_CATS (16): include/epa_dev.h, where the host's model parser reads it too
 #define EPA_MAX_COLS 24
 // HIP's limit of grid.y / grid.z: a launch with the branch (or a record of a tree level) in grid.y goes out in slices
 // of this many, the kernel adds the slice's first branch

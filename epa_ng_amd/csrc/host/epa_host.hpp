@@ -386,6 +386,7 @@ private:
   bool bfast_ = false;
   std::vector<uint64_t> bfast_offsets_;
   size_t bfast_next_ = 0;
+  uint64_t bfast_size_ = 0;               // bytes of the bfast file: the bound of every count and length read from it
   std::FILE* f_ = nullptr;
   const char* map_ = nullptr;             // regular fasta files are mapped (no copy through a read buffer)
   size_t map_len_ = 0;

@@ -50,6 +50,13 @@ bool Fasta_Stream::open_bfast() {
     return false;
   }
   const uint64_t n = get_u64(f_);
+  {  // counts and lengths read from the file size nothing before they are held against the file's own size
+    struct stat sb;
+    bfast_size_ = (::fstat(::fileno(f_), &sb) == 0 && sb.st_size > 0) ? (uint64_t)sb.st_size : 0;
+    if (n > bfast_size_ / 16)
+      throw std::runtime_error{"bfast: the header announces " + std::to_string(n) + " sequences, more than a file of " +
+                               std::to_string(bfast_size_) + " bytes can hold"};
+  }
   // with or without the mask string?  The first table entry names the data section's offset.
   const long table_plain = 7 + 8;
   std::vector<uint64_t> offs(n);
@@ -129,7 +136,9 @@ size_t Fasta_Stream::read_next_wire(MSA& out, Encoded_Chunk& enc, size_t sites, 
     mx = std::max(mx, (uint32_t)(hi - lo));
   }
   for (size_t i = 0; i < m; ++i) {   // the first offender in file order, with the reference's messages
-    if (stat[i] == 1) throw std::runtime_error{"bfast: truncated sequence"};
+    if (stat[i] == 1)
+      throw std::runtime_error{"bfast: truncated sequence (record " + std::to_string(bfast_next_ + i) + " at offset " +
+                               std::to_string(bfast_offsets_[bfast_next_ + i]) + ")"};
     if (stat[i] == 2) throw std::runtime_error{"Query sequence length not same as reference alignment!"};   // Tiny_Tree.cpp:145-147
     if (stat[i] == 3)   // Tiny_Tree.cpp:153-156
       throw std::runtime_error{"Sequence with header '" + out[first + i].header() + "' does not appear to have any non-gap sites!"};
@@ -162,15 +171,20 @@ size_t Fasta_Stream::read_next_bfast(MSA& out, size_t max_seqs) {
   size_t got = 0;
   std::vector<unsigned char> packed;
   while (got < max_seqs && bfast_next_ < bfast_offsets_.size()) {
-    if (std::fseek(f_, (long)bfast_offsets_[bfast_next_], SEEK_SET) != 0)
-      throw std::runtime_error{"bfast: bad sequence offset"};
+    const uint64_t off = bfast_offsets_[bfast_next_];
+    const std::string rec = " (record " + std::to_string(bfast_next_) + " at offset " + std::to_string(off) + ")";
+    // the same bounds as read_next_wire, before anything is sized by a number from the file
+    if (off > bfast_size_ || bfast_size_ - off < 16 || std::fseek(f_, (long)off, SEEK_SET) != 0)
+      throw std::runtime_error{"bfast: bad sequence offset" + rec};
     const uint64_t hlen = get_u64(f_);
+    if (hlen > (1u << 20) || bfast_size_ - off - 16 < hlen) throw std::runtime_error{"bfast: truncated header" + rec};
     std::string header(hlen, '\0');
-    if (hlen && std::fread(&header[0], 1, hlen, f_) != hlen) throw std::runtime_error{"bfast: truncated header"};
+    if (hlen && std::fread(&header[0], 1, hlen, f_) != hlen) throw std::runtime_error{"bfast: truncated header" + rec};
     const uint64_t sites = get_u64(f_);
+    if (sites / 2 > bfast_size_ - off - 16 - hlen) throw std::runtime_error{"bfast: truncated sequence" + rec};
     packed.resize((sites + 1) / 2);
     if (!packed.empty() && std::fread(packed.data(), 1, packed.size(), f_) != packed.size())
-      throw std::runtime_error{"bfast: truncated sequence"};
+      throw std::runtime_error{"bfast: truncated sequence" + rec};
     std::string seq(sites, '-');
     for (uint64_t i = 0; i < sites; ++i) {
       const unsigned char b = packed[i / 2];
@@ -332,10 +346,12 @@ size_t Fasta_Stream::read_next_views(MSA& out, std::vector<const char*>& rows, s
     const char* sb = nl + 1;
     const char* se = e;
     while (se > sb && (se[-1] == '\n' || se[-1] == '\r')) --se;
-    // exactly `sites` bytes between the header line and the next record: a row with a line break or a blank INSIDE
-    // those bytes is short of real characters -- the encoder, which looks at every one of them, refuses it
-    // ("char is invalid!"), so the bytes are not walked twice
-    const bool good = (size_t)(se - sb) == sites;
+    // exactly `sites` bytes between the header line and the next record, and no line break among them: a record start
+    // taken from the predicted offset can span a short record and the next record's header, which must come out as
+    // two records through read_next() (and then fail with the reference's "Query sequence length not same as reference
+    // alignment!", Tiny_Tree.cpp:145-147), not as one merged row.  A blank inside the row is still left to the
+    // encoder, which looks at every character ("char is invalid!")
+    const bool good = (size_t)(se - sb) == sites && !std::memchr(sb, '\n', sites);
     if (!good) { ok = 0; continue; }
     const char* h = nl;
     while (h > b && (h[-1] == '\r' || h[-1] == ' ' || h[-1] == '\t')) --h;
@@ -616,9 +632,10 @@ std::vector<Jplace_PQuery> read_jplace(const std::string& path) {
   for (size_t i = 0; i < fields->items.size(); ++i) {
     if (fields->items[i].kind != Json::kString) fail("\"fields\" holds something that is not a string");
     const std::string& n = fields->items[i].str;
-    if (n == "edge_num") col_edge = (int)i;
-    else if (n == "distal_length") col_distal = (int)i;
-    else if (n == "pendant_length") col_pendant = (int)i;
+    int* col = n == "edge_num" ? &col_edge : n == "distal_length" ? &col_distal : n == "pendant_length" ? &col_pendant : nullptr;
+    if (!col) continue;
+    if (*col >= 0) fail("field \"" + n + "\" is named twice in \"fields\" (entries " + std::to_string(*col) + " and " + std::to_string(i) + ")");
+    *col = (int)i;
   }
   if (col_edge < 0) fail("required field \"edge_num\" is missing from \"fields\"");
   if (col_distal < 0) fail("required field \"distal_length\" is missing from \"fields\"");
@@ -683,7 +700,16 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
     size_t est = 0;
     for (long i = i0; i < i1; ++i) est += 48 + sample[i].header().size() + sample[i].size() * (24 + (size_t)n_vals * (size_t)(precision + 12));
     o.reserve(est);
-    char line[1024];
+    // The stack line is used only for rows that provably fit it.  With precision <= 18 and every |value| < 9e18 (or
+    // NaN) a number is at most 1 sign + 19 digits + '.' + 18 digits = 39 characters, so a row of the 15 values the six
+    // extras add up to is at most 7 ("      [") + 20 (edge: a 64-bit integer) + 15 x (2 + 39) + 3 ("],\n") = 645 of the
+    // 1024 bytes, and format_fixed always sees a capacity of at least 1024 - 645 + 39 = 418.  Every other row (a larger
+    // precision, a huge or infinite value) is appended number by number from a buffer sized for the longest double:
+    // 1 sign + 309 digits + '.' + precision.
+    constexpr size_t kLineBytes = 1024;
+    static_assert(7 + 20 + 15 * (2 + 39) + 3 <= kLineBytes, "a fast-path row must fit the stack line");
+    char line[kLineBytes];
+    std::vector<char> wide;
     for (long i = i0; i < i1; ++i) {
       const auto& pq = sample[i];
       o += "    {\"p\": [\n";
@@ -696,9 +722,6 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
           edge = m.first;
           distal = m.second;
         }
-        char* w = line;
-        std::memcpy(w, "      [", 7); w += 7;
-        w = std::to_chars(w, line + 64, edge).ptr;
         double vals[15] = {p.likelihood(), p.lwr(), distal, p.pendant_length()};
         int nv = 4;
         if (rell) vals[nv++] = p.rell_support();
@@ -707,9 +730,24 @@ std::string jplace_chunk_text(const Sample& sample, unsigned int precision, cons
         if (kh) { vals[nv++] = p.p_kh(); vals[nv++] = p.p_wkh(); vals[nv++] = p.p_wsh(); }
         if (posterior) { vals[nv++] = p.marginal_like(); vals[nv++] = p.post_prob(); }
         if (edpl) { vals[nv++] = p.exp_dist(); vals[nv++] = p.edpl(); }
-        for (int k = 0; k < n_vals; ++k) {
-          *w++ = ','; *w++ = ' ';
-          w += format_fixed(w, (size_t)(line + sizeof(line) - w) - 8, vals[k], precision);
+        bool fits = precision <= 18;
+        for (int k = 0; k < n_vals; ++k) fits = fits && !(std::fabs(vals[k]) >= 9.0e18);
+        char* w = line;
+        std::memcpy(w, "      [", 7); w += 7;
+        w = std::to_chars(w, line + 64, edge).ptr;
+        if (fits) {
+          for (int k = 0; k < n_vals; ++k) {
+            *w++ = ','; *w++ = ' ';
+            w += format_fixed(w, (size_t)(line + sizeof(line) - w), vals[k], precision);
+          }
+        } else {
+          if (wide.empty()) wide.resize((size_t)precision + 320);
+          for (int k = 0; k < n_vals; ++k) {
+            *w++ = ','; *w++ = ' ';
+            o.append(line, (size_t)(w - line));
+            w = line;
+            o.append(wide.data(), format_fixed(wide.data(), wide.size(), vals[k], precision));
+          }
         }
         *w++ = ']';
         if (++j < pq.size()) *w++ = ',';

@@ -84,17 +84,41 @@ void jacobi(int n, std::vector<double>& a, std::vector<double>& w, std::vector<d
   for (int i = 0; i < n; ++i) w[i] = a[(size_t)i * n + i];
 }
 
-std::vector<double> parse_list(const std::string& s) {
+// one number of a descriptor; `what` names the parameter in the message (std::stod's own says "stod")
+double parse_number(const std::string& tok, const std::string& what) {
+  size_t used = 0;
+  double v = 0.0;
+  try { v = std::stod(tok, &used); } catch (const std::exception&) { used = 0; }
+  if (used == 0 || used != tok.size()) throw std::runtime_error{"Model: " + what + ": '" + tok + "' is not a number"};
+  return v;
+}
+
+std::vector<double> parse_list(const std::string& s, const std::string& what) {
   std::vector<double> out;
   std::string tok;
   std::stringstream ss(s);
-  while (std::getline(ss, tok, '/')) out.push_back(std::stod(tok));
+  while (std::getline(ss, tok, '/')) out.push_back(parse_number(tok, what));
   return out;
+}
+
+// the category count behind +G / +R: 1 .. EPA_MAX_CATS, what the device's kernels are built for
+int parse_cats(const std::string& digits, const std::string& opt) {
+  unsigned long n = 0;
+  try { n = std::stoul(digits); } catch (const std::exception&) { n = ~0ul; }
+  if (n < 1 || n > (unsigned long)EPA_MAX_CATS)
+    throw std::runtime_error{"Model: +" + opt + digits + ": the number of rate categories must be 1 .. " +
+                             std::to_string(EPA_MAX_CATS)};
+  return (int)n;
 }
 
 }  // namespace
 
 std::vector<double> compute_gamma_cats(double alpha, int k, bool median) {
+  // the bisection below never ends on alpha <= 0 (P(alpha, x) is not a distribution function then) and means nothing
+  // on nan / inf
+  if (!std::isfinite(alpha) || !(alpha > 0.0))
+    throw std::invalid_argument{"compute_gamma_cats: alpha must be a finite positive number (" + std::to_string(alpha) + " given)"};
+  if (k < 1) throw std::invalid_argument{"compute_gamma_cats: the number of categories must be at least 1 (" + std::to_string(k) + " given)"};
   // Yang 1994.  Quantiles of Gamma(alpha, rate alpha) by bisection on the regularised P.
   auto quantile = [&](double p) {
     double lo = 0.0, hi = 1.0;
@@ -175,7 +199,8 @@ Model::Model(const std::string& descriptor_in) {
   if (dna) states_ = 4;
   else if (aa || name == "PROTGTR") states_ = 20;
   else
-    throw std::runtime_error{"Invalid model name: " + name};
+    throw std::runtime_error{name.empty() ? std::string("Invalid model name: the descriptor is empty or begins with an option")
+                                          : "Invalid model name: " + name};
   name_ = name;
   const int nr = states_ * (states_ - 1) / 2;
   // defaults of raxml::Model (Model.cpp:190-193,470,487-488): parameters a model does not fix
@@ -201,7 +226,7 @@ Model::Model(const std::string& descriptor_in) {
     out.clear();
     if (i < rest.size() && rest[i] == '{') {
       size_t e = rest.find('}', i);
-      if (e == std::string::npos) throw std::runtime_error{"Model: unbalanced '{'"};
+      if (e == std::string::npos) throw std::runtime_error{"Model: unbalanced '{' in '" + rest.substr(i) + "'"};
       out = rest.substr(i + 1, e - i - 1);
       i = e + 1;
       return true;
@@ -211,7 +236,7 @@ Model::Model(const std::string& descriptor_in) {
   std::string arg;
   if (braces(arg)) {
     // user rates: one value per class of the model's rate symmetry (Model.cpp:218-241)
-    const std::vector<double> user = parse_list(arg);
+    const std::vector<double> user = parse_list(arg, "substitution rates");
     if (dna) {
       int nuniq = 0;
       for (const char* c = dna->sym; *c; ++c) nuniq = std::max(nuniq, *c - '0' + 1);
@@ -235,7 +260,7 @@ Model::Model(const std::string& descriptor_in) {
     std::transform(opt.begin(), opt.end(), opt.begin(), ::toupper);
     if (opt == "FU" || (opt == "F" && i < rest.size() && rest[i] == '{')) {
       if (!braces(arg)) throw std::runtime_error{"Model: +FU needs explicit frequencies, e.g. +FU{0.25/0.25/0.25/0.25}"};
-      freqs_ = parse_list(arg);
+      freqs_ = parse_list(arg, "+FU frequencies");
       if ((int)freqs_.size() != states_)
         throw std::runtime_error{"Invalid number of user frequencies specified: " + std::to_string(freqs_.size())};
       double sum = 0;
@@ -256,12 +281,16 @@ Model::Model(const std::string& descriptor_in) {
       cats = 4;
       size_t nb = i;
       while (i < rest.size() && std::isdigit((unsigned char)rest[i])) ++i;
-      if (i > nb) cats = std::stoi(rest.substr(nb, i - nb));
+      if (i > nb) cats = parse_cats(rest.substr(nb, i - nb), opt);
       // rate mode suffix of RAxML-NG descriptors (Model.cpp:390-396): m = category means
       // (default), a = medians
       if (i < rest.size() && (rest[i] == 'm' || rest[i] == 'M')) ++i;
       else if (i < rest.size() && (rest[i] == 'a' || rest[i] == 'A')) { ++i; gamma_median = true; }
-      if (braces(arg)) alpha_ = std::stod(arg);
+      if (braces(arg)) {
+        alpha_ = parse_number(arg, "+G alpha");
+        if (!std::isfinite(alpha_) || !(alpha_ > 0.0))
+          throw std::runtime_error{"Model: +G alpha must be a finite positive number ('" + arg + "' given)"};
+      }
     } else if (opt == "R") {
       // free rates: +R<n>{r1/../rn}{w1/../wn} (Model.cpp:405-455): weights normalised to sum 1
       // (equal if omitted), then rates divided by sum_k w_k r_k
@@ -269,14 +298,14 @@ Model::Model(const std::string& descriptor_in) {
       cats = 4;
       size_t nb = i;
       while (i < rest.size() && std::isdigit((unsigned char)rest[i])) ++i;
-      if (i > nb) cats = std::stoi(rest.substr(nb, i - nb));
+      if (i > nb) cats = parse_cats(rest.substr(nb, i - nb), opt);
       if (!braces(arg)) throw std::runtime_error{"Model: +R needs explicit rates, e.g. +R4{0.1/0.5/1/3}{0.25/0.25/0.25/0.25}"};
-      rates_ = parse_list(arg);
+      rates_ = parse_list(arg, "+R rates");
       if ((int)rates_.size() != cats)
         throw std::runtime_error{"Invalid number of free rates specified: " + std::to_string(rates_.size()) +
                                  " (expected: " + std::to_string(cats) + ")"};
       if (braces(arg)) {
-        weights_ = parse_list(arg);
+        weights_ = parse_list(arg, "+R weights");
         if ((int)weights_.size() != cats)
           throw std::runtime_error{"Invalid number of rate weights specified: " + std::to_string(weights_.size()) +
                                    " (expected: " + std::to_string(cats) + ")"};
@@ -293,8 +322,8 @@ Model::Model(const std::string& descriptor_in) {
       // +I{p} / +IU{p}: user-defined proportion of invariant sites (Model.cpp:355-375); +IO / +IC
       // (ML / empirical estimate) need the optimiser EPA-ng never runs: a value must be given
       if (!braces(arg)) throw std::runtime_error{"Model: +" + opt + " needs an explicit value, e.g. +I{0.1}"};
-      pinv_ = std::stod(arg);
-      if (!(pinv_ >= 0.0 && pinv_ < 1.0)) throw std::runtime_error{"Model: p-inv must be in [0, 1)"};
+      pinv_ = parse_number(arg, "+" + opt + " p-inv");
+      if (!(pinv_ >= 0.0 && pinv_ < 1.0)) throw std::runtime_error{"Model: +" + opt + " p-inv must be in [0, 1) ('" + arg + "' given)"};
     } else {
       throw std::runtime_error{"Model: option +" + opt + " is not supported by this build"};
     }

@@ -31,9 +31,28 @@ void label_and_length(const char*& p, std::string* label, double& len) {
     ++p;
     char* e = nullptr;
     len = std::strtod(p, &e);
+    // no check of the reference's to cite (its newick grammar lives in libpll): a length that is not a finite
+    // non-negative number ("1e400", "nan", "-0.2") would turn every likelihood of the tree into nan
+    if (!std::isfinite(len) || len < 0.0)
+      throw std::invalid_argument{"Treeparsing failed! branch length '" + std::string(p, (const char*)e) + "'" +
+                                  (label && !label->empty() ? " of '" + *label + "'" : std::string()) +
+                                  " is not a finite non-negative number"};
     p = e;
   }
   skip_ws(p);
+}
+
+// Quoted labels and bracket comments are legal newick that this parser does not read: refused by name, where the
+// tip-label lookup would otherwise report "failed to find 'a'".  Neither character can occur in an unquoted label.
+void refuse_unsupported_newick(const std::string& newick) {
+  for (size_t i = 0; i < newick.size(); ++i) {
+    const char c = newick[i];
+    if (c == '\'' || c == '"')
+      throw std::invalid_argument{"Treeparsing failed! quoted labels are not supported (quote at byte " + std::to_string(i) + ")"};
+    if (c == '[' || c == ']')
+      throw std::invalid_argument{"Treeparsing failed! bracket comments are not supported ('" + std::string(1, c) + "' at byte " +
+                                  std::to_string(i) + ")"};
+  }
 }
 }  // namespace
 
@@ -42,39 +61,53 @@ int Tree::new_rec() {
   return (int)recs_.size() - 1;
 }
 
-// returns the record facing the parent
+// returns the record facing the parent.  The open '(' are kept on an explicit stack: a ladder of tens of thousands of
+// levels (a legal reference tree) would overflow the call stack of a recursive descent.  Records are created in the
+// order of the recursion: first subtree, second subtree, then the inner node's ring
 int Tree::parse_subtree(const char*& p, double& len) {
-  skip_ws(p);
-  if (*p == '(') {
-    ++p;
-    double l1, l2;
-    const int k1 = parse_subtree(p, l1);
+  struct Open { int k1 = -1; double l1 = 0.0; };   // an inner node whose first child is (not yet) complete
+  std::vector<Open> open;
+  for (;;) {
     skip_ws(p);
-    if (*p != ',') throw std::invalid_argument{"Input Tree contains a unary node or is malformed!"};
-    ++p;
-    const int k2 = parse_subtree(p, l2);
-    skip_ws(p);
-    if (*p == ',') throw std::invalid_argument{"Input Tree contains multifurcations (polytomies)!"};
-    if (*p != ')') throw std::runtime_error{"Treeparsing failed! expected ')'"};
-    ++p;
-    const int a = new_rec(), b = new_rec(), c = new_rec();
-    recs_[a].next = b; recs_[b].next = c; recs_[c].next = a;
-    recs_[b].back = k1; recs_[k1].back = b; recs_[b].length = recs_[k1].length = l1;
-    recs_[c].back = k2; recs_[k2].back = c; recs_[c].length = recs_[k2].length = l2;
-    label_and_length(p, &recs_[a].label, len);  // inner label (printed by numbered_newick)
-    return a;
+    if (*p == '(') { ++p; open.emplace_back(); continue; }
+    int done = new_rec();
+    double dlen = 0.0;
+    {
+      recs_[done].tip = (int)labels_.size();
+      std::string lab;
+      label_and_length(p, &lab, dlen);
+      if (lab.empty()) throw std::runtime_error{"Treeparsing failed! empty tip label"};
+      labels_.push_back(lab);
+    }
+    for (;;) {   // `done` is a complete subtree: hand it to the innermost open node
+      if (open.empty()) { len = dlen; return done; }
+      skip_ws(p);
+      Open& f = open.back();
+      if (f.k1 < 0) {
+        if (*p != ',') throw std::invalid_argument{"Input Tree contains a unary node or is malformed!"};
+        ++p;
+        f.k1 = done; f.l1 = dlen;
+        break;   // on to the second child
+      }
+      if (*p == ',') throw std::invalid_argument{"Input Tree contains multifurcations (polytomies)!"};
+      if (*p != ')') throw std::runtime_error{"Treeparsing failed! expected ')'"};
+      ++p;
+      const int k1 = f.k1, k2 = done;
+      const double l1 = f.l1, l2 = dlen;
+      open.pop_back();
+      const int a = new_rec(), b = new_rec(), c = new_rec();
+      recs_[a].next = b; recs_[b].next = c; recs_[c].next = a;
+      recs_[b].back = k1; recs_[k1].back = b; recs_[b].length = recs_[k1].length = l1;
+      recs_[c].back = k2; recs_[k2].back = c; recs_[c].length = recs_[k2].length = l2;
+      label_and_length(p, &recs_[a].label, dlen);  // inner label (printed by numbered_newick)
+      done = a;
+    }
   }
-  const int a = new_rec();
-  recs_[a].tip = (int)labels_.size();
-  std::string lab;
-  label_and_length(p, &lab, len);
-  if (lab.empty()) throw std::runtime_error{"Treeparsing failed! empty tip label"};
-  labels_.push_back(lab);
-  return a;
 }
 
 Tree::Tree(const std::string& newick, const MSA& ref_msa, const Model& model, const Options& options)
     : model_(model) {
+  refuse_unsupported_newick(newick);
   const char* p = newick.c_str();
   skip_ws(p);
   if (*p != '(') throw std::runtime_error{"Treeparsing failed! expected '('"};
@@ -161,6 +194,13 @@ Tree::Tree(const std::string& newick, const MSA& ref_msa, const Model& model, co
   vroot_ = a;
   }
   if (labels_.size() < 3) throw std::runtime_error{"Number of tip nodes too small"};
+  {  // two tips of one name would share an alignment row and leave another row's taxon out of the tree.  (The reference
+     // keys its label table by name, src/core/pll/epa_pll_util.cpp:19-21, and does not notice: the second tip keeps
+     // whatever its CLV held.)
+    std::unordered_map<std::string, int> seen;
+    for (const auto& l : labels_)
+      if (++seen[l] == 2) throw std::invalid_argument{"Treeparsing failed! tip label '" + l + "' appears more than once"};
+  }
   // set_missing_branch_lengths (src/core/pll/pll_util.cpp:13-39): a zero length counts as missing
   for (auto& r : recs_)
     if (r.length == 0.0) r.length = kDefaultBranchLength;
@@ -216,10 +256,12 @@ Tree::Tree(const std::string& newick, const MSA& ref_msa, const Model& model, co
     for (uint32_t m = 0; m < 16; ++m) { tipmap_[m] = m; code_of[m] = (uint8_t)m; }
   }
   tipchars_.resize(n);
+  std::vector<char> row_used(ref_msa.size(), 0);
   for (unsigned t = 0; t < n; ++t) {
     auto it = by_label.find(labels_[t]);
     if (it == by_label.end())
       throw std::invalid_argument{"Bad tree/ref msa combination: failed to find " + labels_[t]};
+    row_used[it->second] = 1;
     const std::string& sq = ref_msa[it->second].sequence();
     if (sq.size() != sites_) throw std::runtime_error{"reference MSA rows differ in length"};
     tipchars_[t].resize(sites_);
@@ -235,6 +277,13 @@ Tree::Tree(const std::string& newick, const MSA& ref_msa, const Model& model, co
       tipchars_[t][w] = c->second;
     }
   }
+  // A reference alignment row that no tip names is refused.  The reference tolerates it ("the MSA may also contain query
+  // sequences", src/core/pll/epa_pll_util.cpp:27-32); here the reference file holds the tree's taxa only, its rows feed
+  // the premasking column mask and +F frequencies, and a left-over row is most often a misspelt or missing tip
+  for (size_t i = 0; i < ref_msa.size(); ++i)
+    if (!row_used[i])
+      throw std::invalid_argument{"Bad tree/ref msa combination: reference MSA sequence '" + ref_msa[i].header() +
+                                  "' (row " + std::to_string(i) + ") is not a tip of the tree"};
   if (model_.empirical_base_freqs()) {
     // +F / +FC: compute_and_set_empirical_frequencies (src/core/pll/epa_pll_util.cpp:55-57 ->
     // pllmod_msa_empirical_frequencies, pll-modules, restated): every tip character adds

@@ -97,9 +97,10 @@ typedef enum {
  * src/core/pll/pll_util.cpp:182-205).  Orientation is the caller's job exactly as in
  * Tiny_Tree.cpp:64-74: when one end of the branch is a tip it is passed as the DISTAL side.
  */
+#define EPA_MAX_CATS 16 /* most rate categories a reference may have (the kernels' table sizes) */
 typedef struct {
   uint32_t states;     /* 4 (DNA) or 20 (AA)                                                   */
-  uint32_t rate_cats;  /* number of rate categories c                                          */
+  uint32_t rate_cats;  /* number of rate categories c, 1 .. EPA_MAX_CATS                       */
   uint32_t sites;      /* alignment width W after column pre-masking                           */
   uint32_t branches;   /* B = 2n-3                                                             */
 

@@ -120,3 +120,32 @@ def test_fields_come_last_and_nothing_else_changes(setup):
     assert text.count(', "exp_dist", "edpl"]') == 1
     strip = lambda t: re.sub(r"(\n      \[[^\]\n]*), [-0-9.]+, [-0-9.]+\]", r"\1]", t)   # noqa: E731
     assert strip(text).replace(', "exp_dist", "edpl"]', "]") == body(without)
+
+
+def test_all_fifteen_values_at_precision_70(setup):
+    """Every optional field at once at --precision 70: rows of 15 numbers of more than 70 characters each, far beyond the
+    writer's stack line.  The file is JSON, "fields" has 16 names, every number carries exactly 70 digits behind the
+    point, and every value equals the same field of a --precision 15 run with the same flags within 5e-16 (half a unit
+    of the fifteenth decimal) plus one ulp of the value."""
+    import math
+    flags = ["--rell", 100, "--rell-tests", "--au", "--kh", "--posterior", "--edpl"]
+    p70 = setup["run"]("all70", flags + ["--precision", 70])
+    p15 = setup["run"]("all15", flags + ["--precision", 15])
+    res70, res15 = json.load(open(p70)), json.load(open(p15))
+    assert len(res70["fields"]) == 16 and res70["fields"] == res15["fields"] and res70["fields"][-2:] == EDPL
+    assert len(res70["placements"]) == len(res15["placements"]) == 40
+    rows70, rows15 = raw_rows(p70), raw_rows(p15)
+    worst, count = 0.0, 0
+    for pq70, pq15, t70, t15 in zip(res70["placements"], res15["placements"], rows70, rows15):
+        assert pq70["n"] == pq15["n"] and len(pq70["p"]) == len(pq15["p"]) == len(t70) == len(t15)
+        for r70, r15, x70, x15 in zip(pq70["p"], pq15["p"], t70, t15):
+            assert len(r70) == len(r15) == len(x70) == len(x15) == 16
+            assert x70[0] == x15[0] and re.fullmatch(r"\d+", x70[0])
+            for a, b, ta, tb in zip(r70[1:], r15[1:], x70[1:], x15[1:]):
+                assert re.fullmatch(r"-?\d+\.\d{70}", ta), ta
+                assert re.fullmatch(r"-?\d+\.\d{15}", tb), tb
+                worst = max(worst, abs(a - b))
+                count += 1
+                assert abs(a - b) <= 5e-16 + math.ulp(a), (pq70["n"], ta, tb)
+    print("\n--precision 70 against 15: max |difference| %.3g over %d values" % (worst, count))
+    assert count >= 15 * 40
