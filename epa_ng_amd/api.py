@@ -131,6 +131,8 @@ def dev_lib():
         L.epa_dev_set_topology.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.epa_dev_edpl.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                    C.c_void_p]
+        L.epa_dev_krd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -703,6 +705,24 @@ class Evaluator:
         self._check(self.L.epa_dev_edpl(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, int(Q),
                                         _ptr(row_out) if row_dist else None, _ptr(out)))
         return (out, row_out) if row_dist else out
+
+    def krd(self, pairs, distal, weight, S, masses=False, out=None, edge_out=None, clade_out=None):
+        """Kantorovich-Rubinstein distances between S placement samples (epa_dev_krd) -> krd float64 [S][S], or (krd,
+        edge_mass [S][B], clade_mass [S][B]) with masses=True.  Entry i is the mass weight[i] at (pairs[i].branch_id,
+        distal[i]) of sample pairs[i].seq_id; weights are used as given.  Needs set_topology().  Host arrays are converted
+        to float64; device buffers pass as is (out / edge_out / clade_out may be device buffers)."""
+        n, S = len(pairs), int(S)
+        host = (np.ndarray, list, tuple)
+        distal, weight = (np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, host) else a for a in (distal, weight))
+        if out is None:
+            out = np.empty((S, S), np.float64)
+        if masses and edge_out is None:
+            edge_out = np.empty((S, self.B), np.float64)
+        if masses and clade_out is None:
+            clade_out = np.empty((S, self.B), np.float64)
+        self._check(self.L.epa_dev_krd(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, S, _ptr(out),
+                                       _ptr(edge_out) if masses else None, _ptr(clade_out) if masses else None))
+        return (out, edge_out, clade_out) if masses else out
 
     # ---- profile queries (include/epa_dev.h, "Profile queries"): prof is float64 [Q][stride][states] -- numpy on the
     # host or a torch cuda tensor -- holding the per-state likelihoods of every window position; the rows from a

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-DEV_SOURCES = ["epa_dev.hip", "chunk.hip", "preplace.hip", "select.hip", "thorough_dna.hip", "thorough_dna_tipd.hip", "thorough_dna_tipd2h.hip", "thorough_aa.hip", "thorough_aa_mfma.hip", "thorough_generic.hip", "score_at.hip", "marginal.hip", "rell.hip", "profile.hip", "dedup.hip", "treepath.hip", "comm.hip"]
+DEV_SOURCES = ["epa_dev.hip", "chunk.hip", "preplace.hip", "select.hip", "thorough_dna.hip", "thorough_dna_tipd.hip", "thorough_dna_tipd2h.hip", "thorough_aa.hip", "thorough_aa_mfma.hip", "thorough_generic.hip", "score_at.hip", "marginal.hip", "rell.hip", "profile.hip", "dedup.hip", "treepath.hip", "krd.hip", "comm.hip"]
 # Per-file code-generation tuning, measured same-box (round 4, exp/ab.sh / ab_aa.sh, two interleaved rounds):
 # the iterative ILP scheduler removes the dominant nucleotide kernel's scratch (44 -> 0 B per lane) and is worth
 # 5.24 -> 5.17 ms per 262k-pair launch; the 20-state kernel 4.44 -> 4.37 ms per 25.7k pairs.  (iterative-minreg /
@@ -59,7 +59,7 @@ def build_dev(force=False, verbose=False):
     return out
 
 
-HOST_SOURCES = ["model.cpp", "aa_models.cpp", "parse_model.cpp", "tree.cpp", "place.cpp", "place_ranks.cpp", "rescore.cpp", "place_profile.cpp", "fastq.cpp", "place_dedup.cpp", "io.cpp", "capi.cpp"]
+HOST_SOURCES = ["model.cpp", "aa_models.cpp", "parse_model.cpp", "tree.cpp", "place.cpp", "place_ranks.cpp", "rescore.cpp", "krd_samples.cpp", "place_profile.cpp", "fastq.cpp", "place_dedup.cpp", "io.cpp", "capi.cpp"]
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fopenmp", "-Wall", "-Wextra", "-Wno-unused-parameter",
               "-I", os.path.join(ROOT, "include")]
 

@@ -2381,6 +2381,10 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "preplace_profile")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_PREPLACE_PROFILE]][epa_ctx::T_PREPLACE_PROFILE];
   else if (!strcmp(which, "dedup")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_DEDUP]][epa_ctx::T_DEDUP];
   else if (!strcmp(which, "edpl")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_EDPL]][epa_ctx::T_EDPL];
+  else if (!strcmp(which, "krd")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD]][epa_ctx::T_KRD];
+  else if (!strcmp(which, "krd_sort")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD_SORT]][epa_ctx::T_KRD_SORT];
+  else if (!strcmp(which, "krd_tables")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD_TABLES]][epa_ctx::T_KRD_TABLES];
+  else if (!strcmp(which, "krd_pairs")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD_PAIRS]][epa_ctx::T_KRD_PAIRS];
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

@@ -447,6 +447,19 @@ struct Jplace_Row { uint32_t edge_num; double distal_length, pendant_length; };
 struct Jplace_PQuery { std::string name; std::vector<Jplace_Row> rows; };
 std::vector<Jplace_PQuery> read_jplace(const std::string& path);
 
+// a writer that rounded distal_length to a few digits may have pushed it over the branch's length by this much: up to
+// here the readers clamp it to the length, beyond it they refuse the row (rescore.cpp, read_jplace_masses)
+constexpr double kDistalSlack = 1e-6;
+
+// jplace (version 3) reader for --krd: the file as a list of point masses.  Per placement object the multiplicity is the
+// number of names in "n" or the sum of the multiplicities in "nm" (finite, >= 0); per row edge_num (< blen.size()),
+// distal_length (finite, >= 0, clamped to the edge's length within kDistalSlack, refused beyond) and like_weight_ratio
+// (REQUIRED here; finite, >= 0).  mass = multiplicity x like_weight_ratio, not normalised.  Any number of names per
+// object is fine -- read_jplace's "exactly one name" rule is --rescore's.  Throws std::runtime_error naming the file, the
+// object and the row.
+struct Jplace_Mass { uint32_t edge_num; double distal_length, mass; };
+std::vector<Jplace_Mass> read_jplace_masses(const std::string& path, const std::vector<double>& blen);
+
 // ---- device-backed evaluator: one epa_ctx, RAII
 class Device_Evaluator {
 public:
@@ -571,6 +584,14 @@ Run_Stats simple_mpi(const Tree& tree, const std::string& query_file, const MSA_
 // device is created; any error leaves no output file.
 Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::string& query_file, const MSA_Info& msa_info,
                   const std::string& outdir, const Options& options, const std::string& invocation, int device = 0);
+
+// --krd A.jplace,B.jplace,..: one sample per file (`names`, parallel to `files`), its masses normalised to 1 (the total
+// added up in file order; a total of 0 is refused by name); the Kantorovich-Rubinstein distance matrix of the samples
+// on the reference tree (epa_dev_krd) -> <outdir>/krd.tsv, and with `masses` the per-edge and per-clade masses ->
+// <outdir>/edge_masses.tsv, clade_masses.tsv (columns: edge_num).  Every file is parsed and validated before the device
+// is created; the outputs are replaced like epa_result.jplace is, and a failed write leaves none behind.
+Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, const std::vector<std::string>& names,
+                    const std::string& outdir, const Options& options, bool masses, int device = 0);
 
 // -q reads.fastq: every chunk of an aligned FASTQ premasked (both lines), encoded, turned into rows of state
 // likelihoods (epa_profile_from_phred) and placed by epa_dev_place_chunk_profile; LWR, filter and jplace as simple_mpi.

@@ -679,6 +679,85 @@ std::vector<Jplace_PQuery> read_jplace(const std::string& path) {
   return out;
 }
 
+std::vector<Jplace_Mass> read_jplace_masses(const std::string& path, const std::vector<double>& blen) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw std::runtime_error{path + ": cannot open the jplace file"};
+  std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  const Json doc = Json_Parser(text, path).parse();
+  auto fail = [&](const std::string& what) -> void { throw std::runtime_error{path + ": " + what}; };
+  if (doc.kind != Json::kObject) fail("not a jplace document (no top-level object)");
+  const Json* fields = doc.member("fields");
+  const Json* pls = doc.member("placements");
+  if (!fields || fields->kind != Json::kArray) fail("no \"fields\" array");
+  if (!pls || pls->kind != Json::kArray) fail("no \"placements\" array");
+  int col_edge = -1, col_distal = -1, col_lwr = -1;
+  for (size_t i = 0; i < fields->items.size(); ++i) {
+    if (fields->items[i].kind != Json::kString) fail("\"fields\" holds something that is not a string");
+    const std::string& n = fields->items[i].str;
+    int* col = n == "edge_num" ? &col_edge : n == "distal_length" ? &col_distal : n == "like_weight_ratio" ? &col_lwr : nullptr;
+    if (!col) continue;
+    if (*col >= 0) fail("field \"" + n + "\" is named twice in \"fields\" (entries " + std::to_string(*col) + " and " + std::to_string(i) + ")");
+    *col = (int)i;
+  }
+  if (col_edge < 0) fail("required field \"edge_num\" is missing from \"fields\"");
+  if (col_distal < 0) fail("required field \"distal_length\" is missing from \"fields\"");
+  if (col_lwr < 0) fail("required field \"like_weight_ratio\" is missing from \"fields\": --krd weighs every row by it");
+  const size_t ncol = fields->items.size(), B = blen.size();
+  std::vector<Jplace_Mass> out;
+  for (size_t i = 0; i < pls->items.size(); ++i) {
+    const Json& o = pls->items[i];
+    const std::string where = "placement object " + std::to_string(i) + ": ";
+    if (o.kind != Json::kObject) fail(where + "not an object");
+    const Json *n = o.member("n"), *nm = o.member("nm"), *p = o.member("p");
+    if ((n != nullptr) == (nm != nullptr)) fail(where + "needs exactly one of \"n\" and \"nm\"");
+    const Json& names = n ? *n : *nm;
+    if (names.kind != Json::kArray || names.items.empty()) fail(where + "carries no name");
+    double mult = 0.0;
+    for (size_t k = 0; k < names.items.size(); ++k) {
+      const Json& e = names.items[k];
+      if (n) {
+        if (e.kind != Json::kString) fail(where + "name " + std::to_string(k) + " is not a string");
+        mult += 1.0;
+      } else {
+        if (e.kind != Json::kArray || e.items.size() != 2 || e.items[0].kind != Json::kString || e.items[1].kind != Json::kNumber)
+          fail(where + "\"nm\" entry " + std::to_string(k) + " is not [name, multiplicity]");
+        const double m = e.items[1].num;
+        if (!(std::isfinite(m) && m >= 0.0))
+          fail(where + "\"nm\" entry " + std::to_string(k) + ": the multiplicity of '" + e.items[0].str + "' is negative or not finite");
+        mult += m;
+      }
+    }
+    if (!std::isfinite(mult)) fail(where + "the multiplicities add up to something that is not finite");
+    if (!p || p->kind != Json::kArray) fail(where + "no \"p\" array");
+    for (size_t r = 0; r < p->items.size(); ++r) {
+      const Json& row = p->items[r];
+      const std::string rw = where + "row " + std::to_string(r) + ": ";
+      if (row.kind != Json::kArray || row.items.size() != ncol) fail(rw + "does not have one value per field");
+      for (int c : {col_edge, col_distal, col_lwr})
+        if (row.items[(size_t)c].kind != Json::kNumber) fail(rw + "\"" + fields->items[(size_t)c].str + "\" is not a number");
+      const double e = row.items[(size_t)col_edge].num;
+      if (!(e >= 0.0 && e <= 4294967295.0) || e != std::floor(e)) fail(rw + "edge_num is not a non-negative integer");
+      if (e >= (double)B)
+        fail(rw + "edge_num " + std::to_string((uint64_t)e) + " is not a branch of the reference tree (" + std::to_string(B) + " branches)");
+      const uint32_t edge = (uint32_t)e;
+      double distal = row.items[(size_t)col_distal].num;
+      const double lwr = row.items[(size_t)col_lwr].num;
+      if (!std::isfinite(distal) || distal < 0.0) fail(rw + "distal_length " + std::to_string(distal) + " is negative or not finite");
+      if (distal > blen[edge]) {
+        if (distal > blen[edge] + kDistalSlack)
+          fail(rw + "distal_length " + std::to_string(distal) + " lies beyond the length of edge " + std::to_string(edge) + " (" +
+               std::to_string(blen[edge]) + ")");
+        distal = blen[edge];
+      }
+      if (!(std::isfinite(lwr) && lwr >= 0.0)) fail(rw + "like_weight_ratio " + std::to_string(lwr) + " is negative or not finite");
+      const double mass = mult * lwr;
+      if (!std::isfinite(mass)) fail(rw + "multiplicity x like_weight_ratio is not finite");
+      out.push_back(Jplace_Mass{edge, distal, mass});
+    }
+  }
+  return out;
+}
+
 // One chunk of the "placements" array as text (sample_to_jplace_string, src/io/jplace_util.cpp:
 // 60-98): formatted per pquery in parallel with snprintf into per-thread strings, then joined.
 // Numbers are fixed-point with `precision` digits like the reference's stream settings.

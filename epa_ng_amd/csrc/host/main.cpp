@@ -65,6 +65,15 @@ static void usage() {
       "                        \"exp_dist\", the like_weight_ratio-weighted mean path distance from the row's attachment point to\n"
       "                        the rows of its object, and \"edpl\", the object's value (the weighted mean of exp_dist), repeated\n"
       "                        on each of its rows.  Weights are the recomputed like_weight_ratios; pendant lengths do not enter\n"
+      "  --krd A.jplace,B.jplace,..  no placement: every file is one sample of placements on this reference tree (its rows weigh\n"
+      "                        multiplicity x like_weight_ratio, normalised to 1 per file); writes krd.tsv, the matrix of\n"
+      "                        Kantorovich-Rubinstein (earth mover's) distances between the samples, as `guppy kr` and\n"
+      "                        `gappa analyze krd` define it for exponent 1: a header line sample<TAB>names, then one line per\n"
+      "                        sample; a sample is named after its file, without directory and .jplace.  Needs -t, -s, -m and\n"
+      "                        -w as --rescore does, takes no -q; one device; --rescore / --dedup / --devices a,b / --rank are\n"
+      "                        refused with it; --preserve-rooting off for rooted trees\n"
+      "  --krd-masses          with --krd: also edge_masses.tsv and clade_masses.tsv, per sample the mass on every edge and in the\n"
+      "                        subtree below it (the edge included), columns by edge_num: the inputs of squash clustering and edge PCA\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -105,6 +114,8 @@ int main(int argc, char** argv) {
   Options opt;
   int device = 0;
   bool dedup = false;   // --dedup: the loop of place_dedup.cpp
+  std::string krd_list;   // --krd: comma-separated jplace files, one sample each (krd_samples.cpp)
+  bool krd_given = false, krd_masses = false;
   bool device_given = false, rell_given = false, prior_given = false, nodes_given = false, rank_given = false;
   std::string diag_flag;   // --host-heuristic / --device-min-chunk: steer the coded chunk loop only
   std::vector<int> devices;
@@ -149,6 +160,8 @@ int main(int argc, char** argv) {
     else if (a == "--kh") opt.kh = true;
     else if (a == "--posterior") opt.posterior = true;
     else if (a == "--edpl") opt.edpl = true;
+    else if (a == "--krd") { krd_list = need(i); krd_given = true; }
+    else if (a == "--krd-masses") krd_masses = true;
     else if (a == "--prior-mean") {
       const std::string v = need(i);
       char* end = nullptr;
@@ -220,7 +233,46 @@ int main(int argc, char** argv) {
     std::cerr << "--edpl works on an existing result: place first, then run again with --rescore out.jplace --edpl\n";
     return 1;
   }
-  if (tree_file.empty() || ref_file.empty() || query_file.empty()) { usage(); return 1; }
+  // --krd compares existing results: what it does not do is refused before any file is parsed or a device is opened
+  std::vector<std::string> krd_files_list, krd_names;
+  if (krd_masses && !krd_given) { std::cerr << "--krd-masses adds the mass tables to the output of --krd and needs it: --krd A.jplace,B.jplace --krd-masses\n"; return 1; }
+  if (krd_given) {
+    const char* const what = "--krd (distances between placement samples) ";
+    if (!query_file.empty()) { std::cerr << what << "reads placements, not sequences: -q is not supported with it\n"; return 1; }
+    if (!rescore_file.empty()) { std::cerr << what << "compares the files as they are: --rescore is not supported with it\n"; return 1; }
+    if (dedup) { std::cerr << what << "places no reads: --dedup is not supported with it\n"; return 1; }
+    if (devices.size() > 1) { std::cerr << what << "runs on one device: --devices with several GPUs is not supported with it\n"; return 1; }
+    if (rank_given || world > 1 || !comm_file.empty()) {
+      std::cerr << what << "runs in one process: --rank / --world / --comm-file are not supported with it\n";
+      return 1;
+    }
+    if (!placing_flags.empty() || rell_given || opt.rell_tests || opt.au || opt.kh || opt.posterior || opt.edpl || prior_given || nodes_given) {
+      std::cerr << what << "places and rescores nothing: " << (placing_flags.empty() ? "the flags of --rescore" : placing_flags[0])
+                << " cannot be combined with it\n";
+      return 1;
+    }
+    std::stringstream ls(krd_list);
+    std::string tok;
+    while (std::getline(ls, tok, ',')) {
+      if (tok.empty()) continue;
+      std::string name = tok.substr(tok.find_last_of('/') == std::string::npos ? 0 : tok.find_last_of('/') + 1);
+      const std::string ext = ".jplace";
+      if (name.size() > ext.size() && name.compare(name.size() - ext.size(), ext.size(), ext) == 0) name.resize(name.size() - ext.size());
+      for (size_t k = 0; k < krd_names.size(); ++k)
+        if (krd_names[k] == name) {
+          std::cerr << "--krd: " << krd_files_list[k] << " and " << tok << " both give the sample name '" << name
+                    << "': a sample is named after its file, rename one of them\n";
+          return 1;
+        }
+      krd_files_list.push_back(tok);
+      krd_names.push_back(name);
+    }
+    if (krd_files_list.empty() || krd_files_list.size() > 4096) {
+      std::cerr << "--krd: one call compares 1 .. 4096 files (" << krd_files_list.size() << " given)\n";
+      return 1;
+    }
+  }
+  if (tree_file.empty() || ref_file.empty() || (query_file.empty() && !krd_given)) { usage(); return 1; }
   // the reference's CLI checks (src/main.cpp:165-218, 368-370)
   if (!(opt.prescoring_threshold >= 0.0 && opt.prescoring_threshold <= 1.0)) {
     std::cerr << "-g / -G: " << opt.prescoring_threshold << " not in [0, 1]\n";
@@ -285,7 +337,7 @@ int main(int argc, char** argv) {
   }
   // an aligned FASTQ query runs the profile chunk loop (place_profile.cpp): synchronous, one device, resident tables.
   // What that loop does not do is refused here, before any file is parsed or a device is opened
-  const bool fastq = is_fastq_file(query_file);
+  const bool fastq = !krd_given && is_fastq_file(query_file);
   if (fastq) {
     const char* const what = "a FASTQ query (quality-aware placement) ";
     if (!rescore_file.empty()) { std::cerr << what << "is placed, not rescored: --rescore is not supported with it\n"; return 1; }
@@ -325,7 +377,8 @@ int main(int argc, char** argv) {
     MSA ref = read_fasta(ref_file);
     // "Peeking into MSA files and generating masks" (src/main.cpp:468-494): columns that are all-gap in
     // the reference or in the whole query file leave both alignments (unless --no-pre-mask)
-    MSA_Info ref_info(ref), qry_info = fastq ? fastq_msa_info(query_file) : MSA_Info::from_file(query_file);
+    // (--krd has no query file: the reference's own gap columns are the mask)
+    MSA_Info ref_info(ref), qry_info = krd_given ? MSA_Info(ref) : fastq ? fastq_msa_info(query_file) : MSA_Info::from_file(query_file);
     if (ref_info.sites() != qry_info.sites()) {
       std::cerr << "The reference and query alignment files do not seem to have the same alignment width! ("
                 << ref_info.sites() << " vs. " << qry_info.sites() << "). Are the query sequences not aligned?\n";
@@ -353,7 +406,9 @@ int main(int argc, char** argv) {
     const double secs_tree = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tree).count();
     if (devices.empty()) devices.push_back(device);
     const bool rank_mode = world > 1 || !comm_file.empty();   // a 1-rank communicator is legal (tests, 1-GPU nodes)
-    const Run_Stats st = fastq
+    const Run_Stats st = krd_given
+        ? krd_files(tree, krd_files_list, krd_names, outdir, opt, krd_masses, devices[0])
+        : fastq
         ? place_profile_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
         : dedup
         ? place_dedup_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
@@ -368,7 +423,8 @@ int main(int argc, char** argv) {
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     std::cout << "Reference tree log-likelihood: " << st.ref_tree_logl << "\n";
-    std::cout << st.queries << " Sequences done! (" << st.pairs << " thorough pairs)\n"
+    std::cout << st.queries << (krd_given ? " Samples done! (" : " Sequences done! (") << st.pairs
+              << (krd_given ? " placements)\n" : " thorough pairs)\n")
               << "Time breakdown [s]: tree + MSA " << secs_tree << ", device setup " << st.seconds_setup
               << ", read queries " << st.seconds_read << ", wait for encoded chunk " << st.seconds_stage_wait
               << ", device " << st.seconds_place + st.seconds_thorough << ", lwr+filter " << st.seconds_post

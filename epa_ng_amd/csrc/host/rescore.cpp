@@ -23,11 +23,6 @@
 
 namespace epa {
 
-namespace {
-// a writer that rounded distal_length to a few digits may have pushed it over the branch's length by this much
-constexpr double kDistalSlack = 1e-6;
-}  // namespace
-
 Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::string& query_file, const MSA_Info& msa_info,
                   const std::string& outdir, const Options& options, const std::string& invocation, int device) {
   using clk = std::chrono::steady_clock;

@@ -13,6 +13,9 @@
 //   sparse [levels][L] doubles, L = 2 n_nodes - 1, levels = floor(log2 L) + 1    (19.7 MB at 65 537 branches)
 //   cdepth [B] doubles   depth[child(b)], child(b) = the end of b farther from the root
 //   cinfo  [B] uint32    first Euler index of child(b), bit 31 set where child(b) == node_dist[b]
+//   rank   [B] uint32    b's position in the order the walk first reaches the child ends: a pre-order
+//   size   [B] uint32    branches in the subtree of child(b), b included: the subtree is the ranks [rank, rank + size)
+// (EpaTopology, epa_dev_internal.hpp: krd.hip reads the last four.)
 //
 // epa_dev_edpl.  The entries are grouped by query with the stable radix sort of their indices that the RELL calls use
 // (launch_group_entries, rell.hip: a group keeps the caller's entry order; the run bounds are read on the device), then
@@ -28,14 +31,6 @@
 #include <string.h>
 
 #pragma clang fp contract(off)   // every step of the specification is ONE fp64 operation: hipcc contracts by default
-
-struct EpaTopology {
-  uint32_t n_nodes = 0, L = 0, levels = 0;
-  void* base = nullptr;        // the one allocation
-  const double* sparse = nullptr;
-  const double* cdepth = nullptr;
-  const uint32_t* cinfo = nullptr;
-};
 
 void epa_topology_free(epa_ctx* ctx) {
   if (!ctx->topo) return;
@@ -168,6 +163,7 @@ extern "C" int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32
   const uint32_t root = prox[0], L = 2 * n_nodes - 1, NONE = 0xffffffffu;
   std::vector<double> depth(n_nodes, 0.0), tour;
   std::vector<uint32_t> first(n_nodes, NONE), up(n_nodes, NONE), cur(off.begin(), off.end() - 1), child(B, NONE), stack;
+  std::vector<uint32_t> brank(B, 0), bsize(B, 0);   // pre-order position of every branch and the size of its subtree
   tour.reserve(L);
   stack.reserve(n_nodes);
   first[root] = 0;
@@ -184,12 +180,14 @@ extern "C" int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32
       depth[w] = depth[v] + ctx->h_blen[b];
       up[w] = b;
       child[b] = w;
+      brank[b] = seen - 1;   // the branches reached before this one
       first[w] = (uint32_t)tour.size();
       tour.push_back(depth[w]);
       stack.push_back(w);
       ++seen;
     } else {
       stack.pop_back();
+      if (up[v] != NONE) bsize[up[v]] = seen - 1 - brank[up[v]];   // everything reached since, the branch itself included
       if (!stack.empty()) tour.push_back(depth[stack.back()]);
     }
   }
@@ -207,18 +205,20 @@ extern "C" int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32
   uint32_t levels = 1;
   while ((2u << (levels - 1)) <= L) ++levels;
   Carver cv;
-  auto layout = [&](Carver& c, double*& sp, double*& cd, uint32_t*& ci) {
+  auto layout = [&](Carver& c, double*& sp, double*& cd, uint32_t*& ci, uint32_t*& rk, uint32_t*& sz) {
     sp = c.take<double>((size_t)levels * L);
     cd = c.take<double>(B);
     ci = c.take<uint32_t>(B);
+    rk = c.take<uint32_t>(B);
+    sz = c.take<uint32_t>(B);
   };
   double *sp = nullptr, *cd = nullptr;
-  uint32_t* ci = nullptr;
-  layout(cv, sp, cd, ci);
+  uint32_t *ci = nullptr, *rk = nullptr, *sz = nullptr;
+  layout(cv, sp, cd, ci, rk, sz);
   const size_t bytes = cv.off;
   std::vector<char> host(bytes, 0);
   cv = Carver{host.data(), 0};
-  layout(cv, sp, cd, ci);
+  layout(cv, sp, cd, ci, rk, sz);
   memcpy(sp, tour.data(), sizeof(double) * L);
   for (uint32_t k = 1; k < levels; ++k) {
     const double* lo = sp + (size_t)(k - 1) * L;
@@ -229,6 +229,8 @@ extern "C" int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32
   for (uint32_t b = 0; b < B; ++b) {
     cd[b] = depth[child[b]];
     ci[b] = first[child[b]] | (child[b] == dist[b] ? EDPL_DIST_BIT : 0u);
+    rk[b] = brank[b];
+    sz[b] = bsize[b];
   }
   void* d_base = nullptr;
   EPA_HIP(ctx, hipMalloc(&d_base, bytes));
@@ -245,10 +247,12 @@ extern "C" int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32
   t->levels = levels;
   t->base = d_base;
   cv = Carver{(char*)d_base, 0};
-  layout(cv, sp, cd, ci);
+  layout(cv, sp, cd, ci, rk, sz);
   t->sparse = sp;
   t->cdepth = cd;
   t->cinfo = ci;
+  t->rank = rk;
+  t->size = sz;
   ctx->topo = t;
   return EPA_OK;
 }

@@ -278,7 +278,7 @@ int epa_dev_build_lookup(epa_ctx* ctx);
  * banks: scratch banks that will run a preplacement (the direct entry points are one, every pipeline slot in
  * use another).  refi is counted for the shapes the tuned Newton kernels serve (a proper GTR is assumed).
  * Not counted, because it is optional: the path-distance table of epa_dev_set_topology, 8 (2 n - 1) (floor(log2(2 n - 1)) + 1)
- * + 12 B bytes for n = B + 1 nodes (19.7 MB at 65 537 branches).
+ * + 20 B bytes for n = B + 1 nodes (20.2 MB at 65 537 branches).
  */
 typedef struct {
   uint64_t reft;          /* both CLVs of every branch in the eigenbasis                                  */
@@ -731,7 +731,7 @@ int epa_dev_rell_kh(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, 
 
 /*
  * Tree geometry: which branch touches which.  A context knows its branches' lengths but not how they join; this call
- * attaches the topology that path distances need (epa_dev_edpl below).  node_prox[b] / node_dist[b] (HOST or device
+ * attaches the topology that path distances need (epa_dev_edpl and epa_dev_krd below).  node_prox[b] / node_dist[b] (HOST or device
  * arrays, [B]) are the node ids, 0 .. n_nodes - 1, at the proximal and the distal end of branch b, in the orientation of
  * epa_dev_score_at: distal[i] of an entry is measured from the node_dist[b] end, the remainder is branch_length[b] -
  * distal[i].  The lengths are the context's own.
@@ -739,6 +739,9 @@ int epa_dev_rell_kh(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, 
  *   root       node_prox[0]; depth[root] = 0.0
  *   depth      depth[child] = depth[parent] + branch_length[edge]: ONE fp64 add per level
  *   child(b)   the end of b that is farther from the root
+ *   rank(b)    b's position, 0 .. B - 1, when the branches are listed in the order a depth-first walk from the root first
+ *              reaches their child ends, a node's branches taken by ascending branch id: a pre-order
+ *   size(b)    the number of branches in the subtree of child(b), b included: that subtree is the ranks [rank, rank + size)
  * EPA_ERR_INVALID_ARG, the text names the first offending branch: n_nodes != B + 1 (the text names both counts); a node id
  * >= n_nodes; a branch with both ends on one node or a length that is negative or not finite; a graph that is not connected (with n_nodes - 1 branches that also
  * rules out a cycle).  A refused call leaves the context, and a topology set before, as they were.  A second call
@@ -747,7 +750,8 @@ int epa_dev_rell_kh(epa_ctx* ctx, const epa_pair* pairs, const double* pendant, 
  * DEPTHS.  Lengths are >= 0 and a rounded add never decreases, so the minimum over the tour between two nodes is the
  * depth of their lowest common ancestor itself, zero-length branches included: a query is two 8-byte loads, O(1).
  * Built once per call on the host without recursion (a ladder tree is an ordinary input), kept in device memory:
- * 8 (2 n_nodes - 1) (floor(log2(2 n_nodes - 1)) + 1) + 12 B bytes, 19.7 MB at 65 537 branches.  The table is optional and
+ * 8 (2 n_nodes - 1) (floor(log2(2 n_nodes - 1)) + 1) + 20 B bytes (the table; per branch the child's depth, its Euler
+ * index, the pre-order rank and the subtree size that epa_dev_krd reads), 20.2 MB at 65 537 branches.  The table is optional and
  * therefore NOT part of epa_dev_footprint's numbers.  (An all-pairs node distance matrix would be 34 GB there.)
  */
 int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32_t* node_prox /* [B] */,
@@ -781,6 +785,58 @@ int epa_dev_set_topology(epa_ctx* ctx, uint32_t n_nodes, const uint32_t* node_pr
  */
 int epa_dev_edpl(epa_ctx* ctx, const epa_pair* pairs, const double* distal, const double* weight, uint64_t n, uint32_t Q,
                  double* row_dist /* [n] or NULL */, double* edpl /* [Q] */);
+
+/*
+ * Kantorovich-Rubinstein (earth mover's) distances between S placement samples on the reference tree, exponent 1 (Evans
+ * and Matsen; `guppy kr`, `gappa analyze krd`), and the edge and clade masses squash clustering and edge PCA start from.
+ * Entry i is a point mass weight[i] at distal[i] on branch pairs[i].branch_id, in epa_dev_edpl's orientation; it belongs
+ * to sample pairs[i].seq_id < S.  Entries come in any order.  Weights are used as given: normalising a sample is the
+ * caller's business.  Root, depth and child(b) are those of epa_dev_set_topology:
+ *   x_i            the point's distance from the child end of its branch: EDPL's x_i, from the same expression
+ *   child side     of a point y of the tree: everything that y separates from the root
+ *   F_s(y)         the total weight of sample s's points strictly on the child side of y
+ *   krd[a][b]      the integral of |F_a(y) - F_b(y)| over all branches by length
+ * F is piecewise constant.  On a branch of length L whose points of a and b, merged by x ascending, are x_1 <= ... <= x_k,
+ * the term is the sum over t of |f_t| (x_{t+1} - x_t) with x_0 = 0 and x_{k+1} = L; f_0 = T_a - T_b, T the mass of a sample
+ * in the subtree hanging from child(b) without the branch's own points; f_t adds +w for a point of a and -w for one of b.
+ * Points at equal x bound a segment of length zero.  With equal sample totals the value does not depend on the root; with
+ * unequal totals it is this rooted definition.
+ *   edge_mass[s][b]   the sum of sample s's weights on b
+ *   clade_mass[s][b]  the mass in the subtree hanging from child(b), b's own points included
+ * The order of the operations is the structure below and no more, so a restatement agrees within a bound, not bit for bit
+ * (tests/krd_ref.py: 8 (B + n_a + n_b + 4) 2^-53 (W_a + W_b) times the tree's length).  Exact, and tested:
+ *   (a) krd[a][a] == 0.0
+ *   (b) krd[a][b] and krd[b][a] have the same bits: computed once, stored twice
+ *   (c) krd[a][b] is a function of the tree and of the entries of a and b alone: the same two samples give the same bits
+ *       in a call with S = 2 and among 65 samples, however the other samples' entries are interleaved and whichever of the
+ *       two has the smaller id, as long as each sample's own entries keep their relative order.  Tile sizes and reduction
+ *       shapes are compile-time constants; nothing depends on S, on the grid or on the other samples
+ *   (d) two samples with the same entries in the same relative order are at 0.0 exactly, and their rows are bit-equal
+ *   (e) the same call returns the same bits every time; there are no floating-point atomics
+ * Structure (krd.hip).  Branches are addressed by pre-order rank: epa_dev_set_topology keeps rank(b), b's position in the
+ * order its walk first reaches the child ends, and size(b), the branches in the subtree of child(b) with b; that subtree is
+ * the ranks [rank, rank + size).  One work item per entry computes (sample, rank, x); two stable radix sorts order the
+ * entries by x's bits (x >= 0) and then by (sample << 32 | rank), so equal x keep entry order.  Per sample, in rank order:
+ * M_s[r], the run's weights added one after the other; P_s[r], the inclusive scan of M_s over the ranks (256 ranks at a
+ * time, a fixed-shape scan plus the carry of the blocks before); T_s(b) = P_s[rank + size - 1] - P_s[rank]; clade_mass =
+ * T + M.  The pair pass runs one 256-thread workgroup per (pair a < b, tile of 1024 ranks): lanes stride the ranks and merge
+ * the two samples' points of their branches -- the points of both samples at one x are taken together, each sample's
+ * weights there added in its own order and f moved by their difference -- and a fixed-shape wave and LDS reduction leaves
+ * one partial per tile; a second kernel adds a pair's partials in tile order and stores [a][b] and [b][a].  A branch that
+ * carries hundreds of points of one sample is one lane's long loop, as in epa_dev_edpl's pair sums.
+ * pairs, distal, weight and the three outputs may be host or device pointers.  Host arrays are validated,
+ * EPA_ERR_INVALID_ARG names the first offending entry: branch_id >= B, seq_id >= S ("sample id"), a distal length that is
+ * negative, not finite or beyond the branch's length, a weight that is negative or not finite (device pairs: an id out of
+ * range is found by the kernels, nothing is read through it, and the call is refused).  No topology set:
+ * EPA_ERR_INVALID_ARG, the text says so.  S must be 1 .. 4096 (EPA_ERR_INVALID_ARG): the output stays within 128 MiB.
+ * n < 2^32.  n == 0 writes zeros.  A sample without entries is legal: F = 0.
+ * Scratch: about 12 S B bytes (P and the run starts), 8 S B more when a mass output is asked for, 68 n bytes of keys,
+ * indices and sorted points plus rocPRIM's sort buffers, and at most 32 MiB of tile partials.  Timer: "krd" (points, sorts,
+ * tables, pair pass and masses together), and inside it "krd_sort" (points, the two sorts, the gather), "krd_tables" (run
+ * starts, M and P) and "krd_pairs" (the pair pass and the sum of its partials).
+ */
+int epa_dev_krd(epa_ctx* ctx, const epa_pair* pairs, const double* distal, const double* weight, uint64_t n, uint32_t S,
+                double* krd /* [S][S] */, double* edge_mass /* [S][B] or NULL */, double* clade_mass /* [S][B] or NULL */);
 
 /*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
@@ -1060,7 +1116,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl", "krd", "krd_sort", "krd_tables", "krd_pairs"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
