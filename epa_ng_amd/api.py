@@ -133,6 +133,8 @@ def dev_lib():
                                    C.c_void_p]
         L.epa_dev_krd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                   C.c_void_p, C.c_void_p]
+        L.epa_dev_squash.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -723,6 +725,25 @@ class Evaluator:
         self._check(self.L.epa_dev_krd(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, S, _ptr(out),
                                        _ptr(edge_out) if masses else None, _ptr(clade_out) if masses else None))
         return (out, edge_out, clade_out) if masses else out
+
+    def squash(self, pairs, distal, weight, S, with_krd=False, out=None, krd_out=None):
+        """Squash clustering of S placement samples (epa_dev_squash) -> (merge_a uint32 [S-1], merge_b uint32 [S-1],
+        merge_dist float64 [S-1], merge_size uint32 [S-1]), with with_krd=True also krd float64 [S][S], the initial matrix
+        (epa_dev_krd's bits).  Samples are clusters 0 .. S-1, step t creates cluster S + t = the average of its members;
+        a step merges the pair of active clusters at the smallest distance (ties: smallest a, then smallest b, a < b).
+        The inputs are those of krd(); needs set_topology().  out: four buffers (host or device) to write into instead;
+        krd_out: the same for the matrix."""
+        n, S = len(pairs), int(S)
+        host = (np.ndarray, list, tuple)
+        distal, weight = (np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, host) else a for a in (distal, weight))
+        m = max(S - 1, 0)
+        if out is None:
+            out = (np.empty(m, np.uint32), np.empty(m, np.uint32), np.empty(m, np.float64), np.empty(m, np.uint32))
+        if with_krd and krd_out is None:
+            krd_out = np.empty((S, S), np.float64)
+        self._check(self.L.epa_dev_squash(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, S, _ptr(out[0]), _ptr(out[1]),
+                                          _ptr(out[2]), _ptr(out[3]), _ptr(krd_out) if with_krd else None))
+        return tuple(out) + ((krd_out,) if with_krd else ())
 
     # ---- profile queries (include/epa_dev.h, "Profile queries"): prof is float64 [Q][stride][states] -- numpy on the
     # host or a torch cuda tensor -- holding the per-state likelihoods of every window position; the rows from a

@@ -2385,6 +2385,13 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "krd_sort")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD_SORT]][epa_ctx::T_KRD_SORT];
   else if (!strcmp(which, "krd_tables")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD_TABLES]][epa_ctx::T_KRD_TABLES];
   else if (!strcmp(which, "krd_pairs")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_KRD_PAIRS]][epa_ctx::T_KRD_PAIRS];
+  else if (!strcmp(which, "squash")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SQUASH]][epa_ctx::T_SQUASH];
+  else if (!strcmp(which, "squash_init")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_SQUASH_INIT]][epa_ctx::T_SQUASH_INIT];
+  // recorded once per merge step: the sums over the steps of the last call (squash.hip)
+  else if (!strcmp(which, "squash_argmin")) return ctx->squash_ms[0];
+  else if (!strcmp(which, "squash_merge")) return ctx->squash_ms[1];
+  else if (!strcmp(which, "squash_row")) return ctx->squash_ms[2];
+  else if (!strcmp(which, "squash_loop_wall")) return ctx->squash_ms[3];   // no event pair: the host's clock
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

@@ -365,7 +365,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 28;   // named by EpaSlot below
+  static constexpr int N_SCRATCH = 29;   // named by EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -390,7 +390,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, T_EDPL = 12, T_KRD = 13, T_KRD_SORT = 14, T_KRD_TABLES = 15, T_KRD_PAIRS = 16, N_TIMERS = 17 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, T_EDPL = 12, T_KRD = 13, T_KRD_SORT = 14, T_KRD_TABLES = 15, T_KRD_PAIRS = 16, T_SQUASH = 17, T_SQUASH_INIT = 18, T_SQUASH_ARGMIN = 19, T_SQUASH_MERGE = 20, T_SQUASH_ROW = 21, N_TIMERS = 22 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -414,6 +414,10 @@ struct epa_ctx {
   const void* clean_stats[N_BANKS] = {};
   bool clean_ctr[N_BANKS] = {};
   int t_last[N_TIMERS] = {};
+  // epa_dev_squash records "squash_argmin", "squash_merge" and "squash_row" once per merge step: the sums over the steps
+  // of the last call, and [3] the host's wall clock around its merge loop, "squash_loop_wall" (squash.hip); < 0: never
+  // run, or the timers are off
+  double squash_ms[4] = {-1.0, -1.0, -1.0, -1.0};
   epa_thorough_stats last_stats{};
 };
 
@@ -489,7 +493,7 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
 // launchers of preplace.hip, select.hip, thorough_*.hip); 0 .. 4, 7 .. 9 and 13 .. 20: the post-placement entry points
 // (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au, _rell_kh) and their launchers
 // (score_at.hip, marginal.hip, rell.hip); 21 .. 22: profile queries; 23 .. 25: duplicate queries (dedup.hip); 26: path
-// distances (treepath.hip); 27: distances between samples (krd.hip).  Names that share a
+// distances (treepath.hip); 27: distances between samples (krd.hip); 28: squash clustering (squash.hip).  Names that share a
 // number never hold live data at the same time:
 //   2   the tip map is read only by the transform kernels of epa_dev_create, queued before any call can stage a span
 //       (SLOT_CLV_*, SLOT_SCALER_*: creation only, in the same way)
@@ -556,6 +560,10 @@ enum EpaSlot : int {
   SLOT_KRD = 27,          // epa_dev_krd (krd.hip): [status | P [S][B] | run starts S B + 1 | rank-ordered lengths and sizes B |
                           //   sort keys, indices and sorted points n | tile partials | M [S][B] when masses are asked | rocprim temp];
                           //   its inputs in 4, 7 and 8 and its host outputs in 3, as epa_dev_edpl keeps them
+  SLOT_SQUASH = 28,       // epa_dev_squash (squash.hip): [D [S][S] | run starts [S][B + 1] and one spare row | two point arenas of 2 n
+                          //   (x, weight, entry) | slot ids, active list, positions, new bases S each | row minima S | merge records
+                          //   S | row partials S x tiles | SLOT_KRD's layout without its sorted points]; inputs and host outputs as
+                          //   epa_dev_krd keeps them
 };
 
 // The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,

@@ -343,4 +343,25 @@ int epa_host_format_fixed(const double* v, size_t n, unsigned int precision, cha
   return 0;
 }
 
+// the writer of --squash (squash_texts): n_names sample names and the merge arrays [n_names - 1] -> the texts of squash.tsv
+// and squash.newick, NUL-terminated.  Returns 0, -1 on error, or 1 when a buffer is too small (*table_len / *newick_len say
+// what is needed, the NUL included)
+int epa_host_squash_texts(const char* const* names, uint32_t n_names, const uint32_t* merge_a, const uint32_t* merge_b,
+                          const double* merge_dist, const uint32_t* merge_size, unsigned int precision, char* table,
+                          size_t* table_len, char* newick, size_t* newick_len) {
+  int small = 0;
+  const int rc = guarded([&] {
+    std::vector<std::string> nm(names, names + n_names);
+    std::string t, k;
+    epa::squash_texts(nm, merge_a, merge_b, merge_dist, merge_size, precision, t, k);
+    small = t.size() + 1 > *table_len || k.size() + 1 > *newick_len;
+    *table_len = t.size() + 1;
+    *newick_len = k.size() + 1;
+    if (small) return;
+    std::memcpy(table, t.c_str(), t.size() + 1);
+    std::memcpy(newick, k.c_str(), k.size() + 1);
+  });
+  return rc ? rc : small;
+}
+
 }  // extern "C"

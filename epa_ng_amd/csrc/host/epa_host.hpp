@@ -590,8 +590,23 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
 // on the reference tree (epa_dev_krd) -> <outdir>/krd.tsv, and with `masses` the per-edge and per-clade masses ->
 // <outdir>/edge_masses.tsv, clade_masses.tsv (columns: edge_num).  Every file is parsed and validated before the device
 // is created; the outputs are replaced like epa_result.jplace is, and a failed write leaves none behind.
+// `squash`: the samples are clustered as well (epa_dev_squash, which also returns the matrix: krd.tsv is the same file) ->
+// <outdir>/squash.tsv and squash.newick (squash_texts below).
 Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, const std::vector<std::string>& names,
-                    const std::string& outdir, const Options& options, bool masses, int device = 0);
+                    const std::string& outdir, const Options& options, bool masses, bool squash = false, int device = 0);
+
+// The two texts of --squash from the sample names (S of them) and the merge arrays of epa_dev_squash ([S - 1] each).
+//   table   a header line step<TAB>a<TAB>b<TAB>distance<TAB>size, then one line per merge: a and b are sample names, or
+//           cluster<k> for the cluster of step k; the distance in fixed notation with `precision` digits
+//   newick  the cluster tree, one line: leaves named after the samples, inner nodes labelled cluster<t>, the smaller-id
+//           child first; height(leaf) = 0, height(S + t) = merge_dist[t] / 2, the branch to a child is height(parent) -
+//           height(child) (UPGMA's convention) in fixed notation -- negative where the distances invert
+// Throws where the arrays are no linkage (an id that does not exist yet at its step, or is merged twice).  Names are
+// written as they are: the caller refuses those that would need quoting (squash_name_ok).
+void squash_texts(const std::vector<std::string>& names, const uint32_t* merge_a, const uint32_t* merge_b, const double* merge_dist,
+                  const uint32_t* merge_size, unsigned int precision, std::string& table, std::string& newick);
+// false: the name holds one of ( ) , : ; [ ] ' or white space
+bool squash_name_ok(const std::string& name);
 
 // -q reads.fastq: every chunk of an aligned FASTQ premasked (both lines), encoded, turned into rows of state
 // likelihoods (epa_profile_from_phred) and placed by epa_dev_place_chunk_profile; LWR, filter and jplace as simple_mpi.

@@ -2,9 +2,13 @@
 // rows become point masses (multiplicity x like_weight_ratio at edge_num / distal_length, read_jplace_masses), normalised
 // to a total of 1; the matrix, and with --krd-masses the per-edge and per-clade masses, come from ONE epa_dev_krd call on
 // the tree's topology.  Everything that can be refused without a device is refused before one is opened.
+// --squash: the same samples clustered by ONE epa_dev_squash call, which returns the matrix too (krd.tsv is byte for byte
+// the file written without the flag); squash.tsv and squash.newick come from squash_texts.
 #include <chrono>
 #include <cmath>
+#include <cctype>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 
@@ -37,10 +41,54 @@ void write_table(const std::string& path, const std::vector<std::string>& header
   if (!os) { os.close(); std::remove(path.c_str()); throw std::runtime_error{"writing " + path + " failed"}; }
 }
 
+void write_text(const std::string& path, const std::string& text) {
+  std::ofstream os(path);
+  if (!os) throw std::runtime_error{"cannot open " + path};
+  os << text;
+  os.flush();
+  if (!os) { os.close(); std::remove(path.c_str()); throw std::runtime_error{"writing " + path + " failed"}; }
+}
+
 }  // namespace
 
+bool squash_name_ok(const std::string& name) {
+  for (const char ch : name)
+    if (std::strchr("(),:;[]'", ch) || std::isspace((unsigned char)ch)) return false;
+  return true;
+}
+
+void squash_texts(const std::vector<std::string>& names, const uint32_t* merge_a, const uint32_t* merge_b, const double* merge_dist,
+                  const uint32_t* merge_size, unsigned int precision, std::string& table, std::string& newick) {
+  const size_t S = names.size(), steps = S ? S - 1 : 0;
+  if (!S) throw std::runtime_error{"squash: no samples"};
+  std::vector<char> buf(400 + (size_t)precision);
+  auto fixed = [&](double v) { return std::string(buf.data(), format_fixed(buf.data(), buf.size(), v, precision)); };
+  auto label = [&](size_t id) { return id < S ? names[id] : "cluster" + std::to_string(id - S); };
+  auto height = [&](size_t id) { return id < S ? 0.0 : merge_dist[id - S] / 2; };
+  table = "step\ta\tb\tdistance\tsize\n";
+  std::vector<std::string> text(S + steps);   // a cluster's subtree, moved into its parent's
+  std::vector<char> used(S + steps, 0);
+  for (size_t s = 0; s < S; ++s) text[s] = names[s];
+  for (size_t t = 0; t < steps; ++t) {
+    const size_t a = merge_a[t], b = merge_b[t], me = S + t;
+    if (!(a < b && b < me) || used[a] || used[b])
+      throw std::runtime_error{"squash: step " + std::to_string(t) + " merges " + std::to_string(a) + " and " + std::to_string(b) +
+                               ": not two clusters that exist and are unmerged at that step"};
+    used[a] = used[b] = 1;
+    table += std::to_string(t) + '\t' + label(a) + '\t' + label(b) + '\t' + fixed(merge_dist[t]) + '\t' + std::to_string(merge_size[t]) + '\n';
+    std::string node = "(";
+    node += text[a]; node += ':'; node += fixed(height(me) - height(a)); node += ',';
+    node += text[b]; node += ':'; node += fixed(height(me) - height(b)); node += ')';
+    node += label(me);
+    std::string().swap(text[a]);
+    std::string().swap(text[b]);
+    text[me].swap(node);
+  }
+  newick = text[S + steps - 1] + ";\n";
+}
+
 Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, const std::vector<std::string>& names,
-                    const std::string& outdir, const Options& options, bool masses, int device) {
+                    const std::string& outdir, const Options& options, bool masses, bool squash, int device) {
   using clk = std::chrono::steady_clock;
   // ---- everything that can be refused without a device
   if (tree.mapper())
@@ -89,10 +137,25 @@ Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, con
   dev.set_topology(tree);
   std::vector<double> krd(S * S), edge, clade;
   if (masses) { edge.resize(S * B); clade.resize(S * B); }
-  const int rc = epa_dev_krd(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)S, krd.data(),
-                             masses ? edge.data() : nullptr, masses ? clade.data() : nullptr);
-  if (rc != EPA_OK)
-    throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+  auto check = [&](int rc) {
+    if (rc != EPA_OK)
+      throw std::runtime_error{std::string(epa_dev_last_error(dev.ctx())) + " (epa_dev status " + std::to_string(rc) + ")"};
+  };
+  std::vector<uint32_t> merge_a, merge_b, merge_size;
+  std::vector<double> merge_dist;
+  if (squash) {
+    merge_a.resize(S - 1); merge_b.resize(S - 1); merge_size.resize(S - 1); merge_dist.resize(S - 1);
+    check(epa_dev_squash(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)S, merge_a.data(),
+                         merge_b.data(), merge_dist.data(), merge_size.data(), krd.data()));
+    if (masses) {   // the masses are epa_dev_krd's outputs; its matrix has the bits the call above returned
+      std::vector<double> again(S * S);
+      check(epa_dev_krd(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)S, again.data(), edge.data(),
+                        clade.data()));
+    }
+  } else {
+    check(epa_dev_krd(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)S, krd.data(),
+                      masses ? edge.data() : nullptr, masses ? clade.data() : nullptr));
+  }
   st.seconds_place = std::chrono::duration<double>(clk::now() - ts).count();
   std::cout << "Kantorovich-Rubinstein distances between " << S << " samples (" << st.pairs << " placements)." << std::endl;
 
@@ -105,6 +168,13 @@ Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, con
     for (size_t b = 0; b < B; ++b) edges[b] = std::to_string(b);
     write_table(dir + "edge_masses.tsv", edges, names, edge, B, options.precision);
     write_table(dir + "clade_masses.tsv", edges, names, clade, B, options.precision);
+  }
+  if (squash) {
+    std::string table, newick;
+    squash_texts(names, merge_a.data(), merge_b.data(), merge_dist.data(), merge_size.data(), options.precision, table, newick);
+    write_text(dir + "squash.tsv", table);
+    write_text(dir + "squash.newick", newick);
+    std::cout << "Squash clustering: " << S - 1 << " merges." << std::endl;
   }
   st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();
   st.seconds_loop = std::chrono::duration<double>(clk::now() - t_loop).count();

@@ -74,6 +74,13 @@ static void usage() {
       "                        refused with it; --preserve-rooting off for rooted trees\n"
       "  --krd-masses          with --krd: also edge_masses.tsv and clade_masses.tsv, per sample the mass on every edge and in the\n"
       "                        subtree below it (the edge included), columns by edge_num: the inputs of squash clustering and edge PCA\n"
+      "  --squash              with --krd: squash clustering of the samples (Matsen & Evans; `guppy squash`, `gappa analyze\n"
+      "                        squash`): the two clusters at the smallest distance are merged into the average of their samples'\n"
+      "                        masses, whose distances to the others are computed on the tree, until one is left.  Writes\n"
+      "                        squash.tsv (step<TAB>a<TAB>b<TAB>distance<TAB>size; a and b are sample names or cluster<k>, the\n"
+      "                        cluster of step k) and squash.newick (the cluster tree: inner nodes cluster<k> at height distance / 2,\n"
+      "                        branch = height(parent) - height(child), negative where the distances invert) beside krd.tsv.\n"
+      "                        Two files at least; sample names with ( ) , : ; [ ] ' or white space are refused\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -115,7 +122,7 @@ int main(int argc, char** argv) {
   int device = 0;
   bool dedup = false;   // --dedup: the loop of place_dedup.cpp
   std::string krd_list;   // --krd: comma-separated jplace files, one sample each (krd_samples.cpp)
-  bool krd_given = false, krd_masses = false;
+  bool krd_given = false, krd_masses = false, krd_squash = false;
   bool device_given = false, rell_given = false, prior_given = false, nodes_given = false, rank_given = false;
   std::string diag_flag;   // --host-heuristic / --device-min-chunk: steer the coded chunk loop only
   std::vector<int> devices;
@@ -162,6 +169,7 @@ int main(int argc, char** argv) {
     else if (a == "--edpl") opt.edpl = true;
     else if (a == "--krd") { krd_list = need(i); krd_given = true; }
     else if (a == "--krd-masses") krd_masses = true;
+    else if (a == "--squash") krd_squash = true;
     else if (a == "--prior-mean") {
       const std::string v = need(i);
       char* end = nullptr;
@@ -236,6 +244,7 @@ int main(int argc, char** argv) {
   // --krd compares existing results: what it does not do is refused before any file is parsed or a device is opened
   std::vector<std::string> krd_files_list, krd_names;
   if (krd_masses && !krd_given) { std::cerr << "--krd-masses adds the mass tables to the output of --krd and needs it: --krd A.jplace,B.jplace --krd-masses\n"; return 1; }
+  if (krd_squash && !krd_given) { std::cerr << "--squash clusters the samples of --krd and needs it: --krd A.jplace,B.jplace,C.jplace --squash\n"; return 1; }
   if (krd_given) {
     const char* const what = "--krd (distances between placement samples) ";
     if (!query_file.empty()) { std::cerr << what << "reads placements, not sequences: -q is not supported with it\n"; return 1; }
@@ -271,6 +280,18 @@ int main(int argc, char** argv) {
       std::cerr << "--krd: one call compares 1 .. 4096 files (" << krd_files_list.size() << " given)\n";
       return 1;
     }
+  }
+  if (krd_squash) {
+    if (krd_files_list.size() < 2) {
+      std::cerr << "--squash: clustering needs two samples at least (" << krd_files_list.size() << " file given)\n";
+      return 1;
+    }
+    for (size_t k = 0; k < krd_names.size(); ++k)
+      if (!squash_name_ok(krd_names[k])) {
+        std::cerr << "--squash: the sample name '" << krd_names[k] << "' (" << krd_files_list[k] << ") holds one of ( ) , : ; [ ] ' or white "
+                  << "space and would need quoting in squash.newick: rename the file\n";
+        return 1;
+      }
   }
   if (tree_file.empty() || ref_file.empty() || (query_file.empty() && !krd_given)) { usage(); return 1; }
   // the reference's CLI checks (src/main.cpp:165-218, 368-370)
@@ -407,7 +428,7 @@ int main(int argc, char** argv) {
     if (devices.empty()) devices.push_back(device);
     const bool rank_mode = world > 1 || !comm_file.empty();   // a 1-rank communicator is legal (tests, 1-GPU nodes)
     const Run_Stats st = krd_given
-        ? krd_files(tree, krd_files_list, krd_names, outdir, opt, krd_masses, devices[0])
+        ? krd_files(tree, krd_files_list, krd_names, outdir, opt, krd_masses, krd_squash, devices[0])
         : fastq
         ? place_profile_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
         : dedup

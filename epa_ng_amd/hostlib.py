@@ -312,6 +312,29 @@ def fastq_copy(in_file, out_file):
     return int(n)
 
 
+def squash_texts(names, merge_a, merge_b, merge_dist, merge_size, precision=10):
+    """the writer of epa-ng-amd --squash: sample names and the merge arrays of Evaluator.squash -> (text of squash.tsv,
+    text of squash.newick); RuntimeError where the arrays are no linkage.  Needs no device."""
+    lib = host_lib()
+    u32p, szp = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)
+    lib.epa_host_squash_texts.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, u32p, u32p, C.POINTER(C.c_double), u32p, C.c_uint,
+                                          C.c_char_p, szp, C.c_char_p, szp]
+    a, b, sz = (np.ascontiguousarray(v, np.uint32) for v in (merge_a, merge_b, merge_size))
+    d = np.ascontiguousarray(merge_dist, np.float64)
+    if not len(a) == len(b) == len(d) == len(sz) == len(names) - 1:
+        raise ValueError("squash_texts: %d names need %d merges" % (len(names), len(names) - 1))
+    cap = [C.c_size_t(1 << 16), C.c_size_t(1 << 16)]
+    for _ in range(2):
+        bufs = [C.create_string_buffer(c.value) for c in cap]
+        rc = lib.epa_host_squash_texts(_strs(names), len(names), a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), _dp(d),
+                                       sz.ctypes.data_as(u32p), int(precision), bufs[0], C.byref(cap[0]), bufs[1], C.byref(cap[1]))
+        if rc < 0:
+            raise RuntimeError(lib.epa_host_last_error().decode())
+        if rc == 0:
+            return bufs[0].value.decode(), bufs[1].value.decode()
+    raise RuntimeError("squash_texts: the texts did not fit")
+
+
 def heuristic(lnl, mode="dynamic", thresh=0.99999):
     lnl = np.ascontiguousarray(lnl, np.float64)
     Q, B = lnl.shape

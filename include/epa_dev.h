@@ -839,6 +839,50 @@ int epa_dev_krd(epa_ctx* ctx, const epa_pair* pairs, const double* distal, const
                 double* krd /* [S][S] */, double* edge_mass /* [S][B] or NULL */, double* clade_mass /* [S][B] or NULL */);
 
 /*
+ * Squash clustering of the S samples (Matsen and Evans 2013; `guppy squash`, `gappa analyze squash`): hierarchical
+ * clustering under the distance above in which a merged cluster is a new mass distribution on the tree, the average of
+ * its member samples, whose distances to the other clusters are computed on the tree.  The inputs are epa_dev_krd's.
+ *   cluster ids    the samples are clusters 0 .. S - 1; merge step t = 0 .. S - 2 creates cluster S + t
+ *   a cluster      C with member samples m(C) is this entry sequence: the members in ascending sample id, each member's
+ *                  entries in entry order, entry i with weight[i] / |m(C)| -- one fp64 division of the original weight,
+ *                  never a product of earlier scalings.  (Squash's count-weighted average of the two merged clusters.)  A
+ *                  cluster depends on its member set, not on the merge history
+ *   D(C, C')       epa_dev_krd's value for two samples holding those two entry sequences, BIT FOR BIT (property (c) above
+ *                  makes that well defined)
+ *   step t         among all pairs of active clusters the smallest D, compared as doubles with <; on equal values the
+ *                  smallest id a, then the smallest id b, a < b.  merge_a[t] = a, merge_b[t] = b, merge_dist[t] = D,
+ *                  merge_size[t] = |m(a)| + |m(b)|; a and b retire, S + t is active with m(a) and m(b) united
+ * The argmin takes a valid pair whatever the values are, so there are exactly S - 1 steps.  Distances need NOT grow with t
+ * (an average can be nearer to a third cluster than either part was), and nothing assumes it.
+ * krd, when given, receives the initial matrix: the bits epa_dev_krd returns for the same call.  S == 1 writes nothing to
+ * the merge arrays.  n == 0 and samples without entries are legal: distances of 0.0, decided by the tie rule.
+ * Every array may be a host or a device pointer.  Validation, its wording (led by "squash:") and the limits are
+ * epa_dev_krd's -- S in 1 .. 4096, no topology refused, host arrays checked with the first offending entry named, ids in
+ * device arrays found by the kernels and the call refused -- except that n < 2^31 (point storage is addressed with 32
+ * bits).  A refused call leaves the context and the results of later calls as they were.
+ * Structure (squash.hip).  The initial state is epa_dev_krd's own: its kernels, from one shared text (krd_kernels.hpp),
+ * leave the sorted points, M, P, the run starts and the matrix.  Per step: a two-level fixed-shape argmin over the active
+ * part of the device-resident matrix; ONE read-back of the winning record (24 bytes); one work item per rank merges the
+ * children's runs into the new cluster's point list (sorted by rank, x, sample id, entry order; weight / |C| formed from the
+ * original weight) and sums its M the way the run kernel does; the scan kernel forms its P; then one 256-thread workgroup
+ * per (active cluster, tile of 1024 ranks) with the new cluster as the fixed side repeats the pair pass's lane -> rank
+ * mapping, branch merge, butterfly and four-wave order, and a second kernel adds the partials in tile order into both
+ * matrix entries.  The same operations in the same shape on rows formed the same way: hence the same bits.  Late steps
+ * launch small grids (active x ceil(B / 1024) workgroups).  The argmin rereads the active part of the matrix every step.
+ * Scratch (its own bank, beside epa_dev_krd's): 8 S^2 (matrix) + 12 S B (P and run starts) + 80 n (two arenas of 2 n
+ * points of 20 bytes: new lists are appended, and the active lists, which always partition the entries, are compacted
+ * into the other arena when one is full) + 48 n of sort keys and indices plus rocPRIM's buffers + 8 S ceil(B / 1024) of
+ * row partials, at most 32 MiB of pair partials and a few arrays of S words.
+ * Timers: "squash" (the whole call on the device's time line, the host's read-backs included), inside it "squash_init"
+ * (the initial state) and, summed over the steps, "squash_argmin", "squash_merge" (list, M, P, compaction) and
+ * "squash_row"; "squash_loop_wall" is the host's wall clock around the merge loop (no event pair), for the share of a
+ * step that is not kernel time.
+ */
+int epa_dev_squash(epa_ctx* ctx, const epa_pair* pairs, const double* distal, const double* weight, uint64_t n, uint32_t S,
+                   uint32_t* merge_a /* [S-1] */, uint32_t* merge_b /* [S-1] */, double* merge_dist /* [S-1] */,
+                   uint32_t* merge_size /* [S-1] */, double* krd /* [S][S] or NULL */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -1116,7 +1160,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl", "krd", "krd_sort", "krd_tables", "krd_pairs"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl", "krd", "krd_sort", "krd_tables", "krd_pairs", "squash", "squash_init", "squash_argmin", "squash_merge", "squash_row", "squash_loop_wall"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
