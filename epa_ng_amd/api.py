@@ -135,6 +135,8 @@ def dev_lib():
                                   C.c_void_p, C.c_void_p]
         L.epa_dev_squash.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.epa_dev_epca.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.epa_dev_marginal_like.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.c_void_p, C.c_void_p]
@@ -744,6 +746,34 @@ class Evaluator:
         self._check(self.L.epa_dev_squash(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, S, _ptr(out[0]), _ptr(out[1]),
                                           _ptr(out[2]), _ptr(out[3]), _ptr(krd_out) if with_krd else None))
         return tuple(out) + ((krd_out,) if with_krd else ())
+
+    def epca(self, pairs, distal, weight, S, K, with_imbalance=False, with_gram=False, out=None):
+        """Edge principal components of S placement samples (epa_dev_epca) -> (eigenvalue float64 [K], edge_vec float64
+        [K][B], proj float64 [S][K], total_var float64 [1], sweeps uint32 [1]), then imbalance float64 [S][B] with
+        with_imbalance=True and gram float64 [S][S] with with_gram=True.  eigenvalue: of the sample covariance of the
+        centred edge imbalances; edge_vec: unit length, 0.0 on edges next to a leaf, the entry of largest magnitude
+        positive; proj: the samples on those axes; total_var: the covariance's trace; sweeps: Jacobi sweeps run.  The
+        inputs are those of krd(); needs set_topology(); S in 2 .. 1024, K in 1 .. S-1.  out: the five (to seven) buffers,
+        host or device, to write into instead."""
+        n, S, K = len(pairs), int(S), int(K)
+        host = (np.ndarray, list, tuple)
+        distal, weight = (np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, host) else a for a in (distal, weight))
+        if out is None:
+            k, s = max(K, 0), max(S, 0)
+            out = [np.empty(k, np.float64), np.empty((k, self.B), np.float64), np.empty((s, k), np.float64),
+                   np.empty(1, np.float64), np.empty(1, np.uint32)]
+            if with_imbalance:
+                out.append(np.empty((s, self.B), np.float64))
+            if with_gram:
+                out.append(np.empty((s, s), np.float64))
+        if len(out) != 5 + bool(with_imbalance) + bool(with_gram):
+            raise ValueError("epca: out holds %d buffers, %d are written" % (len(out), 5 + bool(with_imbalance) + bool(with_gram)))
+        imb = out[5] if with_imbalance else None
+        gram = out[5 + bool(with_imbalance)] if with_gram else None
+        self._check(self.L.epa_dev_epca(self.h, _ptr(pairs), _ptr(distal), _ptr(weight), n, S, K, _ptr(out[0]), _ptr(out[1]),
+                                        _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(imb) if with_imbalance else None,
+                                        _ptr(gram) if with_gram else None))
+        return tuple(out)
 
     # ---- profile queries (include/epa_dev.h, "Profile queries"): prof is float64 [Q][stride][states] -- numpy on the
     # host or a torch cuda tensor -- holding the per-state likelihoods of every window position; the rows from a

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-DEV_SOURCES = ["epa_dev.hip", "chunk.hip", "preplace.hip", "select.hip", "thorough_dna.hip", "thorough_dna_tipd.hip", "thorough_dna_tipd2h.hip", "thorough_aa.hip", "thorough_aa_mfma.hip", "thorough_generic.hip", "score_at.hip", "marginal.hip", "rell.hip", "profile.hip", "dedup.hip", "treepath.hip", "krd.hip", "squash.hip", "comm.hip"]
+DEV_SOURCES = ["epa_dev.hip", "chunk.hip", "preplace.hip", "select.hip", "thorough_dna.hip", "thorough_dna_tipd.hip", "thorough_dna_tipd2h.hip", "thorough_aa.hip", "thorough_aa_mfma.hip", "thorough_generic.hip", "score_at.hip", "marginal.hip", "rell.hip", "profile.hip", "dedup.hip", "treepath.hip", "krd.hip", "squash.hip", "epca.hip", "comm.hip"]
 # Per-file code-generation tuning, measured same-box (round 4, exp/ab.sh / ab_aa.sh, two interleaved rounds):
 # the iterative ILP scheduler removes the dominant nucleotide kernel's scratch (44 -> 0 B per lane) and is worth
 # 5.24 -> 5.17 ms per 262k-pair launch; the 20-state kernel 4.44 -> 4.37 ms per 25.7k pairs.  (iterative-minreg /
@@ -20,7 +20,7 @@ EXTRA_FLAGS = {"thorough_dna.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-
                "thorough_dna_tipd.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
                "thorough_aa_mfma.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
 EXTRA_DEPS = {"thorough_dna_tipd.hip": ["thorough_dna.hip"], "thorough_dna_tipd2h.hip": ["thorough_dna.hip"],
-              "krd.hip": ["krd_kernels.hpp"], "squash.hip": ["krd_kernels.hpp"]}   # sources a file includes
+              "krd.hip": ["krd_kernels.hpp"], "squash.hip": ["krd_kernels.hpp"], "epca.hip": ["krd_kernels.hpp"]}   # sources a file includes
 DEV_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"),
              "-I", CSRC, "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 

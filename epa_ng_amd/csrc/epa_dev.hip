@@ -2392,6 +2392,13 @@ extern "C" double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which) 
   else if (!strcmp(which, "squash_merge")) return ctx->squash_ms[1];
   else if (!strcmp(which, "squash_row")) return ctx->squash_ms[2];
   else if (!strcmp(which, "squash_loop_wall")) return ctx->squash_ms[3];   // no event pair: the host's clock
+  else if (!strcmp(which, "epca")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_EPCA]][epa_ctx::T_EPCA];
+  else if (!strcmp(which, "epca_tables")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_EPCA_TABLES]][epa_ctx::T_EPCA_TABLES];
+  else if (!strcmp(which, "epca_gram")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_EPCA_GRAM]][epa_ctx::T_EPCA_GRAM];
+  else if (!strcmp(which, "epca_project")) t = &ctx->t_bank[ctx->t_last[epa_ctx::T_EPCA_PROJECT]][epa_ctx::T_EPCA_PROJECT];
+  // recorded once per Jacobi sweep: the sum over the sweeps of the last call (epca.hip)
+  else if (!strcmp(which, "epca_eig")) return ctx->epca_ms[0];
+  else if (!strcmp(which, "epca_loop_wall")) return ctx->epca_ms[1];   // no event pair: the host's clock
   if (!t || !t->valid) return -1.0;
   if (hipEventSynchronize(t->b) != hipSuccess) return -1.0;
   float ms = -1.f;

@@ -365,7 +365,7 @@ struct epa_ctx {
   // Banks: 0 = the direct entry points (caller's stream), 1 .. N_SLOTS = the slots of the chunk
   // pipeline, whose kernels run concurrently on their own streams and therefore share no scratch
   // (allocated on first use: a two-slot caller pays for two).
-  static constexpr int N_SCRATCH = 29;   // named by EpaSlot below
+  static constexpr int N_SCRATCH = 30;   // named by EpaSlot below
   static constexpr int N_SLOTS = 24;
   static constexpr int N_BANKS = 1 + N_SLOTS;
   int bank = 0;
@@ -390,7 +390,7 @@ struct epa_ctx {
   // kernel-family timers (epa_dev_last_kernel_ms): one set per scratch bank -- the pipeline slots run
   // concurrently on their own streams, a single set would have its start event re-recorded by slot k + 1
   // before slot k records its stop; t_last = the bank whose timer was stopped last
-  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, T_EDPL = 12, T_KRD = 13, T_KRD_SORT = 14, T_KRD_TABLES = 15, T_KRD_PAIRS = 16, T_SQUASH = 17, T_SQUASH_INIT = 18, T_SQUASH_ARGMIN = 19, T_SQUASH_MERGE = 20, T_SQUASH_ROW = 21, N_TIMERS = 22 };
+  enum { T_PREPLACE = 0, T_THOROUGH = 1, T_SELECT = 2, T_SCORE = 3, T_SITES = 4, T_RELL = 5, T_MARGINAL = 6, T_RELL_TESTS = 7, T_RELL_AU = 8, T_RELL_KH = 9, T_PREPLACE_PROFILE = 10, T_DEDUP = 11, T_EDPL = 12, T_KRD = 13, T_KRD_SORT = 14, T_KRD_TABLES = 15, T_KRD_PAIRS = 16, T_SQUASH = 17, T_SQUASH_INIT = 18, T_SQUASH_ARGMIN = 19, T_SQUASH_MERGE = 20, T_SQUASH_ROW = 21, T_EPCA = 22, T_EPCA_TABLES = 23, T_EPCA_GRAM = 24, T_EPCA_EIG = 25, T_EPCA_PROJECT = 26, N_TIMERS = 27 };
   EvTimer t_lookup;
   // blocked layout: events e[0] build e[1] preplace e[2] build ... of the bank's last chunk body (blk_ev_n valid)
   std::vector<hipEvent_t> blk_ev[N_BANKS];
@@ -418,6 +418,9 @@ struct epa_ctx {
   // of the last call, and [3] the host's wall clock around its merge loop, "squash_loop_wall" (squash.hip); < 0: never
   // run, or the timers are off
   double squash_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+  // epa_dev_epca records "epca_eig" once per Jacobi sweep: [0] the sum over the sweeps of the last call, [1] the host's
+  // wall clock around its Jacobi loop, "epca_loop_wall" (epca.hip); < 0: never run, or the timers are off
+  double epca_ms[2] = {-1.0, -1.0};
   epa_thorough_stats last_stats{};
 };
 
@@ -493,8 +496,8 @@ inline EvTimer& epa_t(epa_ctx* ctx, int which) { ctx->t_last[which] = ctx->bank;
 // launchers of preplace.hip, select.hip, thorough_*.hip); 0 .. 4, 7 .. 9 and 13 .. 20: the post-placement entry points
 // (epa_dev_score_at, _site_lnl, _marginal_like, _rell_support, _rell_tests, _rell_au, _rell_kh) and their launchers
 // (score_at.hip, marginal.hip, rell.hip); 21 .. 22: profile queries; 23 .. 25: duplicate queries (dedup.hip); 26: path
-// distances (treepath.hip); 27: distances between samples (krd.hip); 28: squash clustering (squash.hip).  Names that share a
-// number never hold live data at the same time:
+// distances (treepath.hip); 27: distances between samples (krd.hip); 28: squash clustering (squash.hip); 29: edge PCA
+// (epca.hip).  Names that share a number never hold live data at the same time:
 //   2   the tip map is read only by the transform kernels of epa_dev_create, queued before any call can stage a span
 //       (SLOT_CLV_*, SLOT_SCALER_*: creation only, in the same way)
 //   6   the preplacement's status words are read (preplace_check_status; k_pack_readback through SelectPending::
@@ -564,6 +567,10 @@ enum EpaSlot : int {
                           //   (x, weight, entry) | slot ids, active list, positions, new bases S each | row minima S | merge records
                           //   S | row partials S x tiles | SLOT_KRD's layout without its sorted points]; inputs and host outputs as
                           //   epa_dev_krd keeps them
+  SLOT_EPCA = 29,         // epa_dev_epca (epca.hip): [XT [B][S up to 16] | the Jacobi matrix and the rotations' product [m][m] each, m = S
+                          //   up to even | the circle method's pairs [m - 1][m / 2] | per-pair (c, s, t) | threshold and count | Gram
+                          //   partials (tile pairs x slices x 256, at most 64 MiB a launch) | eigenvalues, columns, signs K each |
+                          //   staged outputs | SLOT_KRD's layout with M]; inputs and host outputs as epa_dev_krd keeps them
 };
 
 // The entries of a post-placement call as the device sees them (EntryCall::stage, epa_dev.hip): n rows (pair, pendant,

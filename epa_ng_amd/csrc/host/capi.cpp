@@ -364,4 +364,24 @@ int epa_host_squash_texts(const char* const* names, uint32_t n_names, const uint
   return rc ? rc : small;
 }
 
+// the writer of --epca (epca_texts): n_names sample names, K components on B branches -> the texts of
+// epca_eigenvalues.tsv, epca_projection.tsv and epca_edges.tsv, NUL-terminated.  Returns 0, -1 on error, or 1 when a
+// buffer is too small (len[0 .. 3) say what is needed, the NUL included)
+int epa_host_epca_texts(const char* const* names, uint32_t n_names, uint32_t K, uint32_t B, const double* eigenvalue, double total_var,
+                        const double* edge_vec, const double* proj, unsigned int precision, char* eigenvalues, char* projection,
+                        char* edges, size_t* len) {
+  int small = 0;
+  const int rc = guarded([&] {
+    std::vector<std::string> nm(names, names + n_names);
+    std::string t[3];
+    epa::epca_texts(nm, K, B, eigenvalue, total_var, edge_vec, proj, precision, t[0], t[1], t[2]);
+    char* const dst[3] = {eigenvalues, projection, edges};
+    for (int k = 0; k < 3; ++k) small |= t[k].size() + 1 > len[k];
+    for (int k = 0; k < 3; ++k) len[k] = t[k].size() + 1;
+    if (small) return;
+    for (int k = 0; k < 3; ++k) std::memcpy(dst[k], t[k].c_str(), t[k].size() + 1);
+  });
+  return rc ? rc : small;
+}
+
 }  // extern "C"

@@ -592,8 +592,11 @@ Run_Stats rescore(const Tree& tree, const std::string& jplace_file, const std::s
 // is created; the outputs are replaced like epa_result.jplace is, and a failed write leaves none behind.
 // `squash`: the samples are clustered as well (epa_dev_squash, which also returns the matrix: krd.tsv is the same file) ->
 // <outdir>/squash.tsv and squash.newick (squash_texts below).
+// `epca` = K > 0: the first K edge principal components of the samples as well (one epa_dev_epca call beside the one
+// above; krd.tsv is the same file) -> <outdir>/epca_eigenvalues.tsv, epca_projection.tsv and epca_edges.tsv (epca_texts).
 Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, const std::vector<std::string>& names,
-                    const std::string& outdir, const Options& options, bool masses, bool squash = false, int device = 0);
+                    const std::string& outdir, const Options& options, bool masses, bool squash = false, int device = 0,
+                    unsigned int epca = 0);
 
 // The two texts of --squash from the sample names (S of them) and the merge arrays of epa_dev_squash ([S - 1] each).
 //   table   a header line step<TAB>a<TAB>b<TAB>distance<TAB>size, then one line per merge: a and b are sample names, or
@@ -607,6 +610,18 @@ void squash_texts(const std::vector<std::string>& names, const uint32_t* merge_a
                   const uint32_t* merge_size, unsigned int precision, std::string& table, std::string& newick);
 // false: the name holds one of ( ) , : ; [ ] ' or white space
 bool squash_name_ok(const std::string& name);
+
+// The three texts of --epca K from the sample names (S of them) and the outputs of epa_dev_epca (eigenvalue [K], edge_vec
+// [K][B], proj [S][K]); every number in fixed notation with `precision` digits.
+//   eigenvalues  a header line component<TAB>eigenvalue<TAB>fraction, then one line per component, counted from 1;
+//                fraction = eigenvalue / total_var, and 0 when total_var is 0
+//   projection   a header line sample<TAB>pc1 .. pcK, then one line per sample name
+//   edges        a header line edge_num<TAB>pc1 .. pcK, then one line per edge in ascending edge_num (the branch id, as
+//                in the mass tables); excluded edges print zeros
+// Throws where S < 2 or K is not in 1 .. S - 1.
+void epca_texts(const std::vector<std::string>& names, size_t K, size_t B, const double* eigenvalue, double total_var,
+                const double* edge_vec, const double* proj, unsigned int precision, std::string& eigenvalues, std::string& projection,
+                std::string& edges);
 
 // -q reads.fastq: every chunk of an aligned FASTQ premasked (both lines), encoded, turned into rows of state
 // likelihoods (epa_profile_from_phred) and placed by epa_dev_place_chunk_profile; LWR, filter and jplace as simple_mpi.

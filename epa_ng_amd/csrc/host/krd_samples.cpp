@@ -4,6 +4,8 @@
 // the tree's topology.  Everything that can be refused without a device is refused before one is opened.
 // --squash: the same samples clustered by ONE epa_dev_squash call, which returns the matrix too (krd.tsv is byte for byte
 // the file written without the flag); squash.tsv and squash.newick come from squash_texts.
+// --epca K: ONE epa_dev_epca call on the same masses beside the call above, which it does not touch; epca_eigenvalues.tsv,
+// epca_projection.tsv and epca_edges.tsv come from epca_texts.
 #include <chrono>
 #include <cmath>
 #include <cctype>
@@ -87,8 +89,36 @@ void squash_texts(const std::vector<std::string>& names, const uint32_t* merge_a
   newick = text[S + steps - 1] + ";\n";
 }
 
+void epca_texts(const std::vector<std::string>& names, size_t K, size_t B, const double* eigenvalue, double total_var,
+                const double* edge_vec, const double* proj, unsigned int precision, std::string& eigenvalues, std::string& projection,
+                std::string& edges) {
+  const size_t S = names.size();
+  if (S < 2) throw std::runtime_error{"epca: " + std::to_string(S) + " samples: principal components need two at least"};
+  if (K < 1 || K >= S)
+    throw std::runtime_error{"epca: " + std::to_string(K) + " components: " + std::to_string(S) + " samples have 1 .. " + std::to_string(S - 1)};
+  std::vector<char> buf(400 + (size_t)precision);
+  auto fixed = [&](double v) { return std::string(buf.data(), format_fixed(buf.data(), buf.size(), v, precision)); };
+  std::string pcs;
+  for (size_t k = 0; k < K; ++k) pcs += "\tpc" + std::to_string(k + 1);
+  eigenvalues = "component\teigenvalue\tfraction\n";
+  for (size_t k = 0; k < K; ++k)
+    eigenvalues += std::to_string(k + 1) + '\t' + fixed(eigenvalue[k]) + '\t' + fixed(total_var == 0.0 ? 0.0 : eigenvalue[k] / total_var) + '\n';
+  projection = "sample" + pcs + '\n';
+  for (size_t s = 0; s < S; ++s) {
+    projection += names[s];
+    for (size_t k = 0; k < K; ++k) { projection += '\t'; projection += fixed(proj[s * K + k]); }
+    projection += '\n';
+  }
+  edges = "edge_num" + pcs + '\n';
+  for (size_t b = 0; b < B; ++b) {   // edge_num is the branch id, as in the mass tables
+    edges += std::to_string(b);
+    for (size_t k = 0; k < K; ++k) { edges += '\t'; edges += fixed(edge_vec[k * B + b]); }
+    edges += '\n';
+  }
+}
+
 Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, const std::vector<std::string>& names,
-                    const std::string& outdir, const Options& options, bool masses, bool squash, int device) {
+                    const std::string& outdir, const Options& options, bool masses, bool squash, int device, unsigned int epca) {
   using clk = std::chrono::steady_clock;
   // ---- everything that can be refused without a device
   if (tree.mapper())
@@ -156,6 +186,14 @@ Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, con
     check(epa_dev_krd(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)S, krd.data(),
                       masses ? edge.data() : nullptr, masses ? clade.data() : nullptr));
   }
+  std::vector<double> pc_eig, pc_vec, pc_proj;
+  double pc_total = 0.0;
+  uint32_t pc_sweeps = 0;
+  if (epca) {   // a call of its own beside the one above, which it does not touch
+    pc_eig.resize(epca); pc_vec.resize((size_t)epca * B); pc_proj.resize(S * epca);
+    check(epa_dev_epca(dev.ctx(), pairs.data(), distal.data(), weight.data(), pairs.size(), (uint32_t)S, epca, pc_eig.data(),
+                       pc_vec.data(), pc_proj.data(), &pc_total, &pc_sweeps, nullptr, nullptr));
+  }
   st.seconds_place = std::chrono::duration<double>(clk::now() - ts).count();
   std::cout << "Kantorovich-Rubinstein distances between " << S << " samples (" << st.pairs << " placements)." << std::endl;
 
@@ -175,6 +213,14 @@ Run_Stats krd_files(const Tree& tree, const std::vector<std::string>& files, con
     write_text(dir + "squash.tsv", table);
     write_text(dir + "squash.newick", newick);
     std::cout << "Squash clustering: " << S - 1 << " merges." << std::endl;
+  }
+  if (epca) {
+    std::string eigenvalues, projection, edges;
+    epca_texts(names, epca, B, pc_eig.data(), pc_total, pc_vec.data(), pc_proj.data(), options.precision, eigenvalues, projection, edges);
+    write_text(dir + "epca_eigenvalues.tsv", eigenvalues);
+    write_text(dir + "epca_projection.tsv", projection);
+    write_text(dir + "epca_edges.tsv", edges);
+    std::cout << "Edge PCA: " << epca << " components (" << pc_sweeps << " Jacobi sweeps)." << std::endl;
   }
   st.seconds_write = std::chrono::duration<double>(clk::now() - ts).count();
   st.seconds_loop = std::chrono::duration<double>(clk::now() - t_loop).count();

@@ -81,6 +81,14 @@ static void usage() {
       "                        cluster of step k) and squash.newick (the cluster tree: inner nodes cluster<k> at height distance / 2,\n"
       "                        branch = height(parent) - height(child), negative where the distances invert) beside krd.tsv.\n"
       "                        Two files at least; sample names with ( ) , : ; [ ] ' or white space are refused\n"
+      "  --epca K              with --krd: edge principal components of the samples (Matsen & Evans; `guppy epca`, `gappa analyze\n"
+      "                        edgepca`): per sample and inner edge the mass on the edge's child side minus the mass on its root\n"
+      "                        side (edges next to a leaf are left out), centred over the samples; the first K principal\n"
+      "                        components.  Writes epca_eigenvalues.tsv (component<TAB>eigenvalue<TAB>fraction of the total\n"
+      "                        variance), epca_projection.tsv (sample<TAB>pc1..pcK: the samples on those axes) and epca_edges.tsv\n"
+      "                        (edge_num<TAB>pc1..pcK: the unit-length axes, zeros on left-out edges; the entry of largest\n"
+      "                        magnitude is positive, and an edge's sign follows the rooting at the first branch) beside krd.tsv.\n"
+      "                        2 .. 1024 files, K in 1 .. files - 1; combines with --squash and --krd-masses\n"
       "  --precision N         output digits (default 10)\n"
       "  --chunk-size N        queries per chunk (default 50000; EPA-ng's CPU default is 5000)\n"
       "  --device-min-chunk N  a device chunk holds at least N queries whatever --chunk-size says\n"
@@ -122,7 +130,8 @@ int main(int argc, char** argv) {
   int device = 0;
   bool dedup = false;   // --dedup: the loop of place_dedup.cpp
   std::string krd_list;   // --krd: comma-separated jplace files, one sample each (krd_samples.cpp)
-  bool krd_given = false, krd_masses = false, krd_squash = false;
+  bool krd_given = false, krd_masses = false, krd_squash = false, epca_given = false;
+  std::string epca_arg;   // --epca K: edge principal components of the samples of --krd
   bool device_given = false, rell_given = false, prior_given = false, nodes_given = false, rank_given = false;
   std::string diag_flag;   // --host-heuristic / --device-min-chunk: steer the coded chunk loop only
   std::vector<int> devices;
@@ -170,6 +179,7 @@ int main(int argc, char** argv) {
     else if (a == "--krd") { krd_list = need(i); krd_given = true; }
     else if (a == "--krd-masses") krd_masses = true;
     else if (a == "--squash") krd_squash = true;
+    else if (a == "--epca") { epca_arg = need(i); epca_given = true; }
     else if (a == "--prior-mean") {
       const std::string v = need(i);
       char* end = nullptr;
@@ -245,6 +255,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> krd_files_list, krd_names;
   if (krd_masses && !krd_given) { std::cerr << "--krd-masses adds the mass tables to the output of --krd and needs it: --krd A.jplace,B.jplace --krd-masses\n"; return 1; }
   if (krd_squash && !krd_given) { std::cerr << "--squash clusters the samples of --krd and needs it: --krd A.jplace,B.jplace,C.jplace --squash\n"; return 1; }
+  if (epca_given && !krd_given) { std::cerr << "--epca finds the principal components of the samples of --krd and needs it: --krd A.jplace,B.jplace,C.jplace --epca 2\n"; return 1; }
   if (krd_given) {
     const char* const what = "--krd (distances between placement samples) ";
     if (!query_file.empty()) { std::cerr << what << "reads placements, not sequences: -q is not supported with it\n"; return 1; }
@@ -292,6 +303,21 @@ int main(int argc, char** argv) {
                   << "space and would need quoting in squash.newick: rename the file\n";
         return 1;
       }
+  }
+  unsigned int epca_k = 0;
+  if (epca_given) {
+    const size_t files = krd_files_list.size();
+    if (files < 2 || files > 1024) {
+      std::cerr << "--epca: principal components take 2 .. 1024 samples (" << files << " given)\n";
+      return 1;
+    }
+    char* end = nullptr;
+    const long long k = std::strtoll(epca_arg.c_str(), &end, 10);
+    if (epca_arg.empty() || *end || k < 1 || k > (long long)files - 1) {
+      std::cerr << "--epca " << epca_arg << ": " << files << " samples have 1 .. " << files - 1 << " components\n";
+      return 1;
+    }
+    epca_k = (unsigned int)k;
   }
   if (tree_file.empty() || ref_file.empty() || (query_file.empty() && !krd_given)) { usage(); return 1; }
   // the reference's CLI checks (src/main.cpp:165-218, 368-370)
@@ -428,7 +454,7 @@ int main(int argc, char** argv) {
     if (devices.empty()) devices.push_back(device);
     const bool rank_mode = world > 1 || !comm_file.empty();   // a 1-rank communicator is legal (tests, 1-GPU nodes)
     const Run_Stats st = krd_given
-        ? krd_files(tree, krd_files_list, krd_names, outdir, opt, krd_masses, krd_squash, devices[0])
+        ? krd_files(tree, krd_files_list, krd_names, outdir, opt, krd_masses, krd_squash, devices[0], epca_k)
         : fastq
         ? place_profile_file(tree, query_file, qry_info, outdir, opt, invocation, devices[0])
         : dedup

@@ -1,6 +1,6 @@
-// What krd.hip (epa_dev_krd) and squash.hip (epa_dev_squash) share: the kernels that bring a call's entries into sorted
-// points, run starts, M and P, the pair pass with its fixed-shape reduction, and the host code that validates a call,
-// lays out its scratch and queues those kernels.  Everything sits in an unnamed namespace: each of the two translation
+// What krd.hip (epa_dev_krd), squash.hip (epa_dev_squash) and epca.hip (epa_dev_epca, the table phase only) share:
+// the kernels that bring a call's entries into sorted points, run starts, M and P, the pair pass with its fixed-shape reduction, and the host code that validates a call,
+// lays out its scratch and queues those kernels.  Everything sits in an unnamed namespace: each of the translation
 // units compiles its own copy, with contraction off, from this one text -- which is what makes a distance of
 // epa_dev_squash the bits epa_dev_krd returns for the same two entry sequences.
 #pragma once
@@ -229,7 +229,7 @@ namespace {
 
 // ---- the host side of a call: validation, scratch layout, launches
 
-// the checks of epa_dev_krd that need no device, worded for `who` ("krd" / "squash"); out: what the caller's last
+// the checks of epa_dev_krd that need no device, worded for `who` ("krd" / "squash" / "epca"); out: what the caller's last
 // argument check is (a null output)
 int krd_validate(epa_ctx* ctx, const std::string& who, const epa_pair* pairs, const double* distal, const double* weight, uint64_t n,
                  uint32_t S) {
@@ -315,16 +315,19 @@ void krd_layout(Carver& c, KrdLay& l, const KrdShape& sh) {
 }
 
 // status words cleared, the matrix zeroed, points, sorts, tables and the full pair pass into d_krd, queued on the
-// context's stream; sub_timers: "krd_sort", "krd_tables" and "krd_pairs" are recorded
+// context's stream; sub_timers: "krd_sort", "krd_tables" and "krd_pairs" are recorded.  pair_pass false (epa_dev_epca):
+// the table phase alone -- points, the two sorts, the gather, rank-ordered lengths and sizes, run starts, M and P --
+// and d_krd is not touched
 int krd_launch(epa_ctx* ctx, const KrdLay& ly, const KrdShape& sh, const epa_pair* d_pairs, const double* d_distal,
-               const double* d_weight, double* d_krd, bool sub_timers) {
+               const double* d_weight, double* d_krd, bool sub_timers, bool pair_pass = true) {
   const EpaTopology& tp = *ctx->topo;
   const uint32_t n32 = sh.n32, B = sh.B, S = sh.S, n_tiles = sh.n_tiles;
   const size_t SB = (size_t)S * B;
   const dim3 ngrid((n32 + 255) / 256), bgrid((B + 255) / 256), blk(256);
   size_t sort_x = sh.sort_x, sort_k = sh.sort_k;   // rocPRIM takes the size by reference
   EPA_HIP(ctx, hipMemsetAsync(ly.status, 0, sizeof(uint32_t) * ST_WORDS, ctx->stream));
-  EPA_HIP(ctx, hipMemsetAsync(d_krd, 0, sizeof(double) * (size_t)S * S, ctx->stream));   // the diagonal, and everything when S == 1
+  if (pair_pass)
+    EPA_HIP(ctx, hipMemsetAsync(d_krd, 0, sizeof(double) * (size_t)S * S, ctx->stream));   // the diagonal, and everything when S == 1
   if (sub_timers) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_KRD_SORT));
   if (n32) {
     hipLaunchKernelGGL(k_krd_points, ngrid, blk, 0, ctx->stream, tp.cinfo, tp.rank, d_pairs, d_distal, ctx->blen, n32, B, S, ly.key,
@@ -343,6 +346,7 @@ int krd_launch(epa_ctx* ctx, const KrdLay& ly, const KrdShape& sh, const epa_pai
                      ly.M);
   hipLaunchKernelGGL(k_krd_scan, dim3(S), blk, 0, ctx->stream, ly.P, B);
   if (sub_timers) epa_timer_stop(ctx, epa_t(ctx, epa_ctx::T_KRD_TABLES));
+  if (!pair_pass) return EPA_OK;
   if (sub_timers) epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_KRD_PAIRS));
   for (unsigned long long q0 = 0; q0 < sh.n_pairs; q0 += sh.per_launch) {
     const uint32_t np = (uint32_t)std::min<unsigned long long>(sh.per_launch, sh.n_pairs - q0);

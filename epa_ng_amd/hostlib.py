@@ -335,6 +335,31 @@ def squash_texts(names, merge_a, merge_b, merge_dist, merge_size, precision=10):
     raise RuntimeError("squash_texts: the texts did not fit")
 
 
+def epca_texts(names, eigenvalue, total_var, edge_vec, proj, precision=10):
+    """the writer of epa-ng-amd --epca: sample names and the outputs of Evaluator.epca (eigenvalue [K], total_var,
+    edge_vec [K][B], proj [S][K]) -> (text of epca_eigenvalues.tsv, of epca_projection.tsv, of epca_edges.tsv).  Needs no
+    device."""
+    lib = host_lib()
+    szp = C.POINTER(C.c_size_t)
+    lib.epa_host_epca_texts.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_double,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint, C.c_char_p, C.c_char_p, C.c_char_p, szp]
+    ev, vec, pr = (np.ascontiguousarray(v, np.float64) for v in (eigenvalue, edge_vec, proj))
+    K = len(ev)
+    if vec.ndim != 2 or vec.shape[0] != K or pr.shape != (len(names), K):
+        raise ValueError("epca_texts: %d components need edge_vec [%d][B] and proj [%d][%d]" % (K, K, len(names), K))
+    total = float(np.ravel(total_var)[0])
+    cap = (C.c_size_t * 3)(1 << 16, 1 << 16, 1 << 16)
+    for _ in range(2):
+        bufs = [C.create_string_buffer(c) for c in cap]
+        rc = lib.epa_host_epca_texts(_strs(names), len(names), K, vec.shape[1], _dp(ev), total, _dp(vec), _dp(pr), int(precision),
+                                     bufs[0], bufs[1], bufs[2], cap)
+        if rc < 0:
+            raise RuntimeError(lib.epa_host_last_error().decode())
+        if rc == 0:
+            return tuple(b.value.decode() for b in bufs)
+    raise RuntimeError("epca_texts: the texts did not fit")
+
+
 def heuristic(lnl, mode="dynamic", thresh=0.99999):
     lnl = np.ascontiguousarray(lnl, np.float64)
     Q, B = lnl.shape

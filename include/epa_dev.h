@@ -883,6 +883,77 @@ int epa_dev_squash(epa_ctx* ctx, const epa_pair* pairs, const double* distal, co
                    uint32_t* merge_size /* [S-1] */, double* krd /* [S][S] or NULL */);
 
 /*
+ * Edge principal components of the S samples (Matsen and Evans 2013; `guppy epca`, `gappa analyze edgepca`): which edges
+ * of the reference tree carry the differences between the samples, and where each sample sits on those axes.  The inputs
+ * are epa_dev_krd's; root, child(b), rank(b), size(b), M_s, P_s and T_s(b) = P_s[rank + size - 1] - P_s[rank] are those of
+ * its description above, computed by its kernels.
+ *   W_s            the sample's total, P_s[B - 1]: the scan's last value, not summed again
+ *   excluded       branch b with size(b) == 1 (a leaf at the child end) or size(b) == B (a leaf at the root end).  The edge
+ *                  next to a leaf has the imbalance +-(W - own mass) and carries no signal (guppy and gappa leave such
+ *                  edges out by default): its column is defined as 0.0
+ *   X[s][b]        of a kept edge: T_s(b) - ((W_s - T_s(b)) - M_s[rank b]), the mass strictly on the child side minus the
+ *                  mass strictly on the root side; the edge's own mass counts for neither.  Three fp64 subtractions in
+ *                  this order.  The sign depends on the root (node_prox[0]): flipping an edge's orientation flips that
+ *                  edge's entry in every eigenvector and nothing else
+ *   mean[b]        (0.0 + X[0][b] + ... + X[S-1][b]) / S, added in ascending s, then one division
+ *   Xc[s][b]       X[s][b] - mean[b].  Given X, a restatement reaches Xc bit for bit.  There is no column filter (a
+ *                  constant column centres to about 0 and contributes nothing) and no kappa transform
+ *   G              Xc Xc^T, [S][S]; the order of the B additions is the kernel's structure and no more.  G replaces the
+ *                  B x B covariance matrix (34 GB at 65 537 branches); the two share their non-zero spectrum
+ *   eigen-decomposition of G: cyclic two-sided Jacobi in the parallel (round-robin) ordering.  Index set 0 .. m - 1, m = S
+ *                  rounded up to even; m - 1 is a dummy when S is odd.  Step t of a sweep pairs positions i and m - 1 - i of
+ *                  the circle method's list, which is turned between steps as [idx0, idx_last, idx1 .. idx_{m-2}]: m - 1
+ *                  steps per sweep.  Pair (p < q) is rotated iff |a_pq| > 2^-53 max_i |a_ii|, the maximum taken at the
+ *                  start of the sweep; theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1))
+ *                  with sign(0) = +1, c = 1 / sqrt(t^2 + 1), s = t c.  The loop ends after the first sweep without a
+ *                  rotation or after EPCA_MAX_SWEEPS = 30.  (Centring makes G singular: a threshold relative to
+ *                  sqrt(a_pp a_qq) does not terminate.)
+ *   sweeps         the number of sweeps run, the rotation-free last one included.  Reaching 30 is not an error: the
+ *                  results are then what 30 sweeps left
+ *   lambda'        the Gram eigenvalues (the diagonal after the loop) sorted descending, equal values by ascending Jacobi
+ *                  column; u_k the matching column of the accumulated rotations
+ *   eigenvalue[k]  max(lambda'_k, 0) / (S - 1): the eigenvalue of the sample covariance Xc^T Xc / (S - 1)
+ *   edge_vec[k][b] sigma_k (sum over s of Xc[s][b] u_k[s]) / sqrt(lambda'_k), added in ascending s: unit length, 0.0 on
+ *                  excluded edges
+ *   proj[s][k]     sigma_k sqrt(lambda'_k) u_k[s], which equals Xc v_k up to rounding
+ *   sigma_k        +-1 such that the entry of edge_vec[k] with the largest |value| is positive; on equal |value| the
+ *                  lowest branch id decides
+ *   null component lambda'_k <= 2^-40 lambda'_0, or lambda'_0 <= 0: the eigenvalue is reported as above, edge_vec[k] and
+ *                  proj[.][k] are all 0.0 (a tree with one inner edge, K beyond the rank, no inner edge at all)
+ *   total_var      (sum over i of G[i][i]) / (S - 1), added one after the other from the diagonal as first computed: the
+ *                  trace of the covariance, for "fraction of variance"
+ *   imbalance      when given: X[s][b] by branch id (not centred);  gram, when given: G
+ * The same call returns the same bits every time: no floating-point atomics (the only atomic is the integer count of a
+ * sweep's rotations), all tile shapes and the slice length are compile-time constants, nothing depends on the grid.  gram
+ * is bit-symmetric: an element is computed once and stored twice, before and during the rotations.
+ * Every array may be a host or a device pointer.  Validation and its wording (led by "epca:") are epa_dev_krd's, except
+ * that S must be 2 .. 1024 (EPCA_MAX_S; the refusal names the count) and K 1 .. S - 1.  A refused call changes nothing on
+ * the context.  n == 0 and samples without entries are legal: their rows of X are zero.  Above 1024 samples the unblocked
+ * Jacobi below would re-read a 128 MiB matrix 4095 times per sweep; a blocked solver for that range is not part of this
+ * library.
+ * Structure (epca.hip).  The table phase of epa_dev_krd (points, two sorts, M, P).  One work item per (branch, sample)
+ * writes X edge-major, XT[rank][sample] with the pitch S rounded up to 16, excluded ranks and pad columns 0.0; one work
+ * item per rank centres its row.  G: one wave per (pair of 16-sample tiles I <= J, slice of 1024 ranks) accumulates
+ * v_mfma_f64_16x16x4_f64 over the slice, four ranks per instruction, into one partial tile; a second kernel adds a tile
+ * pair's partials in slice order and stores [a][b] and [b][a].  Jacobi: the host drives, the matrix A and the rotations'
+ * product V stay on the device; per step one kernel forms (c, s, t) of the step's pairs (the identity where the threshold
+ * skips a pair or the dummy is involved) and counts them, and one kernel with a work item per (pair i <= pair j) forms
+ * J_i^T . block . J_j of its 2 x 2 block and stores the block and its mirror image -- item (i, i) writes a_pq = a_qp = 0.0,
+ * a_pp - t a_pq and a_qq + t a_pq -- and rotates columns p_i, q_i of V; in place, as the blocks of a step are disjoint.
+ * One 4-byte read-back of the rotation count per sweep.  The sort of the eigenvalues runs on the host from one read-back
+ * of the diagonal.  At S of a few hundred the Jacobi loop's 2 (S - 1) small launches per sweep dominate the call.
+ * Scratch (its own bank): 8 B (S up to 16) (XT) + 16 m^2 (A and V) + 4 m^2 (the steps' pairs) + at most 64 MiB of Gram
+ * partials + 8 K B + 8 S K, 8 S^2 and 8 S B more for gram and imbalance when asked, + epa_dev_krd's scratch with M.
+ * Timers: "epca" (the whole call on the device's time line, the host's read-backs included), inside it "epca_tables"
+ * (points, sorts, M, P, X, centring), "epca_gram", "epca_eig" (the sweeps' kernels, summed over the sweeps) and
+ * "epca_project" (edge vectors, signs, projections); "epca_loop_wall" is the host's wall clock around the Jacobi loop (no
+ * event pair).
+ */
+int epa_dev_epca(epa_ctx* ctx, const epa_pair* pairs, const double* distal, const double* weight, uint64_t n, uint32_t S, uint32_t K,
+                 double* eigenvalue /* [K] */, double* edge_vec /* [K][B] */, double* proj /* [S][K] */, double* total_var /* [1] */,
+                 uint32_t* sweeps /* [1] */, double* imbalance /* [S][B] by branch id, or NULL */, double* gram /* [S][S] or NULL */);
+
+/*
  * Replaces apply_heuristic() for the default dynamic heuristic (src/core/heuristics.hpp:119-127,
  * until_accumulated_reached src/set_manipulators.cpp:90-114) on device, so the Q x B table never
  * leaves HBM: per query, branches in descending LWR order until the accumulated LWR reaches
@@ -1160,7 +1231,7 @@ int epa_dev_xcd_shares(const epa_ctx* ctx, double shares[8]);
 double epa_dev_last_sclk_mhz(const epa_ctx* ctx);
 
 /* duration in milliseconds of the last launch of the named kernel family on ctx's stream,
- * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl", "krd", "krd_sort", "krd_tables", "krd_pairs", "squash", "squash_init", "squash_argmin", "squash_merge", "squash_row", "squash_loop_wall"); < 0 if never run.
+ * measured with HIP events ("preplace", "thorough", "lookup", "select", "score_at", "site_lnl", "rell", "marginal", "rell_tests", "rell_au", "rell_kh", "preplace_profile", "dedup", "edpl", "krd", "krd_sort", "krd_tables", "krd_pairs", "squash", "squash_init", "squash_argmin", "squash_merge", "squash_row", "squash_loop_wall", "epca", "epca_tables", "epca_gram", "epca_eig", "epca_project", "epca_loop_wall"); < 0 if never run.
  * Blocked lookup layout: "lookup_block" = the table builds of the last chunk body, summed over its
  * blocks; "preplace" = its preplacement kernels, summed likewise (the builds are not part of it). */
 double epa_dev_last_kernel_ms(const epa_ctx* ctx, const char* which);
