@@ -113,6 +113,8 @@ def dev_lib():
                                                C.c_void_p, C.c_void_p]
         L.epa_dev_preplace_screen_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                     C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.epa_dev_preplace_screen16_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                      C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.epa_dev_preplace_screen_runs.argtypes = [C.c_void_p]
         L.epa_dev_preplace_screen_runs.restype = C.c_uint64
         L.epa_dev_thorough.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -535,6 +537,25 @@ class Evaluator:
         return {"ran": bool(info[0]), "delta": float(info[1]), "included": int(info[2]), "M": float(info[3]),
                 "nonfinite": int(info[4]), "band_t": float(info[5]), "ms_screen": float(info[6]),
                 "ms_band": float(info[7]), "seg32": seg32, "mask": mask}
+
+    def preplace_screen16_probe(self, codes, win_begin, win_span, max_span, threshold=0.99999):
+        """internal: the 16-bit four-branch screen of the pair preplacement and its band test, alone
+        (epa_dev_preplace_screen16_probe) -> dict: ran, delta, included (cells), h, unscreenable (reads), band_t,
+        ms_screen, ms_band, seg16 int32 [Q][nseg] (relative maxima in units of h, -32768 = the floor), cq float64 [Q]
+        and mask uint64 [Q]: cq + h seg16 + delta >= a segment's exact maximum"""
+        Q = len(win_begin)
+        nseg = (self.B + 63) // 64
+        seg16 = np.full((Q, nseg), np.iinfo(np.int32).min, np.int32)
+        cq = np.zeros(Q, np.float64)
+        mask = np.zeros(Q, np.uint64)
+        info = np.zeros(8, np.float64)
+        self._layout(codes)
+        self._check(self.L.epa_dev_preplace_screen16_probe(self.h, _ptr(codes), _ptr(win_begin), _ptr(win_span), Q,
+                                                           int(max_span), float(threshold), _ptr(seg16), _ptr(cq),
+                                                           _ptr(mask), _ptr(info)))
+        return {"ran": bool(info[0]), "delta": float(info[1]), "included": int(info[2]), "h": float(info[3]),
+                "unscreenable": int(info[4]), "band_t": float(info[5]), "ms_screen": float(info[6]),
+                "ms_band": float(info[7]), "seg16": seg16, "cq": cq, "mask": mask}
 
     def thorough(self, pairs, codes, win_begin, win_span, Q=None, n_pairs=None, out=None):
         """pairs: structured PAIR_DTYPE array (or device buffer) -> RESULT_DTYPE array."""

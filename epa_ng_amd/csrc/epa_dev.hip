@@ -655,7 +655,8 @@ extern "C" int epa_dev_set_option(epa_ctx* ctx, const char* key, int value) {
       {"queued_thorough", &EpaOptions::queued_thorough},   {"xcd_balance", &EpaOptions::xcd_balance},
       {"aa_valu", &EpaOptions::aa_valu},                   {"timers", &EpaOptions::timers},
       {"newton_lds", &EpaOptions::newton_lds},             {"tip_distal", &EpaOptions::tip_distal},
-      {"preplace_screen", &EpaOptions::preplace_screen},   {"preplace_screen_scale", &EpaOptions::preplace_screen_scale}};
+      {"preplace_screen", &EpaOptions::preplace_screen},   {"preplace_screen_scale", &EpaOptions::preplace_screen_scale},
+      {"preplace_screen_i16", &EpaOptions::preplace_screen_i16}, {"preplace_screen_i16_shift", &EpaOptions::preplace_screen_i16_shift}};
   for (const Entry& e : table)
     if (strcmp(key, e.name) == 0) {
       ctx->opt.*e.field = value;
@@ -747,6 +748,8 @@ extern "C" void epa_dev_destroy(epa_ctx* ctx) {
   if (ctx->lookup) (void)hipFree(ctx->lookup);
   if (ctx->lookup2) (void)hipFree(ctx->lookup2);
   if (ctx->lookup2f) (void)hipFree(ctx->lookup2f);
+  if (ctx->lookup2q) (void)hipFree(ctx->lookup2q);
+  if (ctx->base2) (void)hipFree(ctx->base2);
   if (ctx->prof_tab) (void)hipFree(ctx->prof_tab);
   epa_topology_free(ctx);
   for (void* p : ctx->blk_buf) if (p) (void)hipFree(p);
@@ -1711,6 +1714,64 @@ extern "C" int epa_dev_preplace_screen_probe(epa_ctx* ctx, const uint8_t* q_code
         seg32[(size_t)q * nseg + s] = v;
       }
   }
+  return EPA_OK;
+}
+
+extern "C" int epa_dev_preplace_screen16_probe(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
+                                               const uint32_t* win_span, uint32_t Q, uint32_t max_span, double threshold,
+                                               int32_t* seg16, double* cq, uint64_t* seg_mask, double* info) {
+  if (!ctx || !q_codes || !win_begin || !win_span || !info)
+    return epa_fail(ctx, EPA_ERR_INVALID_ARG, "null argument");
+  for (int i = 0; i < 8; ++i) info[i] = 0.0;
+  if (Q == 0) return EPA_OK;
+  EPA_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = epa_dev_build_lookup(ctx);
+  if (rc) return rc;
+  if (max_span > ctx->W) max_span = ctx->W;
+  if (max_span && !epa_is_device_ptr(win_span))
+    for (uint32_t q = 0; q < Q; ++q)
+      if (win_span[q] > max_span) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "preplace: a window is longer than max_span");
+  const uint8_t* d_codes = epa_codes_to_device(ctx, q_codes, Q);
+  const uint32_t* d_begin = (const uint32_t*)epa_to_device(ctx, SLOT_BEGIN, win_begin, sizeof(uint32_t) * Q);
+  const uint32_t* d_span = (const uint32_t*)epa_to_device(ctx, SLOT_SPAN, win_span, sizeof(uint32_t) * Q);
+  if (!d_codes || !d_begin || !d_span) return epa_fail(ctx, EPA_ERR_HIP, "query upload failed");
+  PreScreenProbe probe;
+  probe.i16 = true;
+  probe.band_t = epa_select_band_t(threshold, ctx->B);
+  const uint32_t* d_status = nullptr;
+  rc = launch_preplace(ctx, d_codes, d_begin, d_span, Q, PreTable{}, max_span, &d_status, &probe);
+  if (rc) return rc;
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = preplace_check_status(ctx, d_status))) return rc;
+  info[0] = probe.ran ? 1.0 : 0.0;
+  info[5] = probe.band_t;
+  if (!probe.ran) return EPA_OK;
+  const uint32_t nseg = (ctx->B + 63) / 64, segp = (nseg + 7u) & ~7u;
+  unsigned long long n_incl = 0;
+  EPA_HIP(ctx, hipMemcpy(&n_incl, probe.n_incl, sizeof(n_incl), hipMemcpyDeviceToHost));
+  info[1] = probe.delta;
+  info[2] = (double)n_incl;
+  info[3] = probe.h;
+  info[6] = probe.ms_screen;
+  info[7] = probe.ms_band;
+  if (seg_mask) EPA_HIP(ctx, hipMemcpy(seg_mask, probe.mask, sizeof(uint64_t) * Q, hipMemcpyDeviceToHost));
+  if (cq) EPA_HIP(ctx, hipMemcpy(cq, probe.cq, sizeof(double) * Q, hipMemcpyDeviceToHost));
+  // keys -> integers on the host (ScreenI16::key of preplace.hip: value + 32769); a read all of whose segments sit at
+  // the floor could not be screened
+  std::vector<uint32_t> keys((size_t)Q * segp);
+  EPA_HIP(ctx, hipMemcpy(keys.data(), probe.seg32, sizeof(uint32_t) * keys.size(), hipMemcpyDeviceToHost));
+  uint64_t unscreenable = 0;
+  for (uint32_t q = 0; q < Q; ++q) {
+    bool all = true, floor_row = true;
+    for (uint32_t s = 0; s < nseg; ++s) {
+      const uint32_t k = keys[(size_t)q * segp + s];
+      if (!k) all = false;
+      else if (k > 1) floor_row = false;
+      if (seg16) seg16[(size_t)q * nseg + s] = k ? (int32_t)k - 32769 : INT32_MIN;
+    }
+    if (all && floor_row) ++unscreenable;
+  }
+  info[4] = (double)unscreenable;
   return EPA_OK;
 }
 

@@ -293,6 +293,8 @@ struct EpaOptions {
   int preplace_screen = 1;    // the pair path's fp32 two-branch screen where its conditions hold (preplace.hip);
                               // 2: also for chunks below its size condition (tests)
   int preplace_screen_scale = 1;   // test only: the screen's error bound delta is multiplied by this
+  int preplace_screen_i16 = 1;     // the screen in 16-bit fixed point, four branches per gather; 0: the fp32 screen
+  int preplace_screen_i16_shift = 0;   // test only: the 16-bit quantum h is made smaller by this many powers of two
   int dedup_sort_bits = 32;   // low key bits the dedup sort looks at: rows equal there share a run, the full key and the codes part them
 };
 
@@ -339,6 +341,14 @@ struct epa_ctx {
   // (k_build_lookup2f; null until launch_build_lookup2f), the largest finite |entry| and the number of non-finite ones
   float2* lookup2f = nullptr;
   bool lookup2f_refused = false;   // no memory for it: the one-pass preplacement stays
+  // the 16-bit screen's tables (k_build_base2 / k_build_lookup2q; null until launch_build_lookup2q): base2
+  // [2][ceil(W/2)][36] = the maximum over the branches of lookup2's entry, lookup2q [ceil(B/4)][2][ceil(W/2)][36] x 4
+  // int16 = the entries of branches 4p .. 4p + 3 below base2 in units of lookup2q_h
+  double* base2 = nullptr;
+  void* lookup2q = nullptr;
+  double lookup2q_h = 0.0;
+  bool lookup2q_refused = false;   // no memory for them: the fp32 screen stays
+  bool screen_stats = false;       // screen_M / screen_nonfinite are set (by either table build)
   uint64_t screen_runs = 0;        // preplacements that took the two-pass route (epa_dev_preplace_screen_runs)
   double screen_M = 0.0;
   uint64_t screen_nonfinite = 0;
@@ -625,13 +635,25 @@ int launch_build_lookup2f(epa_ctx* ctx);
 // <= M, |fp32 sum - fp64 sum| <= (n + 1) u n M (every entry rounded once, n - 1 additions); delta is twice that, times
 // the option preplace_screen_scale.  < 0: no screen for this context (a non-finite entry, or delta > 1).
 double epa_screen_delta(const epa_ctx* ctx, uint32_t span_bound);
+// The 16-bit screen's quantum and error bound for windows of at most span_bound sites, n gathered entries: every entry
+// is rounded to a multiple of h once (<= h / 2 each, integer addition is exact), C_q is a sum of n fp64 terms of
+// magnitude <= M and C_q + h seg one more fp64 operation: delta = n h / 2 + (n + 2) n M 2^-53.  *h = the largest power of
+// two that keeps this <= 1, made smaller by the option preplace_screen_i16_shift; the returned delta is for that *h and
+// multiplied by preplace_screen_scale.  < 0: no 16-bit screen (no statistics, a non-finite entry, or delta > 1).
+double epa_screen16_delta(const epa_ctx* ctx, uint32_t span_bound, double* h);
+// base2 (once, with the table statistics: synchronises the stream) and lookup2q for the quantum h (again whenever h
+// changes: a power of two, so only when the chunks' longest window moves across a few fixed lengths)
+int launch_build_lookup2q(epa_ctx* ctx, uint32_t span_bound);
 // what a screen-only run of launch_preplace leaves behind (device pointers into SLOT_PREPLACE, valid until the bank's
 // next preplacement): the tests' and the measurements' view of the screen
 struct PreScreenProbe {
   double band_t = 0.0;                   // in: the selection's band (launch_select_begin)
   bool ran = false;                      // the screen's conditions held
+  bool i16 = false;                      // in: probe the 16-bit screen (else the fp32 screen, whatever the option says)
   double delta = 0.0;
-  const uint32_t* seg32 = nullptr;       // [Q][segp] seg_key32 of the fp32 segment maxima, 0 = none
+  double h = 0.0;                        // 16-bit screen: the quantum
+  const double* cq = nullptr;            // 16-bit screen: [Q] C_q
+  const uint32_t* seg32 = nullptr;       // [Q][segp] keys of the segment maxima (seg_key32, or integer + 32769), 0 = none
   const unsigned long long* mask = nullptr;    // [Q] included segments
   const unsigned long long* n_incl = nullptr;  // their total
   float ms_screen = -1.f, ms_band = -1.f;
@@ -645,7 +667,8 @@ int launch_build_lookup_block(epa_ctx* ctx, uint32_t b0, uint32_t nb, double* bl
 int launch_build_lookup2_block(epa_ctx* ctx, uint32_t nb, const double* blk_lookup, double* blk_lookup2);
 // fills t.lnl (and, after clearing them, t.segmax when given); *d_status: the call's status words in SLOT_PREPLACE,
 // [0 .. 4) the window validation -- for preplace_check_status after a synchronisation, or for the selection's read-back
-// probe: run the fp32 screen and its band test INSTEAD of the table kernels and report them (t.lnl is not written)
+// probe: run the screen it names (fp32, or 16 bit with probe->i16) and its band test INSTEAD of the table kernels and report
+// them (t.lnl is not written)
 int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begin, const uint32_t* d_span, uint32_t Q,
                     const PreTable& t, uint32_t max_span, const uint32_t** d_status, PreScreenProbe* probe = nullptr);
 int preplace_check_status(epa_ctx* ctx, const uint32_t* d_status);

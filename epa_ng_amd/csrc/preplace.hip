@@ -31,6 +31,7 @@
 #include "epa_dev_internal.hpp"
 #include "wave_util.hpp"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -1009,19 +1010,127 @@ __global__ void __launch_bounds__(256) k_build_lookup2f(const double* __restrict
   }
 }
 
+// ---- 16-bit screen ("16-bit screen").  The band test only compares sums of ONE read across branches, so
+// every table entry may be shifted by a constant of its slot: base2[i] = the maximum over the real branches of lookup2's
+// entry i, i over [parity][pair row][PE].  Relative entries are <= 0, a read's sums all lose the same C_q = sum of base2
+// over its slots, and its best branches sum to a small negative number: 16-bit fixed point with quantum h holds them.
+// lookup2q has, per QUAD of branches (4p .. 4p + 3) and in lookup2's own layout, four int16 per 8-byte entry --
+// max(rint((entry - base2) / h), -32768) -- so the packed offsets, the staged slice and the groups stay those of
+// k_preplace_pairs, and one ds_read_b64 + two packed saturating adds serve FOUR (query, branch) cells.
+typedef short s4 __attribute__((ext_vector_type(4)));
+constexpr int Q16_FLOOR = -32768;
+
+// base2 and the table statistics in one pass over lookup2: thread = entry, loop over the branches.  stats as in
+// k_build_lookup2f (the largest |entry| and the non-finite count of the entries rounded to fp32, so that either build
+// leaves the same numbers in the context).  Rows past the alignment hold zeros.
+__global__ void __launch_bounds__(256) k_build_base2(const double* __restrict__ lookup2, uint32_t W, uint32_t B,
+                                                     double* __restrict__ base2, uint32_t* __restrict__ stats) {
+  const uint32_t Wh = (W + 1) / 2, n = 2 * Wh * PE;
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  float amax = 0.f;
+  uint32_t bad = 0;
+  if (i < n) {
+    const uint32_t par = i / (Wh * PE), rem = i - par * Wh * PE, r = rem / PE;
+    double m = 0.0;
+    if (2 * r + par < W) {
+      m = -INFINITY;
+#pragma unroll 8
+      for (uint32_t b = 0; b < B; ++b) {
+        const double v = lookup2[(size_t)b * n + i];
+        const float x = (float)v;
+        if (isfinite(x)) amax = fmaxf(amax, fabsf(x)); else ++bad;
+        m = fmax(m, v);
+      }
+    }
+    base2[i] = m;
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    amax = fmaxf(amax, __shfl_xor(amax, off));
+    bad += (uint32_t)__shfl_xor((int)bad, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (amax > 0.f) atomicMax(&stats[0], __float_as_uint(amax));
+    if (bad) atomicAdd(&stats[1], bad);
+  }
+}
+
+// lookup2q[p][i] = the four branches 4p .. 4p + 3 of entry i in units of h below base2[i].  h is a power of two: the
+// division is exact, the only rounding is rint's (<= h / 2 per entry) and the clamp, which only raises an entry.  Phantom
+// branches of the last quad hold the floor everywhere but the exact-zero (none, none) slot: their sums saturate.
+__global__ void __launch_bounds__(256) k_build_lookup2q(const double* __restrict__ lookup2, const double* __restrict__ base2,
+                                                        uint32_t W, uint32_t B, double inv_h, s4* __restrict__ lookup2q,
+                                                        uint32_t p0) {
+  const uint32_t p = p0 + blockIdx.y, Wh = (W + 1) / 2, n = 2 * Wh * PE;
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t par = i / (Wh * PE), rem = i - par * Wh * PE, r = rem / PE, e = rem - r * PE;
+  s4 out = {0, 0, 0, 0};
+  if (2 * r + par < W) {
+    const double bs = base2[i];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      const uint32_t b = 4 * p + k;
+      double qv = e == PE - 1 ? 0.0 : (double)Q16_FLOOR;
+      if (b < B) {
+        const double d = rint((lookup2[(size_t)b * n + i] - bs) * inv_h);
+        qv = d >= (double)Q16_FLOOR ? fmin(d, 0.0) : (double)Q16_FLOOR;   // (a NaN lands on the floor)
+      }
+      out[k] = (short)(int)qv;
+    }
+  }
+  lookup2q[(size_t)p * n + i] = out;
+}
+
+// The cell types of the screening kernel: what one 8-byte table entry holds and how its sums are formed and tracked.
+struct ScreenF32 {   // two branches in fp32
+  using cell = f2;
+  using run = float;                       // the running maximum of a segment
+  static constexpr uint32_t SEGC = 32;     // entries (branch pairs) per 64-branch segment
+  static constexpr bool RELATIVE = false;
+  static __device__ __forceinline__ cell zero() { return cell{0.f, 0.f}; }
+  static __device__ __forceinline__ cell add(cell a, cell b) { return a + b; }
+  static __device__ __forceinline__ run none() { return -INFINITY; }
+  static __device__ __forceinline__ run track(run m, cell s) { return fmaxf(m, fmaxf(s.x, s.y)); }
+  static __device__ __forceinline__ uint32_t key(run m) { return seg_key32(m); }
+};
+// Four branches in 16-bit fixed point, saturating adds (v_pk_add_i16 clamp), the running maximum in 16 bits too
+// (v_pk_max_i16).  Every entry is <= 0, so a partial sum never rises: a final sum above the floor was above it all the
+// way and no add clamped -- it is the exact integer sum of entries none of which was clamped either (a clamped entry IS
+// the floor and pins the sum there).  A sum at the floor stands for "at most the floor": clamps only raise.
+struct ScreenI16 {
+  using cell = s4;
+  using run = s4;
+  static constexpr uint32_t SEGC = 16;     // entries (branch quads) per 64-branch segment
+  static constexpr bool RELATIVE = true;   // sums are relative to C_q: tile 0 gathers base2
+  static __device__ __forceinline__ cell zero() { return cell{0, 0, 0, 0}; }
+  static __device__ __forceinline__ cell add(cell a, cell b) { return __builtin_elementwise_add_sat(a, b); }
+  static __device__ __forceinline__ run none() { return run{Q16_FLOOR, Q16_FLOOR, Q16_FLOOR, Q16_FLOOR}; }
+  static __device__ __forceinline__ run track(run m, cell s) { return __builtin_elementwise_max(m, s); }
+  static __device__ __forceinline__ uint32_t key(run m) {   // 1 .. 65536: order preserving, never 0
+    const int v = max(max((int)m.x, (int)m.y), max((int)m.z, (int)m.w));
+    return (uint32_t)(v - Q16_FLOOR) + 1u;
+  }
+};
+__device__ __forceinline__ int seg_val16(uint32_t k) { return (int)k - 1 + Q16_FLOOR; }
+
 // The screening pass: the item walk, slice staging, register prefetch, gather batches and priorities of
-// k_preplace_pairs<false, SPR, ROWL> over BP = ceil(B / 2) branch PAIRS, sums in fp32 in the same association, no result
-// rows: only the running maximum per query and 64-branch segment (32 pairs: a pair never straddles a segment) leaves,
-// as a seg_key32 by atomicMax into seg32 [Q][segp] (cleared by the caller).
-template <int SPR, int ROWL>
+// k_preplace_pairs<false, SPR, ROWL> over BP entries' worth of branches (CELL = ScreenF32: ceil(B / 2) pairs, ScreenI16:
+// ceil(B / 4) quads), sums in the cell type in the same association, no result rows: only the running maximum per query
+// and 64-branch segment (CELL::SEGC entries: none straddles a segment) leaves, as a non-zero order-preserving key by
+// atomicMax into seg32 [Q][segp] (cleared by the caller).  CELL::RELATIVE: the items of tile 0 first stage base2's slice
+// as one more branch, gather it in fp64 through the same offsets and store cq[query] = C_q.
+template <class CELL, int SPR, int ROWL>
 __global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
-    const float2* __restrict__ lookup2f, const uint16_t* __restrict__ packed,
+    const typename CELL::cell* __restrict__ table, const uint16_t* __restrict__ packed,
     const uint16_t* __restrict__ tails, const uint32_t* __restrict__ win_begin,
     const uint32_t* __restrict__ win_span, const uint32_t* __restrict__ perm,
     const Group* __restrict__ groups, uint32_t W, uint32_t BP, uint32_t NP16,
-    const uint32_t* __restrict__ status, uint32_t* __restrict__ seg32, uint32_t segp) {
+    const uint32_t* __restrict__ status, uint32_t* __restrict__ seg32, uint32_t segp,
+    const double* __restrict__ base2, double* __restrict__ cq) {
+  using cell = typename CELL::cell;
   constexpr int TR2 = (CH + SPR) / 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [TR2] rows of PE float2, ROWL bytes apart
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [TR2] rows of PE cells, ROWL bytes apart
   static_assert(ROWL % 16 == 0 && ROWL >= PROWB && ((TR2 - 1) * ROWL + PROWB) < 65536, "16-bit LDS offsets");
   __shared__ uint32_t s_maxspan;
   const uint32_t ng = status[5];
@@ -1064,7 +1173,7 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
       const uint16_t* tq = tails + (size_t)qi * 4;
       t0 = tq[0] + rowoff; t1 = tq[1] + rowoff; t2 = tq[2] + rowoff;
     }
-    auto at = [&](uint32_t off) -> f2 { return *reinterpret_cast<const f2*>(smem + off); };
+    auto at = [&](uint32_t off) -> cell { return *reinterpret_cast<const cell*>(smem + off); };
     uint32_t cw[PW];
     if (mine) {
       const uint4* p = reinterpret_cast<const uint4*>(packed + (size_t)qi * NP16);
@@ -1085,15 +1194,18 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
     const uint32_t rows = (row0 < W) ? min(need, (W - row0 + 1) / 2) : 0;
     const uint32_t n2 = rows * (PE / 2);
     constexpr int PF = (TR2 * (PE / 2) + GQ2 - 1) / GQ2;
-    auto request = [&](uint32_t j, float4 (&pfs)[PF]) {
-      const float4* src = reinterpret_cast<const float4*>(
-          lookup2f + (((size_t)(b0 + j) * 2 + (row0 & 1u)) * ((W + 1) / 2) + (row0 >> 1)) * PE);
+    const size_t slice0 = ((size_t)(row0 & 1u) * ((W + 1) / 2) + (row0 >> 1)) * PE;   // the slice inside one branch's rows
+    auto request_at = [&](const void* first, float4 (&pfs)[PF]) {   // first: entry slice0 of a [2][ceil(W / 2)][PE] table of 8-byte entries
+      const float4* src = reinterpret_cast<const float4*>(first);
 #pragma unroll
       for (int u = 0; u < PF; ++u) {
         const uint32_t i = u * GQ2 + t;
         pfs[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < n2) pfs[u] = src[i];
       }
+    };
+    auto request = [&](uint32_t j, float4 (&pfs)[PF]) {
+      request_at(table + (size_t)(b0 + j) * 2 * ((W + 1) / 2) * PE + slice0, pfs);
     };
     auto stage = [&](const float4 (&pfs)[PF]) {
 #pragma unroll
@@ -1109,14 +1221,14 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
         }
       }
     };
-    float segm = -INFINITY;
+    typename CELL::run segm = CELL::none();
     auto gather = [&](uint32_t j) {
       if (!mine) return;
-      f2 sum = {0.f, 0.f};
+      cell sum = CELL::zero();
 #pragma unroll
       for (int i = 0; i < PW; ++i) asm volatile("" : "+v"(cw[i]));   // keep the extracted addresses out of VGPRs (k_preplace_pairs)
       constexpr int WPB = PP_WPB, NBATCH = PW / WPB;
-      f2 rb[2][WPB * 2];
+      cell rb[2][WPB * 2];
       auto issue = [&](int bt) {
 #pragma unroll
         for (int w = 0; w < WPB; ++w) {
@@ -1132,23 +1244,36 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
         if (bt + 1 < NBATCH) issue(bt + 1);
 #pragma unroll
         for (int w = 0; w < WPB; ++w) {
-          const f2 s1 = rb[bt & 1][2 * w] + rb[bt & 1][2 * w + 1];  // (a0+a1) + (a2+a3), both branches
-          sum += s1;
+          const cell s1 = CELL::add(rb[bt & 1][2 * w], rb[bt & 1][2 * w + 1]);  // (a0+a1) + (a2+a3), every branch of the entry
+          sum = CELL::add(sum, s1);
         }
       }
       if (span & 3) {  // singles of the window tail, in order
-        sum += at(t0);
-        sum += at(t1);
-        sum += at(t2);
+        sum = CELL::add(sum, at(t0));
+        sum = CELL::add(sum, at(t1));
+        sum = CELL::add(sum, at(t2));
       }
-      segm = fmaxf(segm, fmaxf(sum.x, sum.y));
+      segm = CELL::track(segm, sum);
       const uint32_t bp = b0 + j;
-      if ((bp & 31u) == 31u || j + 1 == nb) {
-        atomicMax(&seg32[(size_t)qi * segp + (bp >> 5)], seg_key32(segm));
-        segm = -INFINITY;
+      if ((bp & (CELL::SEGC - 1u)) == CELL::SEGC - 1u || j + 1 == nb) {
+        atomicMax(&seg32[(size_t)qi * segp + bp / CELL::SEGC], CELL::key(segm));
+        segm = CELL::none();
       }
     };
     float4 pf[PF];
+    if (CELL::RELATIVE && item_t == 0) {   // C_q, once per read: base2 is laid out as one branch of lookup2
+      request_at(base2 + slice0, pf);
+      stage(pf);
+      __syncthreads();
+      if (mine) {
+        auto at64 = [&](uint32_t off) -> double { return *reinterpret_cast<const double*>(smem + off); };
+        double c = 0.0;
+#pragma unroll   // (fully: a dynamic index would move cw[] from registers to scratch)
+        for (int i = 0; i < PW; ++i) c += at64(cw[i] & 0xffffu) + at64(cw[i] >> 16);
+        if (span & 3) c += at64(t0) + at64(t1) + at64(t2);
+        cq[qi] = c;
+      }
+    }
     request(0, pf);
     for (uint32_t j = 0; j < nb; ++j) {
       __syncthreads();  // previous consumers of the slice are done
@@ -1169,30 +1294,41 @@ __global__ void __launch_bounds__(GQ2, 4) k_preplace_screen(
 // pass's SegTrack.  Every included (query, segment) cell is counted under the key s * KB + the query's sort key
 // (ccnt; the old value is its rank among equal keys, as in k_count_keys) for the cell sort.  mask[q]: the included
 // segments (0: not a query of the screen), *n_incl += their number.
+// I16 (the 16-bit screen): the keys are integers in units of h below C_q = cq[q], and the comparison is made in those
+// units: included when seg >= r - band_i, band_i = ceil((band_t + 2 delta) / h).  With the exact maximum of a segment
+// <= C_q + h seg + delta always, and >= C_q + h seg - delta where seg is above the floor, an excluded segment lies
+// more than band_t below the exact row maximum; its key is that of the upper bound C_q + h seg + delta.  A read whose
+// row maximum is the floor cannot be screened: every segment equals r, the comparison includes them all.
+template <bool I16>
 __global__ void __launch_bounds__(256) k_screen_band(const uint32_t* __restrict__ seg32, uint32_t Q, uint32_t nseg,
                                                      uint32_t seg32p, double band, double delta,
                                                      const uint32_t* __restrict__ qkeys, uint32_t KB,
                                                      unsigned long long* __restrict__ segmax, uint32_t segp,
                                                      uint32_t* __restrict__ ccnt, uint32_t* __restrict__ rank,
                                                      unsigned long long* __restrict__ mask,
-                                                     unsigned long long* __restrict__ n_incl) {
+                                                     unsigned long long* __restrict__ n_incl,
+                                                     const double* __restrict__ cq, double h, int band_i) {
   const uint32_t q = blockIdx.x * 256 + threadIdx.x;
   uint32_t cnt = 0;
   if (q < Q) {
     const uint32_t* row = seg32 + (size_t)q * seg32p;
     const uint32_t qk = qkeys[q];
     float r = -INFINITY;
+    uint32_t rk = 0;
     bool all = qk < KB;
     for (uint32_t s = 0; s < nseg; ++s) {
       const uint32_t k = row[s];
-      if (k) r = fmaxf(r, seg_val32(k)); else all = false;
+      if (!k) all = false;
+      else if (I16) rk = max(rk, k);
+      else r = fmaxf(r, seg_val32(k));
     }
     unsigned long long m = 0;
     if (all) {   // every segment has its key: a query the screening kernel served
-      const double lo = (double)r - band;
+      const double lo = (double)r - band, c = I16 ? cq[q] : 0.0;
+      const int lo_i = I16 ? seg_val16(rk) - band_i : 0;
       for (uint32_t s = 0; s < nseg; ++s) {
-        const double v = (double)seg_val32(row[s]);
-        if (v >= lo) {
+        const double v = I16 ? c + h * (double)seg_val16(row[s]) : (double)seg_val32(row[s]);
+        if (I16 ? seg_val16(row[s]) >= lo_i : v >= lo) {
           m |= 1ull << s;
           if (ccnt) rank[(size_t)q * seg32p + s] = atomicAdd(&ccnt[s * KB + qk], 1u);
         } else if (segmax) {
@@ -1504,12 +1640,74 @@ int launch_build_lookup2f(epa_ctx* ctx) {
   memcpy(&m, &h[0], 4);
   ctx->screen_M = (double)m;
   ctx->screen_nonfinite = h[1];
+  ctx->screen_stats = true;
   ctx->lookup2f = reinterpret_cast<float2*>(buf);
   return EPA_OK;
 }
 
+int launch_build_lookup2q(epa_ctx* ctx, uint32_t span_bound) {
+  if (ctx->lookup2q_refused) return EPA_OK;
+  if (!ctx->lookup2) return epa_fail(ctx, EPA_ERR_INVALID_ARG, "the 16-bit quad table needs the resident site-pair table");
+  const uint32_t BQ = (ctx->B + 3) / 4, n = 2 * ((ctx->W + 1) / 2) * PE;
+  if (!ctx->base2) {
+    const size_t bytes = sizeof(double) * n + sizeof(s4) * (size_t)BQ * n;
+    constexpr size_t SCREEN_RESERVE = (size_t)4 << 30;   // best effort, as launch_build_lookup2f
+    size_t free_b = 0, total_b = 0;
+    const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= bytes + 16 + SCREEN_RESERVE;
+    char *b2 = nullptr, *q = nullptr;
+    if (!room || hipMalloc(&b2, sizeof(double) * n + 16) != hipSuccess || hipMalloc(&q, sizeof(s4) * (size_t)BQ * n) != hipSuccess) {
+      (void)hipGetLastError();       // no room for them: the context keeps the fp32 screen
+      if (b2) (void)hipFree(b2);
+      ctx->lookup2q_refused = true;
+      return EPA_OK;
+    }
+    uint32_t* stats = reinterpret_cast<uint32_t*>(b2 + sizeof(double) * n);   // (the two statistics words behind base2)
+    uint32_t hs[4] = {0, 0, 0, 0};
+    hipError_t e = hipMemsetAsync(stats, 0, 16, ctx->stream);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_build_base2, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const double*)ctx->lookup2, ctx->W, ctx->B,
+                         reinterpret_cast<double*>(b2), stats);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hs, stats, 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(b2); (void)hipFree(q); EPA_HIP(ctx, e); }
+    float m;
+    memcpy(&m, &hs[0], 4);
+    ctx->screen_M = (double)m;
+    ctx->screen_nonfinite = hs[1];
+    ctx->screen_stats = true;
+    ctx->base2 = reinterpret_cast<double*>(b2);
+    ctx->lookup2q = q;
+    ctx->lookup2q_h = 0.0;
+  }
+  double h = 0.0;
+  if (epa_screen16_delta(ctx, span_bound, &h) < 0.0 || h == ctx->lookup2q_h) return EPA_OK;
+  // another quantum than the table's: no chunk of the other bank may still be reading it
+  if (ctx->lookup2q_h != 0.0) EPA_HIP(ctx, hipDeviceSynchronize());
+  for (uint32_t p0 = 0; p0 < BQ; p0 += EPA_GRID_Y)
+    hipLaunchKernelGGL(k_build_lookup2q, dim3((n + 255) / 256, std::min<uint32_t>(EPA_GRID_Y, BQ - p0)), dim3(256), 0, ctx->stream,
+                       (const double*)ctx->lookup2, (const double*)ctx->base2, ctx->W, ctx->B, 1.0 / h, reinterpret_cast<s4*>(ctx->lookup2q), p0);
+  EPA_HIP(ctx, hipGetLastError());
+  EPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->lookup2q_h = h;
+  return EPA_OK;
+}
+
+double epa_screen16_delta(const epa_ctx* ctx, uint32_t span_bound, double* h_out) {
+  if (!ctx->screen_stats || ctx->screen_nonfinite) return -1.0;
+  const double n = 2.0 * (span_bound >> 2) + 3.0;   // pair entries of the full quads + the tail singles
+  const double cq_err = (n + 2.0) * n * ctx->screen_M * 0x1p-53;
+  double h = 0.5;
+  while (h > 0x1p-40 && 0.5 * n * h + cq_err > 1.0) h *= 0.5;
+  h = ldexp(h, -std::min(std::max(ctx->opt.preplace_screen_i16_shift, 0), 20));
+  *h_out = h;
+  const double delta = (0.5 * n * h + cq_err) * (double)std::max(ctx->opt.preplace_screen_scale, 1);
+  return delta <= 1.0 ? delta : -1.0;
+}
+
 double epa_screen_delta(const epa_ctx* ctx, uint32_t span_bound) {
-  if (!ctx->lookup2f || ctx->screen_nonfinite) return -1.0;
+  if (!ctx->screen_stats || ctx->screen_nonfinite) return -1.0;
   const double u = 0x1p-24, n = 2.0 * (span_bound >> 2) + 3.0;   // pair entries of the full quads + the tail singles
   const double delta = 2.0 * (n + 1.0) * u * n * ctx->screen_M * (double)std::max(ctx->opt.preplace_screen_scale, 1);
   return delta <= 1.0 ? delta : -1.0;
@@ -1549,7 +1747,8 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
   const uint32_t max_runs_c = (uint32_t)std::min<uint64_t>((max_cells + GQ2 - 1) / GQ2 + n_blocks_c, 0xffffffu);
   const uint32_t max_groups_c = max_runs_c + n_blocks_c * n_buckets;
   const size_t smem_c = sizeof(uint32_t) * (2 * (n_blocks_c + 1) + 4 * (size_t)max_runs_c + 2);   // k_make_groups over the cells
-  double delta = -1.0;
+  double delta = -1.0, h16 = 0.0;
+  bool i16 = false;
   // Worth it only for large chunks: the band test, the cell sort (a scan, a scatter, a single-workgroup k_make_groups) and
   // the wider clear cost ~ 60 us per chunk whatever its size, and the table build ~ 5 ms once; the two passes gain ~ 0.16 ms
   // per 10^8 cells.  Measured (profiles/r9_preplace_screen_ab.txt): + 2.2 % at 100 000 reads x 1021 branches, a LOSS at 5 000
@@ -1559,14 +1758,29 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
   const bool big = ctx->opt.preplace_screen >= 2 || probe || (uint64_t)Q * ctx->B >= SCREEN_MIN_CELLS;
   if (pairs && !blocked && nseg <= 64 && max_span != 0 && max_span <= (uint32_t)CH && ctx->opt.preplace_screen && big &&
       (probe || (segmax && t.band_t > 0.0)) && max_cells < 0x80000000ull && smem_c <= 65536) {
-    // the context's first chunk that screens builds the fp32 table, once (a chunk of this size takes milliseconds itself)
-    const int brc = launch_build_lookup2f(ctx);
-    if (brc) return brc;
-    delta = epa_screen_delta(ctx, span_bound);
+    // The context's first chunk that screens builds its table, once (a chunk of this size takes milliseconds itself).
+    // The 16-bit screen (option preplace_screen_i16, default) is taken exactly where the fp32 screen would be -- the fp32
+    // bound must hold as well -- and its own scaled bound allows it; else the fp32 screen; else one pass.  lookup2f is only
+    // built when that second route (or the fp32 probe) is actually needed.
+    if (probe ? probe->i16 : ctx->opt.preplace_screen_i16 != 0) {   // (a probe names its screen itself)
+      const int qrc = launch_build_lookup2q(ctx, span_bound);
+      if (qrc) return qrc;
+      const double d16 = epa_screen16_delta(ctx, span_bound, &h16);
+      if (ctx->lookup2q && d16 >= 0.0 && ctx->lookup2q_h == h16 && epa_screen_delta(ctx, span_bound) >= 0.0) {
+        i16 = true;
+        delta = d16;
+      }
+    }
+    if (!i16 && !(probe && probe->i16)) {
+      const int brc = launch_build_lookup2f(ctx);
+      if (brc) return brc;
+      if (ctx->lookup2f) delta = epa_screen_delta(ctx, span_bound);
+    }
   }
   const bool screen = delta >= 0.0;
   uint32_t *seg32, *cstatus, *ccnt, *crank, *csorted, *cperm;
   unsigned long long *seg_mask, *n_incl;
+  double* cq;
   Group* cgroups;
   Group* groups;
   uint16_t *packed, *tails;
@@ -1586,6 +1800,7 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
     packed = c.take<uint16_t>((size_t)Q * NP16);
     tails = c.take<uint16_t>((pairs || sites) ? 4 * (size_t)Q : 0);
     seg_mask = c.take<unsigned long long>(screen ? Q : 0);
+    cq = c.take<double>(i16 ? Q : 0);
     crank = c.take<uint32_t>(screen ? (size_t)Q * seg32p : 0);
     csorted = c.take<uint32_t>(screen ? max_cells : 0);
     cperm = c.take<uint32_t>(screen ? max_cells : 0);
@@ -1679,13 +1894,15 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
   if (probe) probe->ran = screen;
   if (probe && !screen) return EPA_OK;
   if (screen) {
-    using ScreenKernel = decltype(&k_preplace_screen<SPREAD, ROWL_NARROW>);
-    const ScreenKernel k_screen = wide ? k_preplace_screen<SPREAD_WIDE, ROWL_PACKED> : k_preplace_screen<SPREAD, ROWL_NARROW>;
+    using ScreenKernel = decltype(&k_preplace_screen<ScreenF32, SPREAD, ROWL_NARROW>);
+    using Screen16Kernel = decltype(&k_preplace_screen<ScreenI16, SPREAD, ROWL_NARROW>);
+    const ScreenKernel k_screen = wide ? k_preplace_screen<ScreenF32, SPREAD_WIDE, ROWL_PACKED> : k_preplace_screen<ScreenF32, SPREAD, ROWL_NARROW>;
+    const Screen16Kernel k_screen16 = wide ? k_preplace_screen<ScreenI16, SPREAD_WIDE, ROWL_PACKED> : k_preplace_screen<ScreenI16, SPREAD, ROWL_NARROW>;
     const FastKernel k_exact = wide ? k_preplace_pairs<false, SPREAD_WIDE, ROWL_PACKED, true> : k_preplace_pairs<false, SPREAD, ROWL_NARROW, true>;
     const size_t lds_scr = wide ? (size_t)((CH + SPREAD_WIDE) / 2) * ROWL_PACKED : (size_t)TROWS2 * ROWL_NARROW;
-    EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_screen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scr));
+    EPA_HIP(ctx, hipFuncSetAttribute(i16 ? (const void*)k_screen16 : (const void*)k_screen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scr));
     EPA_HIP(ctx, hipFuncSetAttribute((const void*)k_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast));
-    const uint32_t BP = (ctx->B + 1) / 2;
+    const uint32_t BP = i16 ? (ctx->B + 3) / 4 : (ctx->B + 1) / 2;   // table entries' worth of branches: quads or pairs
     struct Events {   // the probe's three stamps, destroyed on every way out
       hipEvent_t e[3] = {nullptr, nullptr, nullptr};
       ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
@@ -1695,12 +1912,20 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
     if (probe) EPA_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     else epa_timer_start(ctx, epa_t(ctx, epa_ctx::T_PREPLACE));
     const dim3 grid_s((uint32_t)std::min<uint64_t>((uint64_t)max_groups * ((BP + 15) / 16), (uint64_t)ctx->n_cu));
-    hipLaunchKernelGGL(k_screen, grid_s, dim3(GQ2), (uint32_t)lds_scr, ctx->stream, (const float2*)ctx->lookup2f, (const uint16_t*)packed,
-                       (const uint16_t*)tails, d_begin, d_span, perm, groups, ctx->W, BP, NP16, status, seg32, seg32p);
+    if (i16)
+      hipLaunchKernelGGL(k_screen16, grid_s, dim3(GQ2), (uint32_t)lds_scr, ctx->stream, (const s4*)ctx->lookup2q, (const uint16_t*)packed,
+                         (const uint16_t*)tails, d_begin, d_span, perm, groups, ctx->W, BP, NP16, status, seg32, seg32p,
+                         (const double*)ctx->base2, cq);
+    else
+      hipLaunchKernelGGL(k_screen, grid_s, dim3(GQ2), (uint32_t)lds_scr, ctx->stream, (const f2*)ctx->lookup2f, (const uint16_t*)packed,
+                         (const uint16_t*)tails, d_begin, d_span, perm, groups, ctx->W, BP, NP16, status, seg32, seg32p,
+                         (const double*)nullptr, (double*)nullptr);
     if (probe) EPA_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
     const double band = (probe ? probe->band_t : t.band_t) + 2.0 * delta;
-    hipLaunchKernelGGL(k_screen_band, dim3((Q + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)seg32, Q, nseg, seg32p, band,
-                       delta, (const uint32_t*)keys, KB, probe ? nullptr : segmax, segp, probe ? nullptr : ccnt, crank, seg_mask, n_incl);
+    const int band_i = i16 ? (int)std::min(std::ceil(band / h16), 1e9) : 0;   // the band in units of h, rounded outwards
+    hipLaunchKernelGGL(i16 ? k_screen_band<true> : k_screen_band<false>, dim3((Q + 255) / 256), dim3(256), 0, ctx->stream,
+                       (const uint32_t*)seg32, Q, nseg, seg32p, band, delta, (const uint32_t*)keys, KB, probe ? nullptr : segmax, segp,
+                       probe ? nullptr : ccnt, crank, seg_mask, n_incl, (const double*)cq, h16, band_i);
     if (probe) {
       EPA_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
       EPA_HIP(ctx, hipGetLastError());
@@ -1708,6 +1933,8 @@ int launch_preplace(epa_ctx* ctx, const uint8_t* d_codes, const uint32_t* d_begi
       (void)hipEventElapsedTime(&probe->ms_screen, ev[0], ev[1]);
       (void)hipEventElapsedTime(&probe->ms_band, ev[1], ev[2]);
       probe->delta = delta;
+      probe->h = h16;
+      probe->cq = cq;
       probe->seg32 = seg32;
       probe->mask = seg_mask;
       probe->n_incl = n_incl;

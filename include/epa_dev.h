@@ -259,6 +259,12 @@ int epa_dev_set_stream(epa_ctx* ctx, void* hip_stream);
  *                          the site-pair table's size, if 4 GiB stay free behind it)
  *   "preplace_screen_scale" n: test only, the screen's error bound is multiplied by n >= 1 (default 1); a bound above
  *                          1 lnL unit turns the screen off for the context
+ *   "preplace_screen_i16" 0: the screen runs in fp32 over branch pairs (default 1: where the fp32 screen would run, and a
+ *                          16-bit bound of at most 1 lnL unit holds, it runs over branch quads in 16-bit fixed point relative
+ *                          to the per-slot maximum over the branches, quantum h = the largest power of two with bound <= 1,
+ *                          2^-6 for 150-site reads; its tables take a quarter of the site-pair table's size, under the same
+ *                          4 GiB rule, and the fp32 table is then not built; same candidates, same results)
+ *   "preplace_screen_i16_shift" n: test only, h is made smaller by n powers of two (default 0): sums saturate earlier
  * Unknown key: EPA_ERR_INVALID_ARG.
  */
 int epa_dev_set_option(epa_ctx* ctx, const char* key, int value);
@@ -385,6 +391,16 @@ int epa_dev_preplace_bounded(epa_ctx* ctx, const uint8_t* q_codes, const uint32_
 int epa_dev_preplace_screen_probe(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
                                   const uint32_t* win_span, uint32_t Q, uint32_t max_span, double threshold,
                                   float* seg32, uint64_t* seg_mask, double* info);
+/* Internal (tests and measurements): the same for the 16-bit screen (four branches per table entry in fixed point relative
+ * to the per-slot maximum over the branches), whatever "preplace_screen_i16" says.  seg16 [Q][nseg] (or null):
+ * the relative integer maxima of the segments in units of h, -32768 = at most the floor, INT32_MIN = no key; cq [Q] (or
+ * null): C_q, so that C_q + h seg16 + delta bounds a segment's exact maximum from above, and from below by 2 delta less
+ * where seg16 is above the floor; seg_mask as above; info [8]: 0 the screen ran (the fp32 screen's conditions and its own
+ * delta <= 1), 1 delta, 2 the included cells, 3 h, 4 the reads that could not be screened (row maximum at the floor: all
+ * their segments are included), 5 band_t, 6 / 7 the kernels' times in ms. */
+int epa_dev_preplace_screen16_probe(epa_ctx* ctx, const uint8_t* q_codes, const uint32_t* win_begin,
+                                    const uint32_t* win_span, uint32_t Q, uint32_t max_span, double threshold,
+                                    int32_t* seg16, double* cq, uint64_t* seg_mask, double* info);
 /* Internal (tests): the number of chunk bodies of this context whose preplacement took the screen's two-pass route. */
 uint64_t epa_dev_preplace_screen_runs(const epa_ctx* ctx);
 
